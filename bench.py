@@ -7,9 +7,14 @@ A "step" is one pass of the hot path over one synthetic volume that is already r
 `value` = region merges per second over the whole step (all ranks; weak scaling: every rank owns its own volume,
 the merge loop does not shard -- SURVEY.md 8e).  `roofline` describes the dominant streaming kernel
 (rag_accumulate: 8 algorithmic bytes per voxel), timed live with HIP events on the library's stream.
-`cpu_baseline` times the oracle (the CPU restatement of GLIA's algorithm) on a bounded sub-volume on this host.
-With N > 1 an extra, separately timed phase (`slab_rag`) splits ONE volume into z-slabs across the ranks and exchanges
-the partial region/pair records over RCCL (glia_amd/slab.py).
+A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs DIR also writes what the last
+timed step returned (rank 0).  Everything else runs with --full only, after the timed steps:
+  `verify`        digests of the last step's merge order / saliencies against recorded ones;
+  `bc_loop`       the classifier-linkage merge tree of the same volume, timed once (--no-bc skips it);
+  `cpu_baseline`  the oracle (the CPU restatement of GLIA's algorithm) and the reference's own engine on bounded
+                  sub-volumes on this host (--no-cpu skips it);
+  `slab_rag`      with N > 1 (or --force-slab), ONE volume split into z-slabs across the ranks, the partial region/pair
+                  records exchanged over RCCL (--no-slab skips it).
 """
 import argparse
 import json
@@ -85,6 +90,7 @@ def openmp_bc_feat_baseline(size, S):
     per merge: edge-features/s = merges / seconds of the two parfor loops + serialisation (the region map's set-up excluded)."""
     import subprocess
     ncpu = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    nthr = int(os.environ.get("OMP_NUM_THREADS") or ncpu)        # a thread count the environment sets is the one this host grants
     st = os.path.join(ROOT, "oracle", "_ref", "ref_parfor_st"); mt = os.path.join(ROOT, "oracle", "_ref", "ref_parfor_mt")
     if not (os.path.exists(st) and os.path.exists(mt)):
         return None
@@ -92,7 +98,7 @@ def openmp_bc_feat_baseline(size, S):
                      "reference parfor (util/mp.hxx built in place) over the oracle's RegionFeats / BoundaryFeats restatement" % (size, S),
            "cores_available": ncpu, "kind": "reference parfor + port features", "threads": [], "seconds": [], "edge_features_per_sec": []}
     fnv = set()
-    for exe, threads in ((st, 1), (mt, ncpu)):
+    for exe, threads in ((st, 1), (mt, nthr)):
         try:
             res = subprocess.run([exe, str(size), str(S)], capture_output=True, text=True, check=True, timeout=600,
                                  env=dict(os.environ, OMP_NUM_THREADS=str(threads)))
@@ -236,6 +242,29 @@ def slab_phase(ctx, hmt, dist, torch, size, S, world, rank, clf):
     return out
 
 
+def world_size():
+    return int(os.environ.get("WORLD_SIZE", "1"))
+
+
+OUTPUT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(d, arrays):
+    """arrays: {name: array with one row per item} -> d/<name>.npy as float64.  Above OUTPUT_BYTES together, every array keeps
+    the same fixed, seeded sample of its rows, and d/<name>_rows.npy holds the row numbers kept."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = sum(8 * a.size for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.asarray(a, np.float64)
+        if total > OUTPUT_BYTES:                 # half the budget for the rows, at most as much again for their numbers
+            keep = max(1, len(a) * OUTPUT_BYTES // (2 * total))
+            rows = np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False)).astype(np.float64)
+            np.save(os.path.join(d, name + "_rows.npy"), rows)
+            a = a[rows.astype(np.int64)]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -251,8 +280,15 @@ def main():
     ap.add_argument("--no-bc", action="store_true", help="skip the classifier-linkage merge tree (timed once, outside the steps)")
     ap.add_argument("--no-slab", action="store_true", help="N > 1: skip the z-slab split + RCCL exchange phase")
     ap.add_argument("--slab-timeout", type=int, default=240)
-    ap.add_argument("--force-slab", action="store_true", help="rehearse the slab phase with a 1-rank RCCL group (N = 1)")
+    ap.add_argument("--force-slab", action="store_true", help="with --full: rehearse the slab phase with a 1-rank RCCL group (N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also the digest check, the classifier-linkage merge tree, the CPU baselines and the slab phase")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the merge order and saliencies the last timed step returned to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    slab = args.full and (world_size() > 1 or args.force_slab) and not args.no_slab
 
     import tempfile
     import torch
@@ -262,11 +298,11 @@ def main():
 
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    world = world_size()
     torch.cuda.set_device(local)
     if world > 1:
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    elif args.force_slab:
+    elif slab:
         dist.init_process_group("nccl", init_method="tcp://127.0.0.1:29517", rank=0, world_size=1,
                                 device_id=torch.device("cuda", local))
 
@@ -306,7 +342,7 @@ def main():
         rm.close()
         t_e = time.time()
         info["host_ms"] = dict(build=(t_b - t_a) * 1e3, score=(t_c - t_b) * 1e3, merge_order=(t_d - t_c) * 1e3, close=(t_e - t_d) * 1e3)
-        info["_result"] = (order, sal)          # hashed after the timed region (the `verify` field)
+        info["_result"] = (order, sal)          # dumped / hashed after the timed region (--dump-outputs, the `verify` field)
         return info
 
     for _ in range(args.warmup):
@@ -327,6 +363,9 @@ def main():
     else:
         merges = float(sum(i["merges"] for i in infos))
         edges = float(sum(i["n_edges"] for i in infos))
+    if rank == 0 and args.dump_outputs:
+        o_, s_ = infos[-1]["_result"]
+        dump_outputs(args.dump_outputs, {"pb_mean_order": o_, "pb_mean_saliency": s_})
 
     # `verify`: digests of the LAST timed step's whole merge order / saliency arrays, computed outside the timed region, against the
     # digests tests/test_gpu_headline.py gates (recorded from kernels that were bit-identical to the oracle wherever it finishes)
@@ -338,7 +377,7 @@ def main():
                 (512, 16): ("8e620b69eab2cc31991eaca662446f52ad2231df", "8e30e7ba92d7b89dc09c413260a0841df1cbf886"),
                 (1024, 16): ("6d930d8a816d75d194b20c5f4eb068a3bd362f3f", "1915075dc494d7c5b56baea947414d1890c2d8f8")}
     verify = None
-    if rank == 0:
+    if rank == 0 and args.full:
         o_, s_ = infos[-1]["_result"]
         got = (sha(o_), sha(s_))
         exp = known_pb.get((args.size, args.S))
@@ -347,7 +386,7 @@ def main():
     for i_ in infos:
         i_.pop("_result", None)
     bc_loop = None
-    if rank == 0 and not args.no_bc:
+    if rank == 0 and args.full and not args.no_bc:
         # the north-star linkage: the classifier-driven merge tree (util/struct_merge_bc.hxx:10-58) of the SAME volume, every
         # new edge featurised (D_f doubles) and scored by the 255-tree forest inside the greedy loop; timed once, outside `value`
         rm = hmt.RegionMap(ctx, labels, pb=pb, only_contour=False, cfg=cfg)
@@ -392,7 +431,6 @@ def main():
                        "initial_edges": infos[0]["n_edges"], "merges_per_step": infos[0]["merges"],
                        "parallelism": "replica x%d (the merge loop does not shard)" % world},
             "edge_features_per_sec": edges / dt,
-            "verify": verify,
             # calls that ended with GLIA_HMT_ERR_INTERNAL (a loop's own consistency stop, or an order that failed the O(R) replay of
             # glia_hmt_check_merge_order); the library never runs a loop twice, so a healthy line carries 0 here
             "internal_errors": hmt.Context.internal_errors(),
@@ -406,9 +444,11 @@ def main():
                          "traffic_source": "profiles/acc_traffic.json (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE of tools/acc_bench.py, separate passes; not measured in this run)",
                          "algorithmic_bytes_per_launch": infos[0]["acc_bytes"], "avg_launch_ms": acc_ms},
         }
+        if verify is not None:
+            out["verify"] = verify
         if bc_loop is not None:
             out["bc_loop"] = bc_loop
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             curve = tuple(int(x) for x in args.cpu_curve.split(",") if x)
             out["cpu_baseline"] = cpu_baseline(args.cpu_size, args.S, args.cpu_bc_size, curve, infos[0]["R"])
             # the OpenMP leg, and the SAME sample through the library's bc_feat (given order, no queue) for a like-for-like ratio
@@ -436,7 +476,7 @@ def main():
                 out["slab_rag"] = slab_info     # z-slab split of ONE volume + RCCL record exchange
             print(json.dumps(out), flush=True)
 
-    if (world > 1 or args.force_slab) and not args.no_slab:
+    if slab:
         # Outside the timed region and never allowed to take the bench line down: an exception is reported inside the
         # line, a hang (a collective that never completes) is cut by a watchdog that emits the line without it.
         import threading
@@ -458,7 +498,7 @@ def main():
         emit(slab_info)
     else:
         emit(None)
-    if world > 1 or args.force_slab:
+    if dist.is_initialized():
         dist.destroy_process_group()
 
 

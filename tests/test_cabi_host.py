@@ -1,5 +1,6 @@
 """CPU-only checks of the C ABI: the library loads, exports every symbol include/glia_hmt.h declares (no compute
-calls without a GPU), and its host-side RF model parser agrees with the reference's own reader/writer."""
+calls without a GPU), and its host-side RF model parser agrees with the reference's own reader/writer (runs of
+oracle/_ref/ref_rfmodel recorded in tests/golden/reference/runs.npz, tests/_refruns.py)."""
 import ctypes as C
 import os
 import re
@@ -9,11 +10,11 @@ import tempfile
 import numpy as np
 import pytest
 
+import _refruns
 import _rf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SO = os.path.join(ROOT, "glia_amd", "libglia_hmt.so")
-REF = os.path.join(ROOT, "oracle", "_ref", "ref_rfmodel")
 
 
 def _lib():
@@ -93,13 +94,6 @@ def test_model_parser_matches_python_writer(sparse):
     assert (meta[..., 3][used & term] == (forest["nodeclass"][used & term] == 1)).all()     # class 1 <-> label -1
 
 
-def _ensure_ref():
-    if not os.path.exists(REF) and os.path.isdir("/root/reference/code"):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], stdout=subprocess.DEVNULL)
-    if not os.path.exists(REF):
-        pytest.skip("oracle/_ref/ref_rfmodel not built and /root/reference absent")
-
-
 def _ref_text(forest):
     ntree, nrnodes = forest["xbestsplit"].shape
     nclass = len(forest["orig_labels"])
@@ -119,15 +113,15 @@ def _ref_text(forest):
 
 
 def test_parser_reads_files_written_by_the_reference_writer():
-    """rf_old::writeModelToBinaryFile (built in place from /root/reference) -> our parser."""
-    _ensure_ref()
+    """rf_old::writeModelToBinaryFile (the reference's writer built in place) -> our parser."""
     lib = _lib()
     rng = np.random.default_rng(11)
     forest = _rf.random_forest(rng, 33, 7, rng.random((80, 20)))     # > 128 nodes/array: exercises the sparse encoder
+    written = _refruns.run("ref_rfmodel", ["write", "{in}/f.txt", "{out}/m.bin"], files={"f.txt": _ref_text(forest).encode()},
+                           outputs=["m.bin"])[1]
     with tempfile.TemporaryDirectory() as d:
-        txt, p = os.path.join(d, "f.txt"), os.path.join(d, "m.bin")
-        open(txt, "w").write(_ref_text(forest))
-        subprocess.check_call([REF, "write", txt, p])
+        p = os.path.join(d, "m.bin")
+        open(p, "wb").write(written["m.bin"])
         split, meta = _parse(lib, p)
     used = np.arange(split.shape[1])[None, :] < forest["ndbigtree"][:, None]
     inner = used & (forest["nodestatus"] != -1)
@@ -138,13 +132,12 @@ def test_parser_reads_files_written_by_the_reference_writer():
 
 def test_reference_reader_reads_files_written_by_our_test_writer():
     """tests/_rf.write_model (same layout as glia_amd.synth_forest) -> rf_old::readModelFromBinaryFile."""
-    _ensure_ref()
     rng = np.random.default_rng(5)
     forest = _rf.random_forest(rng, 17, 6, rng.random((60, 10)))
     with tempfile.TemporaryDirectory() as d:
         p = os.path.join(d, "m.bin")
         _rf.write_model(p, forest)
-        out = subprocess.run([REF, "read", p], capture_output=True, text=True, check=True).stdout
+        out = _refruns.run("ref_rfmodel", ["read", "{in}/m.bin"], files={"m.bin": open(p, "rb").read()})[0]
     rows = {l.split()[0]: l.split()[1:] for l in out.strip().split("\n")}
     assert rows["sizeof_model"] == ["520"]
     xb = np.array(rows["xbestsplit"][2:], dtype=np.float64)

@@ -2,7 +2,8 @@
 
 Covers TBoundaryTable (type/boundary_table.hxx), TRegion/TRegionMap merge + boundaryWith
 (type/region.hxx, type/region_map.hxx) and genMergeOrderGreedy (util/struct_merge.hxx:13-33).
-The binary is built by `make -C oracle ref` where /root/reference exists and travels prebuilt otherwise.
+The reference's answers come from tests/golden/reference/runs.npz, recorded from the binaries `make -C oracle ref` builds in
+place (tests/_refruns.py: a recorded answer is used only for the input it was recorded from).
 """
 import os
 import subprocess
@@ -11,16 +12,10 @@ import tempfile
 import numpy as np
 import pytest
 
+import _refruns
 from oracle import pyoracle as O
 
 REF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "ref_engine")
-
-
-def _ensure_ref():
-    if not os.path.exists(REF) and os.path.isdir("/root/reference/code"):
-        subprocess.check_call(["make", "-C", os.path.dirname(os.path.dirname(REF)), "ref"], stdout=subprocess.DEVNULL)
-    if not os.path.exists(REF):
-        pytest.skip("oracle/_ref/ref_engine not built and /root/reference absent")
 
 
 def run_ref(rag, pb, type, upd, cond=None, want_keys=False):
@@ -31,8 +26,8 @@ def run_ref(rag, pb, type, upd, cond=None, want_keys=False):
         if cond is not None:
             with open(p, "a") as f:
                 f.write("%d %s %r\n" % (len(cond[0]), " ".join(str(int(t)) for t in cond[0]), float(cond[1])))
-        with open(p) as f:
-            out = subprocess.run([REF], stdin=f, capture_output=True, text=True, check=True).stdout
+        with open(p, "rb") as f:
+            out = _refruns.run("ref_engine", stdin=f.read())[0]
     rows = [l.split() for l in out.strip().split("\n") if l]
     keys = [r for r in rows if r[0] == "K"]
     rows = [r for r in rows if r[0] != "K"]
@@ -50,7 +45,6 @@ CASES = [((32, 32, 32), 8, 16, 0), ((40, 36, 28), 6, 12, 1), ((96, 96), 8, 32, 0
 @pytest.mark.parametrize("only_contour,type,upd", [(True, 1, False), (True, 2, False), (False, 1, True),
                                                    (False, 2, True), (False, 2, False)])
 def test_engine_matches_reference(shape, S, G, variant, only_contour, type, upd):
-    _ensure_ref()
     lab, pb = O.synth(shape, S, G, variant=variant)
     rag = O.Rag(lab, only_contour=only_contour)
     ro, rs = run_ref(rag, pb, type, upd)
@@ -60,7 +54,6 @@ def test_engine_matches_reference(shape, S, G, variant, only_contour, type, upd)
 
 
 def test_constant_pb_tie_torture():
-    _ensure_ref()
     lab, _ = O.synth((24, 24, 24), 6, 12)
     pb = np.full(lab.shape, 0.25, np.float32)
     rag = O.Rag(lab, only_contour=True)
@@ -73,7 +66,6 @@ def test_constant_pb_tie_torture():
 @pytest.mark.parametrize("only_contour,type,upd", [(True, 2, False), (False, 1, True)])
 def test_transform_keys_matches_reference(shape, S, G, variant, only_contour, type, upd):
     """transformKeys (util/struct_merge.hxx:188-210) of the reference's own order vs the oracle's restatement"""
-    _ensure_ref()
     lab, pb = O.synth(shape, S, G, variant=variant)
     rag = O.Rag(lab, only_contour=only_contour)
     ro, _, keys = run_ref(rag, pb, type, upd, want_keys=True)
@@ -84,7 +76,6 @@ def test_transform_keys_matches_reference(shape, S, G, variant, only_contour, ty
 
 def test_transform_keys_of_a_partial_order_matches_reference():
     """a pre_merge order is a forest: several final keys, untouched labels absent from the map"""
-    _ensure_ref()
     lab, pb = O.synth((36, 40, 28), 6, 12)
     rag = O.Rag(lab, only_contour=False)
     ro, _, keys = run_ref(rag, pb, 2, True, cond=([150], 0.0), want_keys=True)
@@ -104,7 +95,6 @@ PRE_MERGE = [((32, 32, 32), 8, 16, 0, [300], 0.0), ((32, 32, 32), 8, 16, 0, [200
 def test_pre_merge_condition_matches_reference(shape, S, G, variant, sizes, rpb):
     """the fcond path of TBoundaryTable::top (type/boundary_table.hxx:46-52) in the reference's own code, with the size rule of
     gadget/main_pre_merge.cxx:27-76 restated in the driver, vs the oracle's pre_merge"""
-    _ensure_ref()
     lab, pb = O.synth(shape, S, G, variant=variant)
     rag = O.Rag(lab, only_contour=False)
     ro, rs = run_ref(rag, pb, 2, True, cond=(sizes, rpb))
@@ -116,26 +106,18 @@ def test_pre_merge_condition_matches_reference(shape, S, G, variant, sizes, rpb)
 
 
 # ---- type/function.hxx ThresholdModelDistributor, util/text_io.hxx writeData / readData (oracle/_ref/ref_misc) ----
-REF_MISC = os.path.join(os.path.dirname(REF), "ref_misc")
 TEXT_IO_CHECK = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cli", "text_io_check")
-
-
-def _ensure_misc():
-    _ensure_ref()
-    if not os.path.exists(REF_MISC):
-        pytest.skip("oracle/_ref/ref_misc not built")
 
 
 @pytest.mark.parametrize("seed", range(6))
 def test_model_distributor_matches_reference(seed):
-    _ensure_misc()
     rng = np.random.default_rng(500 + seed)
     D = int(rng.integers(2, 12)); n = 200
     dim0, dim1 = int(rng.integers(0, D)), int(rng.integers(0, D))
     thr = float(np.round(1 + rng.random() * 6) / 8)
     x = np.round(rng.random((n, D)) * 8) / 8                 # exact hits on the threshold included
     text = "%d %d %r %d %d\n" % (dim0, dim1, thr, n, D) + "\n".join(" ".join(repr(float(v)) for v in row) for row in x) + "\n"
-    out = subprocess.run([REF_MISC, "dist"], input=text, capture_output=True, text=True, check=True).stdout.split()
+    out = _refruns.run("ref_misc", ["dist"], stdin=text)[0].split()
     ref = np.array([int(t) for t in out])
     got = np.array([O.pick_model(dim0, dim1, thr, row) for row in x])
     assert (ref == got).all() and len(set(ref)) > 1
@@ -145,7 +127,6 @@ def test_model_distributor_matches_reference(seed):
 def test_text_writers_match_reference_bytes(seed):
     """merge order / saliency / feature-row files of the tools (cli/text_io.hpp) vs writeData of util/text_io.hxx:103-133 at the
     call sites' precisions (default, FLT_PREC = 8), byte for byte; and the reference's readData reads them back"""
-    _ensure_misc()
     if not os.path.exists(TEXT_IO_CHECK):
         subprocess.check_call(["make", "-C", os.path.dirname(TEXT_IO_CHECK), "text_io_check"], stdout=subprocess.DEVNULL)
     rng = np.random.default_rng(900 + seed)
@@ -157,25 +138,20 @@ def test_text_writers_match_reference_bytes(seed):
     sal = np.concatenate([sal, [0.0, -0.0, 1e-7, 123456.7, 1234567.0]])
     text = "%d\n" % len(order) + "".join("%d %d %d\n" % tuple(r) for r in order) + "%d\n" % len(sal) + \
            "".join("%r\n" % float(v) for v in sal) + "%d %d\n" % (rows, cols) + "".join("%r\n" % float(v) for v in feats.ravel())
-    with tempfile.TemporaryDirectory() as a, tempfile.TemporaryDirectory() as b:
-        out = subprocess.run([REF_MISC, "write", a], input=text, capture_output=True, text=True, check=True).stdout.split()
+    names = ("order.txt", "sal.txt", "feats.txt")
+    out, written = _refruns.run("ref_misc", ["write", "{out}"], stdin=text, outputs=names)
+    out = out.split()
+    with tempfile.TemporaryDirectory() as b:
         subprocess.run([TEXT_IO_CHECK, b], input=text, capture_output=True, text=True, check=True)
-        for name in ("order.txt", "sal.txt", "feats.txt"):
-            with open(os.path.join(a, name), "rb") as fa, open(os.path.join(b, name), "rb") as fb:
-                assert fa.read() == fb.read(), name
+        for name in names:
+            with open(os.path.join(b, name), "rb") as fb:
+                assert written[name] == fb.read(), name
     assert out == ["roundtrip", "1", "1", str(rows), str(cols), str(rows * cols)]
 
 
 # ---- merge tree: genTree / genTreeWithNodePotentials / resolveTreeGreedy (hmt/tree_build.hxx, hmt/tree_greedy.hxx) ----
-REF_TREE = os.path.join(os.path.dirname(REF), "ref_tree")
-REF_STATS = os.path.join(os.path.dirname(REF), "ref_stats")
-
-
 def run_ref_tree(trees):
     """trees: list of (order, merge_probs | None, region_probs | None) -> per-tree node arrays, single picks, joint picks"""
-    _ensure_ref()
-    if not os.path.exists(REF_TREE):
-        pytest.skip("oracle/_ref/ref_tree not built")
     lines = ["%d" % len(trees)]
     for order, mp, rp in trees:
         lines.append("%d %d %d" % (len(order), mp is not None, rp is not None))
@@ -184,7 +160,7 @@ def run_ref_tree(trees):
             lines += [repr(float(p)) for p in mp]
         if rp is not None:
             lines += [repr(float(p)) for p in rp]
-    out = subprocess.run([REF_TREE], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout.split("\n")
+    out = _refruns.run("ref_tree", stdin="\n".join(lines) + "\n")[0].split("\n")
     k = 0
     nodes = []
     for _ in trees:
@@ -244,9 +220,6 @@ def test_tree_potentials_and_greedy_picks_match_reference(seed):
 @pytest.mark.parametrize("seed", range(20))
 def test_stats_match_reference(seed):
     """entropy / distL1 / distX2 / amedian / rescale restatements vs util/stats.hxx compiled in place"""
-    _ensure_ref()
-    if not os.path.exists(REF_STATS):
-        pytest.skip("oracle/_ref/ref_stats not built")
     rng = np.random.default_rng(100 + seed)
     cases = []
     for _ in range(25):
@@ -259,7 +232,7 @@ def test_stats_match_reference(seed):
         cases.append((a, b))
     text = "%d\n" % len(cases) + "".join("%d\n%s\n%s\n" % (len(a), " ".join(repr(float(x)) for x in a), " ".join(repr(float(x)) for x in b))
                                          for a, b in cases)
-    out = subprocess.run([REF_STATS], input=text, capture_output=True, text=True, check=True).stdout.strip().split("\n")
+    out = _refruns.run("ref_stats", stdin=text)[0].strip().split("\n")
     for i, (a, b) in enumerate(cases):
         ref = np.array([float(x) for x in out[2 * i].split()])
         got = O.stats_case(a, b)
@@ -268,26 +241,20 @@ def test_stats_match_reference(seed):
         assert (O.rescale(a, np.minimum(a, b), np.maximum(a, b)) == rs).all()
 
 
-def test_bc_feat_under_the_reference_parfor_equals_the_serial_oracle(tmp_path):
+def test_bc_feat_under_the_reference_parfor_equals_the_serial_oracle():
     """oracle/_ref/ref_parfor_{st,mt}: the reference's util/mp.hxx (parfor, compiled in place without / with -DGLIA_MT -fopenmp) drives
     the oracle's feature functions over a merge order the way hmt/main_bc_feat.cxx:57-101 does (shuffled indices, two loops).  Both
     builds, and the OpenMP one on 1 and 4 threads, must write the rows of the oracle's own serial bc_feat byte for byte: the baseline
     bench.py times (cpu_baseline.bc_feat) computes what the checker computes."""
-    _ensure_ref()
-    st = os.path.join(os.path.dirname(REF), "ref_parfor_st")
-    mt = os.path.join(os.path.dirname(REF), "ref_parfor_mt")
-    if not (os.path.exists(st) and os.path.exists(mt)):
-        pytest.skip("oracle/_ref/ref_parfor_* not built")
     size, S = 40, 8
     labels, pb = O.synth((size,) * 3, S, 8 * S)
     order, _ = O.Rag(labels, only_contour=True).merge_order_pb(pb, type=2)
     cfg = O.make_cfg(pb, rb=[(pb, 8, 0.0, 1.0)])
     want = O.Rag(labels).bc_feat(cfg, order)
-    for exe, threads in ((st, 1), (mt, 1), (mt, 4)):
-        out = str(tmp_path / "rows.bin")
-        env = dict(os.environ, OMP_NUM_THREADS=str(threads))
-        line = subprocess.run([exe, str(size), str(S), out], capture_output=True, text=True, check=True, env=env).stdout.split()
+    for exe, threads in (("ref_parfor_st", 1), ("ref_parfor_mt", 1), ("ref_parfor_mt", 4)):
+        line, written = _refruns.run(exe, [size, S, "{out}/rows.bin"], outputs=["rows.bin"], env={"OMP_NUM_THREADS": str(threads)})
+        line = line.split()
         kv = dict(zip(line[0::2], line[1::2]))
         assert int(kv["threads"]) == threads and int(kv["merges"]) == len(order) and int(kv["dim"]) == want.shape[1]
-        got = np.fromfile(out, np.float64).reshape(want.shape)
+        got = np.frombuffer(written["rows.bin"], np.float64).reshape(want.shape)
         assert (got.view(np.uint64) == want.view(np.uint64)).all(), (exe, threads)

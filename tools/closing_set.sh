@@ -1,5 +1,5 @@
 # the GPU measurements a round's profiles/ are built from, in two gpurun calls:
-#   bash tools/closing_set.sh <tag> a     bench line, rocprofv3 kernel stats of the same command, the three PMC passes on the accumulation pass
+#   bash tools/closing_set.sh <tag> a     bench line (--full), rocprofv3 kernel stats of the same command, the three PMC passes on the accumulation pass
 #   bash tools/closing_set.sh <tag> b     loop digests and timings, phase counters (profiling build), config 5 end to end, watershed, transform
 set -e
 TAG=${1:-r04z}; PART=${2:-a}
@@ -7,7 +7,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 if [ "$PART" = a ]; then
-timeout -k 10 600 python bench.py --steps 5 --warmup 1 > $OUT/bench1024.json 2> $OUT/bench1024.err
+timeout -k 10 600 python bench.py --full --steps 5 --warmup 1 > $OUT/bench1024.json 2> $OUT/bench1024.err
 echo bench done
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python3 bench.py --steps 2 --warmup 1 --no-cpu --no-bc > $OUT/prof_bench.log 2>&1
 echo stats done
