@@ -26,7 +26,7 @@ void set_error(const std::string& msg) { g_err = msg; }
 // when the table is first used -- no entry point calls getenv() per call.
 static const char* const kOptionKeys[] = {"GLIA_HMT_PB_WINDOW", "GLIA_HMT_PB_BATCH", "GLIA_HMT_WINCAP", "GLIA_HMT_REBASE", "GLIA_HMT_HORIZON",
                                           "GLIA_HMT_FORCE_TREE", "GLIA_HMT_HELPERS", "GLIA_HMT_TRACE", "GLIA_HMT_LIBM", "GLIA_HMT_BC_NOCOMMON",
-                                          "GLIA_HMT_BC_GENERIC", "GLIA_HMT_DEBUG", "GLIA_HMT_MAXITERS"};
+                                          "GLIA_HMT_BC_GENERIC", "GLIA_HMT_DEBUG", "GLIA_HMT_MAXITERS", "GLIA_HMT_MINCAP"};
 static std::mutex g_opt_mu;
 static std::unordered_map<std::string, std::string> g_opt;
 static bool g_opt_init = false;
@@ -130,18 +130,15 @@ static LibmSel probe_host_libm() {
 }  // namespace glia
 
 namespace glia {
-int greedy_bc(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier& clf, hipStream_t stream, uint32_t* h_order,
-              double* h_sal, double* h_feats, int64_t capacity, int64_t* n_merges, double* ms_table, double* ms_init,
-              double* ms_loop, int64_t* n_scored, bool init_only, const uint32_t* h_forced, int64_t n_forced, int shard,
-              int n_shards, double* h_scores) {
+GLIA_DECLARE_GREEDY_BC(greedy_bc) {
   auto* fn = &greedy_bc_generic;
   const bool common = cfg.K == 1 && cfg.n_region == 1 && cfg.n_rlabel == 0 && cfg.n_boundary == 1 && !cfg.use_hist && !cfg.use_log &&
                       !cfg.use_simple && !option("GLIA_HMT_BC_NOCOMMON");
   if (cfg.libm_log2 == kLibmSse2 && cfg.libm_log == kLibmFma && cfg.libm_pow == kLibmFma) fn = common ? &greedy_bc_fma_common : &greedy_bc_fma;
   else if (cfg.libm_log2 == kLibmSse2 && cfg.libm_log == kLibmSse2 && cfg.libm_pow == kLibmSse2) fn = common ? &greedy_bc_sse2_common : &greedy_bc_sse2;
   if (option("GLIA_HMT_BC_GENERIC")) fn = &greedy_bc_generic;       // tests: the run-time-dispatch instance
-  return fn(rag, cfg, clf, stream, h_order, h_sal, h_feats, capacity, n_merges, ms_table, ms_init, ms_loop, n_scored, init_only,
-            h_forced, n_forced, shard, n_shards, h_scores);
+  const int rc = fn(rag, cfg, clf, stream, req, out);
+  return req.init_only ? rc : finish_merge_order(rc, out->order.data(), out->n, (uint32_t)rag.R, stream);
 }
 }  // namespace glia
 
@@ -736,6 +733,26 @@ int glia_hmt_rag_export_pairs(const glia_hmt_rag* r, uint32_t* h_a, uint32_t* h_
   return GLIA_HMT_OK;
 }
 
+// A loop's order in keys, for the caller.  Dense id -> key: leaves = i-th label ascending; merged regions = maxKey + 1 + k
+// (util/struct_merge.hxx:19,27-31), maxKey over the regions the reference's map holds: every label, or with contour_keys
+// (merge_order_pb in contour-only mode, type/region_map.hxx:99-111) every label that owns a directed boundary.
+static int order_to_keys(const glia_hmt_rag* rag, const MergeResult& res, const char* who, bool contour_keys, int64_t capacity,
+                         uint32_t* h_order, double* h_sal, int64_t* n_merges) {
+  const int64_t R = rag->arr.R, n = res.n;
+  if (n > capacity) { set_error(std::string(who) + ": output capacity too small"); return GLIA_HMT_ERR_CAPACITY; }
+  std::vector<uint32_t> lab((size_t)R);
+  GLIA_HIP_TRY(hipMemcpy(lab.data(), rag->arr.d_rlabel, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
+  uint32_t maxKey = lab[R - 1];
+  if (contour_keys) GLIA_HIP_TRY(hipMemcpy(&maxKey, rag->arr.d_pa + (rag->arr.P - 1), sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < 3 * n; ++i) {
+    const uint32_t id = res.order[i];
+    h_order[i] = id < (uint32_t)R ? lab[id] : maxKey + 1u + (id - (uint32_t)R);
+  }
+  std::copy(res.sal.begin(), res.sal.begin() + n, h_sal);
+  *n_merges = n;
+  return GLIA_HMT_OK;
+}
+
 int glia_hmt_merge_order_pb(glia_hmt_ctx* c, glia_hmt_rag* rag, int type, uint32_t* h_order, double* h_sal,
                             int64_t capacity, int64_t* n_merges) {
   if (!c || !rag || !h_order || !h_sal || !n_merges || rag->ctx != c) {
@@ -756,31 +773,16 @@ int glia_hmt_merge_order_pb(glia_hmt_ctx* c, glia_hmt_rag* rag, int type, uint32
     return GLIA_HMT_ERR_ARG;
   }
   GLIA_HIP_TRY(hipSetDevice(c->device));
-  const int64_t R = rag->arr.R, P = rag->arr.P;
   *n_merges = 0;
-  if (R == 0 || P == 0) return GLIA_HMT_OK;
-  std::vector<uint32_t> order((size_t)3 * R);
-  std::vector<double> sal((size_t)R);
-  int64_t n = 0;
-  int rc = greedy_mean(rag->arr, c->stream, order.data(), sal.data(), R, &n, &rag->ms_table, &rag->ms_loop,
-                       &rag->n_scored, 0, nullptr, 0.0, (type == 1 || type == 3) ? &rag->vol : nullptr, type == 3);
+  if (rag->arr.R == 0 || rag->arr.P == 0) return GLIA_HMT_OK;
+  PbRequest req;
+  if (type == 1 || type == 3) req.median_of = &rag->vol;
+  req.size_weight = type == 3;
+  MergeResult res;
+  const int rc = greedy_mean(rag->arr, c->stream, req, &res);
   if (rc) return rc;
-  if (n > capacity) { set_error("merge_order_pb: output capacity too small"); return GLIA_HMT_ERR_CAPACITY; }
-  // dense id -> key.  Leaves: i-th label ascending.  Merged regions: maxKey + 1 + k (util/struct_merge.hxx:19,27-31),
-  // maxKey over the regions the reference's map holds: every label (point-map mode) or every label that owns a
-  // directed boundary (contour-only mode, type/region_map.hxx:99-111).
-  std::vector<uint32_t> lab((size_t)R);
-  GLIA_HIP_TRY(hipMemcpy(lab.data(), rag->arr.d_rlabel, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
-  uint32_t maxKey = lab[R - 1];
-  if (rag->only_contour)
-    GLIA_HIP_TRY(hipMemcpy(&maxKey, rag->arr.d_pa + (P - 1), sizeof(uint32_t), hipMemcpyDeviceToHost));
-  for (int64_t i = 0; i < 3 * n; ++i) {
-    const uint32_t id = order[i];
-    h_order[i] = id < (uint32_t)R ? lab[id] : maxKey + 1u + (id - (uint32_t)R);
-  }
-  for (int64_t i = 0; i < n; ++i) h_sal[i] = sal[i];
-  *n_merges = n;
-  return GLIA_HMT_OK;
+  rag->ms_table = res.ms_table; rag->ms_loop = res.ms_loop; rag->n_scored = res.n_scored;
+  return order_to_keys(rag, res, "merge_order_pb", rag->only_contour, capacity, h_order, h_sal, n_merges);
 }
 
 static int upload_forest(const HostForest& hf, glia_hmt_forest* f, int slot, hipStream_t stream) {
@@ -915,6 +917,24 @@ int glia_hmt_feat_dim(const glia_hmt_rag* rag) {
   return c.fdim + median_extra_cols(rag, c);
 }
 
+// What the classifier entry points check before a run of the loop (`who` prefixes the messages).  forest == nullptr: a given
+// order (bc_feat), where the median features are implemented and no classifier reads the vector.
+static int bc_setup(glia_hmt_ctx* c, const glia_hmt_rag* rag, const glia_hmt_forest* forest, const char* who, BcCfg* cfg) {
+  if (!make_bc_cfg(rag, cfg) || rag->only_contour) {
+    set_error(std::string(who) + ": the region map must be built with a feature configuration and with region points");
+    return GLIA_HMT_ERR_ARG;
+  }
+  if (forest) {
+    if (int rm = refuse_median_in_loop(rag, who)) return rm;
+    if (forest->max_var >= cfg->fdim) { set_error(std::string(who) + ": the classifier reads features beyond the vector"); return GLIA_HMT_ERR_ARG; }
+  }
+  GLIA_HIP_TRY(hipSetDevice(c->device));
+  return GLIA_HMT_OK;
+}
+static void keep_timing(glia_hmt_rag* rag, const MergeResult& res) {
+  rag->ms_table = res.ms_table; rag->ms_init = res.ms_init; rag->ms_loop = res.ms_loop; rag->n_scored = res.n_scored;
+}
+
 int glia_hmt_merge_order_bc(glia_hmt_ctx* c, glia_hmt_rag* rag, const glia_hmt_forest* forest, uint32_t* h_order,
                             double* h_sal, double* h_feats, int64_t capacity, int64_t* n_merges) {
   if (!c || !rag || !forest || !h_order || !h_sal || !n_merges || rag->ctx != c) {
@@ -922,35 +942,17 @@ int glia_hmt_merge_order_bc(glia_hmt_ctx* c, glia_hmt_rag* rag, const glia_hmt_f
     return GLIA_HMT_ERR_ARG;
   }
   BcCfg cfg;
-  if (!make_bc_cfg(rag, &cfg) || rag->only_contour) {
-    set_error("merge_order_bc: the region map must be built with a feature configuration and with region points");
-    return GLIA_HMT_ERR_ARG;
-  }
-  if (int rm = refuse_median_in_loop(rag, "merge_order_bc")) return rm;
-  if (forest->max_var >= cfg.fdim) { set_error("merge_order_bc: the classifier reads features beyond the vector"); return GLIA_HMT_ERR_ARG; }
-  GLIA_HIP_TRY(hipSetDevice(c->device));
-  const int64_t R = rag->arr.R;
+  int rc;
+  if ((rc = bc_setup(c, rag, forest, "merge_order_bc", &cfg))) return rc;
   *n_merges = 0;
-  if (R == 0 || rag->arr.P == 0) return GLIA_HMT_OK;
-  std::vector<uint32_t> order((size_t)3 * R);
-  std::vector<double> sal((size_t)R);
-  std::vector<double> feats;
-  if (h_feats) feats.resize((size_t)R * cfg.fdim);
-  int64_t n = 0;
-  int rc = greedy_bc(rag->arr, cfg, forest->dc, c->stream, order.data(), sal.data(), h_feats ? feats.data() : nullptr, R, &n,
-                     &rag->ms_table, &rag->ms_init, &rag->ms_loop, &rag->n_scored, false);
-  if (rc) return rc;
-  if (n > capacity) { set_error("merge_order_bc: output capacity too small"); return GLIA_HMT_ERR_CAPACITY; }
-  std::vector<uint32_t> lab((size_t)R);
-  GLIA_HIP_TRY(hipMemcpy(lab.data(), rag->arr.d_rlabel, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
-  const uint32_t maxKey = lab[R - 1];
-  for (int64_t i = 0; i < 3 * n; ++i) {
-    const uint32_t id = order[i];
-    h_order[i] = id < (uint32_t)R ? lab[id] : maxKey + 1u + (id - (uint32_t)R);
-  }
-  for (int64_t i = 0; i < n; ++i) h_sal[i] = sal[i];
-  if (h_feats) memcpy(h_feats, feats.data(), sizeof(double) * (size_t)n * cfg.fdim);
-  *n_merges = n;
+  if (rag->arr.R == 0 || rag->arr.P == 0) return GLIA_HMT_OK;
+  BcRequest req;
+  req.rows = h_feats != nullptr;
+  MergeResult res;
+  if ((rc = greedy_bc(rag->arr, cfg, forest->dc, c->stream, req, &res))) return rc;
+  keep_timing(rag, res);
+  if ((rc = order_to_keys(rag, res, "merge_order_bc", false, capacity, h_order, h_sal, n_merges))) return rc;
+  if (h_feats) std::copy(res.rows.begin(), res.rows.end(), h_feats);
   return GLIA_HMT_OK;
 }
 
@@ -962,27 +964,17 @@ int glia_hmt_pre_merge(glia_hmt_ctx* c, glia_hmt_rag* rag, const int* size_thres
   }
   if (rag->only_contour) { set_error("pre_merge: the region map must hold region points (only_contour = 0)"); return GLIA_HMT_ERR_ARG; }
   GLIA_HIP_TRY(hipSetDevice(c->device));
-  const int64_t R = rag->arr.R, P = rag->arr.P;
   *n_merges = 0;
-  if (R == 0 || P == 0) return GLIA_HMT_OK;
-  std::vector<uint32_t> order((size_t)3 * R);
-  std::vector<double> sal((size_t)R);
-  long long sizes[2] = {size_thresholds[0], n_thresholds > 1 ? size_thresholds[1] : 0};
-  int64_t n = 0;
-  int rc = greedy_mean(rag->arr, c->stream, order.data(), sal.data(), R, &n, &rag->ms_table, &rag->ms_loop, &rag->n_scored,
-                       n_thresholds, sizes, rpb_threshold);
+  if (rag->arr.R == 0 || rag->arr.P == 0) return GLIA_HMT_OK;
+  PbRequest req;
+  req.cond_n = n_thresholds;
+  req.cond_sizes[0] = size_thresholds[0]; req.cond_sizes[1] = n_thresholds > 1 ? size_thresholds[1] : 0;
+  req.cond_rpb = rpb_threshold;
+  MergeResult res;
+  const int rc = greedy_mean(rag->arr, c->stream, req, &res);
   if (rc) return rc;
-  if (n > capacity) { set_error("pre_merge: output capacity too small"); return GLIA_HMT_ERR_CAPACITY; }
-  std::vector<uint32_t> lab((size_t)R);
-  GLIA_HIP_TRY(hipMemcpy(lab.data(), rag->arr.d_rlabel, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
-  const uint32_t maxKey = lab[R - 1];
-  for (int64_t i = 0; i < 3 * n; ++i) {
-    const uint32_t id = order[i];
-    h_order[i] = id < (uint32_t)R ? lab[id] : maxKey + 1u + (id - (uint32_t)R);
-  }
-  for (int64_t i = 0; i < n; ++i) h_sal[i] = sal[i];
-  *n_merges = n;
-  return GLIA_HMT_OK;
+  rag->ms_table = res.ms_table; rag->ms_loop = res.ms_loop; rag->n_scored = res.n_scored;
+  return order_to_keys(rag, res, "pre_merge", false, capacity, h_order, h_sal, n_merges);
 }
 
 int glia_hmt_bc_feat(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t* h_order, int64_t n_merges, double* h_feats) {
@@ -999,11 +991,8 @@ int glia_hmt_bc_feat_saliency(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t
                               const double* h_saliencies, double init_saliency, double saliency_bias, double* h_feats) {
   if (!c || !rag || !h_order || !h_feats || n_merges < 0 || rag->ctx != c) { set_error("bc_feat: invalid argument"); return GLIA_HMT_ERR_ARG; }
   BcCfg cfg;
-  if (!make_bc_cfg(rag, &cfg) || rag->only_contour) {
-    set_error("bc_feat: the region map must be built with a feature configuration and with region points");
-    return GLIA_HMT_ERR_ARG;
-  }
-  GLIA_HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  if ((rc = bc_setup(c, rag, nullptr, "bc_feat", &cfg))) return rc;
   const int64_t R = rag->arr.R;
   if (n_merges == 0) return GLIA_HMT_OK;
   if (n_merges >= R) { set_error("bc_feat: more merges than regions"); return GLIA_HMT_ERR_ARG; }
@@ -1026,16 +1015,17 @@ int glia_hmt_bc_feat_saliency(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t
     if (id.count(h_order[3 * i + 2])) { set_error("bc_feat: merge order reuses a region key"); return GLIA_HMT_ERR_ARG; }
     id[h_order[3 * i + 2]] = (uint32_t)(R + i);
   }
-  std::vector<uint32_t> order((size_t)3 * R);
-  std::vector<double> sal((size_t)R), feats((size_t)R * cfg.fdim);
   DeviceClassifier none;
   memset(&none, 0, sizeof(none));
   none.kind = 1;
-  int64_t n = 0;
-  int rc = greedy_bc(rag->arr, cfg, none, c->stream, order.data(), sal.data(), feats.data(), R, &n, &rag->ms_table, &rag->ms_init,
-                     &rag->ms_loop, &rag->n_scored, false, forced.data(), n_merges);
-  if (rc) return rc;
-  if (n != n_merges) { set_error("bc_feat: internal error, merges not completed"); return GLIA_HMT_ERR_HIP; }
+  BcRequest req;
+  req.forced = forced.data(); req.n_forced = n_merges; req.rows = true;
+  MergeResult res;
+  if ((rc = greedy_bc(rag->arr, cfg, none, c->stream, req, &res))) return rc;
+  keep_timing(rag, res);
+  if (res.n != n_merges) { set_error("bc_feat: merges not completed (internal error)"); count_internal_error(); return GLIA_HMT_ERR_INTERNAL; }
+  const int64_t n = res.n;
+  std::vector<double>& feats = res.rows;
   int bfdim = cfg.bfdim, rfdim = cfg.rfdim, fdim = cfg.fdim;
   if (rag->cfg.use_median_features) {
     // GLIA_USE_MEDIAN_AS_FEATS: the kernel's rows (built from the statistics monoids) + the medians, means and standard deviations
@@ -1215,17 +1205,13 @@ int glia_hmt_score_initial_edges(glia_hmt_ctx* c, glia_hmt_rag* rag, const glia_
                                  double* ms) {
   if (!c || !rag || !forest || rag->ctx != c) { set_error("score_initial_edges: invalid argument"); return GLIA_HMT_ERR_ARG; }
   BcCfg cfg;
-  if (!make_bc_cfg(rag, &cfg) || rag->only_contour) {
-    set_error("score_initial_edges: the region map must be built with a feature configuration and with region points");
-    return GLIA_HMT_ERR_ARG;
-  }
-  if (int rm = refuse_median_in_loop(rag, "score_initial_edges")) return rm;
-  if (forest->max_var >= cfg.fdim) { set_error("score_initial_edges: the classifier reads features beyond the vector"); return GLIA_HMT_ERR_ARG; }
-  GLIA_HIP_TRY(hipSetDevice(c->device));
-  int64_t n = 0;
-  int rc = greedy_bc(rag->arr, cfg, forest->dc, c->stream, nullptr, nullptr, nullptr, 0, &n, &rag->ms_table, &rag->ms_init,
-                     &rag->ms_loop, &rag->n_scored, true);
-  if (rc) return rc;
+  int rc;
+  if ((rc = bc_setup(c, rag, forest, "score_initial_edges", &cfg))) return rc;
+  BcRequest req;
+  req.init_only = true;
+  MergeResult res;
+  if ((rc = greedy_bc(rag->arr, cfg, forest->dc, c->stream, req, &res))) return rc;
+  keep_timing(rag, res);
   if (n_edges) *n_edges = rag->n_scored;
   if (ms) *ms = rag->ms_init;
   return GLIA_HMT_OK;
@@ -1238,25 +1224,18 @@ int glia_hmt_score_initial_edges_shard(glia_hmt_ctx* c, glia_hmt_rag* rag, const
     return GLIA_HMT_ERR_ARG;
   }
   BcCfg cfg;
-  if (!make_bc_cfg(rag, &cfg) || rag->only_contour) {
-    set_error("score_initial_edges: the region map must be built with a feature configuration and with region points");
-    return GLIA_HMT_ERR_ARG;
-  }
-  if (int rm = refuse_median_in_loop(rag, "score_initial_edges")) return rm;
-  if (forest->max_var >= cfg.fdim) { set_error("score_initial_edges: the classifier reads features beyond the vector"); return GLIA_HMT_ERR_ARG; }
-  GLIA_HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  if ((rc = bc_setup(c, rag, forest, "score_initial_edges", &cfg))) return rc;
   // one record per unordered leaf pair; the count is needed before the scores can be copied out
-  std::vector<double> scores;
-  int64_t n = 0;
-  const int64_t upper = rag->arr.P;            // records <= directed pairs
-  scores.assign((size_t)(upper ? upper : 1), 0.0);
-  int rc = greedy_bc(rag->arr, cfg, forest->dc, c->stream, nullptr, nullptr, nullptr, 0, &n, &rag->ms_table, &rag->ms_init,
-                     &rag->ms_loop, &rag->n_scored, true, nullptr, 0, shard, n_shards, scores.data());
-  if (rc) return rc;
-  *n_records = n;
+  BcRequest req;
+  req.init_only = true; req.scores = h_scores != nullptr; req.shard = shard; req.n_shards = n_shards;
+  MergeResult res;
+  if ((rc = greedy_bc(rag->arr, cfg, forest->dc, c->stream, req, &res))) return rc;
+  keep_timing(rag, res);
+  *n_records = res.n;
   if (h_scores) {
-    if (n > capacity) { set_error("score_initial_edges_shard: output capacity too small"); return GLIA_HMT_ERR_CAPACITY; }
-    memcpy(h_scores, scores.data(), sizeof(double) * (size_t)n);
+    if (res.n > capacity) { set_error("score_initial_edges_shard: output capacity too small"); return GLIA_HMT_ERR_CAPACITY; }
+    std::copy(res.sal.begin(), res.sal.begin() + res.n, h_scores);
   }
   return GLIA_HMT_OK;
 }

@@ -1970,32 +1970,24 @@ __global__ void fill_leaves_dead(PqTree t, uint32_t from) {
 
 }  // namespace
 
-// Runs the pb-mean greedy merge on a compact RAG.  h_order receives dense ids (leaf i = i-th label ascending,
-// merged region R+k); the caller maps them to keys.
-static int greedy_mean_once(const RagArrays& rag, hipStream_t stream, uint32_t* h_order, double* h_sal, int64_t capacity,
-                            int64_t* n_merges, double* ms_table, double* ms_loop, int64_t* n_scored, int cond_n,
-                            const long long* cond_sizes, double cond_rpb, const VolumeRef* median_of, bool size_weight) {
+// Runs the pb-mean, median or pre_merge greedy merge on a compact RAG; the order is in dense ids (MergeResult).
+static int run_pb_loop(const RagArrays& rag, hipStream_t stream, const PbRequest& req, MergeResult* out) {
   const long long P = rag.P;
   const uint32_t R = (uint32_t)rag.R;
-  *n_merges = 0;
   if (R == 0 || P == 0) return GLIA_HMT_OK;
-  hipEvent_t ev[3];
-  for (auto& e : ev) GLIA_HIP_TRY(hipEventCreate(&e));
-  GLIA_HIP_TRY(hipEventRecord(ev[0], stream));
-  DeviceBuffers buf;
+  const VolumeRef* median_of = req.median_of;
+  CallEvents<3> ev;
   int rc;
+  if ((rc = ev.create())) return rc;
+  GLIA_HIP_TRY(hipEventRecord(ev.ev[0], stream));
+  DeviceBuffers buf;
   uint32_t* flag; uint32_t* eidx; long long* partner;
   if ((rc = buf.get(&flag, P + 1, true, stream))) return rc;
   if ((rc = buf.get(&eidx, P + 1, false, stream))) return rc;
   if ((rc = buf.get(&partner, P, false, stream))) return rc;
   hipLaunchKernelGGL(edge_flags, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream, rag.d_pa, rag.d_pb, P, flag, partner);
-  {
-    size_t tmp = 0;
-    GLIA_HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, flag, eidx, 0u, (size_t)(P + 1), rocprim::plus<uint32_t>(), stream));
-    void* d_tmp;
-    if ((rc = buf.get((char**)&d_tmp, tmp ? tmp : 16, false, stream))) return rc;
-    GLIA_HIP_TRY(rocprim::exclusive_scan(d_tmp, tmp, flag, eidx, 0u, (size_t)(P + 1), rocprim::plus<uint32_t>(), stream));
-  }
+  if ((rc = rocprim_run(buf, stream, [&](void* t, size_t& b) {
+        return rocprim::exclusive_scan(t, b, flag, eidx, 0u, (size_t)(P + 1), rocprim::plus<uint32_t>(), stream); }))) return rc;
   uint32_t E0 = 0;
   GLIA_HIP_TRY(hipMemcpyAsync(&E0, eidx + P, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
   GLIA_HIP_TRY(hipStreamSynchronize(stream));
@@ -2006,35 +1998,32 @@ static int greedy_mean_once(const RagArrays& rag, hipStream_t stream, uint32_t* 
   st.R0 = R;
   // created edges are never reused: a 1024^3 run ends at ~16.4 x E0 edge slots and ~33 x E0 list entries (measured) --
   // sized so that the usual run never stops to grow (growth = a relaunch plus a copy of gigabytes)
-  st.Ecap = (uint32_t)std::min<unsigned long long>(0xFFFFFF00ull, (unsigned long long)E0 * 18ull + (1u << 16));
-  st.pool_cap = (unsigned long long)E0 * 36ull + (1u << 16);
+  const bool mincap = initial_capacities(E0, 18, 36, &st.Ecap, &st.pool_cap);
   if ((rc = buf.get(&st.adj_off, 2 * (size_t)R, true, stream))) return rc;
   if ((rc = buf.get(&st.adj_len, 2 * (size_t)R + 1, true, stream))) return rc;
   // pb-mean linkage (with or without the pre_merge condition) runs on the window queue; GLIA_HMT_PB_WINDOW=0 keeps the
   // tournament tree (kernel experiments, parity gate: both must give byte-identical results)
   std::string o_window, o_batch, o_txt;
   const bool batch_off = option("GLIA_HMT_PB_BATCH", &o_batch) && o_batch[0] == '0';      // one contraction at a time on the window queue (same result)
-  bool window = !median_of && !size_weight && !(option("GLIA_HMT_PB_WINDOW", &o_window) && o_window[0] == '0');
+  bool window = !median_of && !req.size_weight && !(option("GLIA_HMT_PB_WINDOW", &o_window) && o_window[0] == '0');
   WinState ws;
   memset(&ws, 0, sizeof(ws));
+  GrowList edges, entries, values;              // the arrays indexed by edge slot, by list entry, by value
   if (window) {
-    if ((rc = buf.get(&ws.fpool, st.pool_cap, false, stream))) return rc;
-    if ((rc = buf.get(&ws.er, st.Ecap, false, stream))) return rc;
+    if ((rc = entries.add(buf, &ws.fpool, st.pool_cap, stream))) return rc;
+    if ((rc = edges.add(buf, &ws.er, st.Ecap, stream))) return rc;
   }
-  else if ((rc = buf.get(&st.pool, st.pool_cap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_u, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_v, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_posu, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_posv, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_mean, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_n, st.Ecap, true, stream))) return rc;
+  else if ((rc = entries.add(buf, &st.pool, st.pool_cap, stream))) return rc;
+  if ((rc = edges.add(buf, &st.e_u, st.Ecap, stream)) || (rc = edges.add(buf, &st.e_v, st.Ecap, stream)) ||
+      (rc = edges.add(buf, &st.e_posu, st.Ecap, stream)) || (rc = edges.add(buf, &st.e_posv, st.Ecap, stream)) ||
+      (rc = edges.add(buf, &st.e_mean, st.Ecap, stream)) || (rc = edges.add(buf, &st.e_n, st.Ecap, stream, true)) ||
+      (rc = edges.add(buf, &st.pq.leaf_sal, st.Ecap, stream)) || (rc = edges.add(buf, &st.pq.leaf_seq, st.Ecap, stream)))
+    return rc;
   st.pq.nleaves = st.Ecap;
-  if ((rc = buf.get(&st.pq.leaf_sal, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.pq.leaf_seq, st.Ecap, false, stream))) return rc;
   if ((rc = buf.get(&st.rsz, 2 * (size_t)R, true, stream))) return rc;
   if ((rc = buf.get(&st.rsum, 2 * (size_t)R, true, stream))) return rc;
-  st.cond_n = cond_n; st.cond_rpb = cond_rpb; st.size_weight = size_weight ? 1 : 0;
-  st.cond_t0 = cond_n > 0 ? (unsigned long long)cond_sizes[0] : 0; st.cond_t1 = cond_n > 1 ? (unsigned long long)cond_sizes[1] : 0;
+  st.cond_n = req.cond_n; st.cond_rpb = req.cond_rpb; st.size_weight = req.size_weight ? 1 : 0;
+  st.cond_t0 = req.cond_n > 0 ? (unsigned long long)req.cond_sizes[0] : 0; st.cond_t1 = req.cond_n > 1 ? (unsigned long long)req.cond_sizes[1] : 0;
   hipLaunchKernelGGL(region_sizes, dim3((R + 255) / 256), dim3(256), 0, stream, rag.d_rrec, R, st.rsz, st.rsum);
   if ((rc = buf.get(&st.mark0, 2 * (size_t)R, true, stream))) return rc;
   if ((rc = buf.get(&st.mark1, 2 * (size_t)R, true, stream))) return rc;
@@ -2048,35 +2037,25 @@ static int greedy_mean_once(const RagArrays& rag, hipStream_t stream, uint32_t* 
   hipLaunchKernelGGL(fill_leaves_dead, dim3((st.Ecap - E0 + 255) / 256), dim3(256), 0, stream, st.pq, E0);
   hipLaunchKernelGGL(edge_fill, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream, rag.d_pa, rag.d_pb, rag.d_prec, P,
                      flag, eidx, partner, rag.d_rlabel, R, st, st.adj_len);
-  {
-    // adjacency offsets = exclusive scan of the degrees (adj_len[0..R) holds them, the rest is zero)
-    size_t tmp = 0;
-    GLIA_HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, st.adj_len, st.adj_off, 0u, (size_t)R, rocprim::plus<uint32_t>(), stream));
-    void* d_tmp;
-    if ((rc = buf.get((char**)&d_tmp, tmp ? tmp : 16, false, stream))) return rc;
-    GLIA_HIP_TRY(rocprim::exclusive_scan(d_tmp, tmp, st.adj_len, st.adj_off, 0u, (size_t)R, rocprim::plus<uint32_t>(), stream));
-  }
+  // adjacency offsets = exclusive scan of the degrees (adj_len[0..R) holds them, the rest is zero)
+  if ((rc = rocprim_run(buf, stream, [&](void* t, size_t& b) {
+        return rocprim::exclusive_scan(t, b, st.adj_len, st.adj_off, 0u, (size_t)R, rocprim::plus<uint32_t>(), stream); }))) return rc;
   if (window) hipLaunchKernelGGL(adj_fill_fat, dim3((E0 + 255) / 256), dim3(256), 0, stream, st, ws, E0, cursor);
   else hipLaunchKernelGGL(adj_fill, dim3((E0 + 255) / 256), dim3(256), 0, stream, st, E0, cursor);
   GLIA_HIP_TRY(hipGetLastError());
   unsigned long long n_values = 0;
   if (median_of) {
     // sorted value runs: offsets = scan of the edges' voxel counts, one scatter pass over the volume, segmented sort
-    if ((rc = buf.get(&st.e_off, st.Ecap, false, stream))) return rc;
+    if ((rc = edges.add(buf, &st.e_off, st.Ecap, stream))) return rc;
     if ((rc = buf.get(&st.rbv, 2 * (size_t)R, true, stream))) return rc;
-    {
-      size_t tmp = 0;
-      GLIA_HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, st.e_n, st.e_off, 0ull, (size_t)E0 + 1, rocprim::plus<unsigned long long>(), stream));
-      void* d_tmp;
-      if ((rc = buf.get((char**)&d_tmp, tmp ? tmp : 16, false, stream))) return rc;
-      GLIA_HIP_TRY(rocprim::exclusive_scan(d_tmp, tmp, st.e_n, st.e_off, 0ull, (size_t)E0 + 1, rocprim::plus<unsigned long long>(), stream));
-    }
+    if ((rc = rocprim_run(buf, stream, [&](void* t, size_t& b) {
+          return rocprim::exclusive_scan(t, b, st.e_n, st.e_off, 0ull, (size_t)E0 + 1, rocprim::plus<unsigned long long>(), stream); }))) return rc;
     GLIA_HIP_TRY(hipMemcpyAsync(&n_values, st.e_off + E0, sizeof(n_values), hipMemcpyDeviceToHost, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
     if (n_values >= 0xFFFFFFFFull) { set_error("merge_order_pb: more than 2^32 boundary voxels (median linkage)"); return GLIA_HMT_ERR_ARG; }
-    st.vals_cap = n_values * 4ull + (1ull << 20);
+    st.vals_cap = mincap ? std::max(n_values, 1ull) : n_values * 4ull + (1ull << 20);
     float* unsorted;
-    if ((rc = buf.get(&st.vals, (size_t)st.vals_cap, false, stream))) return rc;
+    if ((rc = values.add(buf, &st.vals, (size_t)st.vals_cap, stream))) return rc;
     if ((rc = buf.get(&unsorted, (size_t)n_values, false, stream))) return rc;
     uint32_t* vcursor;
     if ((rc = buf.get(&vcursor, (size_t)E0, true, stream))) return rc;
@@ -2090,15 +2069,8 @@ static int greedy_mean_once(const RagArrays& rag, hipStream_t stream, uint32_t* 
                                      (long long)P, flag, eidx, st.e_off, unsorted);
     }
     GLIA_HIP_TRY(hipGetLastError());
-    {
-      size_t tmp = 0;
-      GLIA_HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, tmp, unsorted, st.vals, (unsigned)n_values, (unsigned)E0, st.e_off,
-                                                      st.e_off + 1, 0, 32, stream));
-      void* d_tmp;
-      if ((rc = buf.get((char**)&d_tmp, tmp ? tmp : 16, false, stream))) return rc;
-      GLIA_HIP_TRY(rocprim::segmented_radix_sort_keys(d_tmp, tmp, unsorted, st.vals, (unsigned)n_values, (unsigned)E0, st.e_off,
-                                                      st.e_off + 1, 0, 32, stream));
-    }
+    if ((rc = rocprim_run(buf, stream, [&](void* t, size_t& b) {
+          return rocprim::segmented_radix_sort_keys(t, b, unsorted, st.vals, (unsigned)n_values, (unsigned)E0, st.e_off, st.e_off + 1, 0, 32, stream); }))) return rc;
     hipLaunchKernelGGL(median_init, dim3((E0 + 255) / 256), dim3(256), 0, stream, st, E0);
     GLIA_HIP_TRY(hipGetLastError());
   }
@@ -2202,20 +2174,26 @@ static int greedy_mean_once(const RagArrays& rag, hipStream_t stream, uint32_t* 
     GLIA_HIP_TRY(hipMemcpyAsync(h_range, range, sizeof(h_range), hipMemcpyDeviceToHost, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
     // the horizon: 0 = off; else the factor on the measured descent (swept 0.05 .. 8 at 1024^3: flat from 0.1 to 0.5, +1 % at 2, +2 % at 4)
-    if (cond_n <= 0 && !batch_off) horizon_factor = option("GLIA_HMT_HORIZON", &o_txt) ? atof(o_txt.c_str()) : 0.5;
+    if (req.cond_n <= 0 && !batch_off) horizon_factor = option("GLIA_HMT_HORIZON", &o_txt) ? atof(o_txt.c_str()) : 0.5;
     if ((rc = win_rebaseline(E0))) return rc;
   } else if ((rc = pq_setup(buf, st.pq, stream))) return rc;
   GLIA_HIP_TRY(hipMemcpyAsync(st.ctrl, ctrl, sizeof(ctrl), hipMemcpyHostToDevice, stream));
-  GLIA_HIP_TRY(hipEventRecord(ev[1], stream));
+  GLIA_HIP_TRY(hipEventRecord(ev.ev[1], stream));
+
 
   // ---- the loop, in bounded launches so a contraction budget can be re-negotiated between them ----
   st.max_iters = window ? 1ull << 22 : 1ull << 16;
   const bool trace = option("GLIA_HMT_TRACE");
-  if (option("GLIA_HMT_MAXITERS", &o_txt)) st.max_iters = strtoull(o_txt.c_str(), nullptr, 10);      // tests: launches that end early
+  if (option("GLIA_HMT_MAXITERS", &o_txt)) st.max_iters = std::max(1ull, strtoull(o_txt.c_str(), nullptr, 10));      // tests: launches that end early
+  const auto kernel = [&]() { return !window ? "tree" : req.cond_n > 0 ? "window" : "batch"; };
+  const auto unhandled = [&]() {
+    set_error(std::string("greedy: the ") + kernel() + " kernel stopped with status " + std::to_string(ctrl[3]) + ", which its driver does not handle (internal error)");
+    return GLIA_HMT_ERR_INTERNAL;
+  };
   while (true) {
     if (window) {
       ws.max_iters = st.max_iters;
-      if (cond_n > 0) hipLaunchKernelGGL(greedy_window_kernel<true>, dim3(1), dim3(kGreedyThreads), 0, stream, ws);
+      if (req.cond_n > 0) hipLaunchKernelGGL(greedy_window_kernel<true>, dim3(1), dim3(kGreedyThreads), 0, stream, ws);
       else if (batch_off) hipLaunchKernelGGL(greedy_window_kernel<false>, dim3(1), dim3(kGreedyThreads), 0, stream, ws);
       else hipLaunchKernelGGL(greedy_batch_kernel, dim3(1), dim3(kGreedyThreads), 0, stream, ws);
     } else if (median_of) hipLaunchKernelGGL(greedy_pb_kernel<true>, dim3(1), dim3(kGreedyThreads), 0, stream, st);
@@ -2224,52 +2202,59 @@ static int greedy_mean_once(const RagArrays& rag, hipStream_t stream, uint32_t* 
     GLIA_HIP_TRY(hipMemcpyAsync(ctrl, st.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
     if (trace) fprintf(stderr, "[trace] merge loop launch ended: status %llu, merges %llu of %u regions, edges %llu, list entries %llu\n", ctrl[3], ctrl[0], R, ctrl[1], ctrl[2]);
-    if (ctrl[3] == ST_RUN && !window) continue;
     if (ctrl[3] == ST_DONE) break;
-    if (ctrl[3] == ST_BAD_SALIENCY) { set_error("Error: invalid boundary saliency..."); return GLIA_HMT_ERR_SALIENCY; }
-    if (ctrl[3] == ST_INTERNAL) {
-      char msg[256];
-      snprintf(msg, sizeof(msg), "greedy: window queue overflow or more merges than regions (internal error: merges %llu of %u regions, %llu edges of %u initial, "
-               "window %llu%s, %s kernel)", ctrl[0], R, ctrl[1], E0, ctrl[10], ctrl[9] ? " overflowed" : "", !window ? "tree" : cond_n > 0 ? "window" : "batch");
-      set_error(msg);
-      return GLIA_HMT_ERR_INTERNAL;
-    }
-    if (ctrl[3] == ST_NEED_TREE) {
-      // a saliency cell with more live items than the window holds (massive exact ties): the tournament tree takes over
-      // from the same state -- leaf keys are the ground truth of both queues, the lists get their thin entries
-      if ((rc = buf.get(&st.pool, st.pool_cap, false, stream))) return rc;
-      hipLaunchKernelGGL(fat_to_thin, dim3((unsigned)((ctrl[2] + 255) / 256)), dim3(256), 0, stream, ws.fpool, st.pool, ctrl[2]);
-      hipLaunchKernelGGL(edge_unpack, dim3((unsigned)((ctrl[1] + 255) / 256)), dim3(256), 0, stream, st, ws.er, ws.rdead, (uint32_t)ctrl[1]);
-      GLIA_HIP_TRY(hipGetLastError());
-      if ((rc = pq_setup(buf, st.pq, stream))) return rc;
-      window = false;
-      st.max_iters = 1ull << 16;
-    } else if (ctrl[3] == ST_NEED_POOL) {
-      unsigned long long ncap = st.pool_cap * 2;
-      if (window) { if ((rc = buf.grow(&ws.fpool, (size_t)st.pool_cap, (size_t)ncap, stream))) return rc; }
-      else if ((rc = buf.grow(&st.pool, (size_t)st.pool_cap, (size_t)ncap, stream))) return rc;
-      st.pool_cap = ncap; ws.pool_cap = ncap;
-    } else if (ctrl[3] == ST_NEED_VALUES) {
-      unsigned long long ncap = st.vals_cap * 2;
-      if ((rc = buf.grow(&st.vals, (size_t)ctrl[4], (size_t)ncap, stream))) return rc;
-      st.vals_cap = ncap;
-    } else if (ctrl[3] == ST_NEED_EDGES) {
-      if (st.Ecap >= 0xFFFFFF00u) { set_error("greedy: more than 2^32 edge slots needed"); return GLIA_HMT_ERR_ARG; }
-      uint32_t ocap = st.Ecap;
-      uint32_t ncap = (uint32_t)std::min<unsigned long long>(0xFFFFFF00ull, (unsigned long long)ocap * 2ull);
-      if ((rc = buf.grow(&st.e_u, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.e_v, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.e_posu, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.e_posv, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.e_mean, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.e_n, ocap, ncap, stream))) return rc;
-      if (median_of && (rc = buf.grow(&st.e_off, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.pq.leaf_sal, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.pq.leaf_seq, ocap, ncap, stream))) return rc;
-      if (window && (rc = buf.grow(&ws.er, ocap, ncap, stream))) return rc;
-      st.Ecap = ncap; st.pq.nleaves = ncap; ws.Ecap = ncap;
-      hipLaunchKernelGGL(fill_leaves_dead, dim3((ncap - ocap + 255) / 256), dim3(256), 0, stream, st.pq, ocap);
-      if (!window && (rc = pq_setup(buf, st.pq, stream))) return rc;
+    switch (ctrl[3]) {
+      case ST_RUN:                              // max_iters reached: the tree kernel goes on from its state, the window queue re-baselines
+        if (!window) continue;
+        break;
+      case ST_REBASE:
+        if (!window) return unhandled();
+        break;
+      case ST_BAD_SALIENCY: set_error("Error: invalid boundary saliency..."); return GLIA_HMT_ERR_SALIENCY;
+      case ST_INTERNAL: {
+        char msg[256];
+        snprintf(msg, sizeof(msg), "greedy: window queue overflow or more merges than regions (internal error: merges %llu of %u regions, %llu edges of %u initial, "
+                 "window %llu%s, %s kernel)", ctrl[0], R, ctrl[1], E0, ctrl[10], ctrl[9] ? " overflowed" : "", kernel());
+        set_error(msg);
+        return GLIA_HMT_ERR_INTERNAL;
+      }
+      case ST_NEED_TREE:
+        // a saliency cell with more live items than the window holds (massive exact ties): the tournament tree takes over
+        // from the same state -- leaf keys are the ground truth of both queues, the lists get their thin entries
+        if (!window) return unhandled();
+        entries.remove(&ws.fpool);
+        edges.remove(&ws.er);
+        if ((rc = entries.add(buf, &st.pool, st.pool_cap, stream))) return rc;
+        hipLaunchKernelGGL(fat_to_thin, dim3((unsigned)((ctrl[2] + 255) / 256)), dim3(256), 0, stream, ws.fpool, st.pool, ctrl[2]);
+        hipLaunchKernelGGL(edge_unpack, dim3((unsigned)((ctrl[1] + 255) / 256)), dim3(256), 0, stream, st, ws.er, ws.rdead, (uint32_t)ctrl[1]);
+        GLIA_HIP_TRY(hipGetLastError());
+        if ((rc = pq_setup(buf, st.pq, stream))) return rc;
+        window = false;
+        st.max_iters = 1ull << 16;
+        break;
+      case ST_NEED_POOL: {
+        const unsigned long long ncap = st.pool_cap * 2;
+        if ((rc = entries.grow(buf, (size_t)st.pool_cap, (size_t)ncap, stream))) return rc;
+        st.pool_cap = ncap; ws.pool_cap = ncap;
+        break;
+      }
+      case ST_NEED_VALUES: {
+        if (!median_of) return unhandled();
+        const unsigned long long ncap = st.vals_cap * 2;
+        if ((rc = values.grow(buf, (size_t)ctrl[4], (size_t)ncap, stream))) return rc;
+        st.vals_cap = ncap;
+        break;
+      }
+      case ST_NEED_EDGES: {
+        if (st.Ecap >= kMaxEdgeSlots) { set_error("greedy: more than 2^32 edge slots needed"); return GLIA_HMT_ERR_ARG; }
+        const uint32_t ocap = st.Ecap, ncap = (uint32_t)std::min<unsigned long long>(kMaxEdgeSlots, (unsigned long long)ocap * 2ull);
+        if ((rc = edges.grow(buf, ocap, ncap, stream))) return rc;
+        st.Ecap = ncap; st.pq.nleaves = ncap; ws.Ecap = ncap;
+        hipLaunchKernelGGL(fill_leaves_dead, dim3((ncap - ocap + 255) / 256), dim3(256), 0, stream, st.pq, ocap);
+        if (!window && (rc = pq_setup(buf, st.pq, stream))) return rc;
+        break;
+      }
+      default: return unhandled();
     }
     if (window) {
       // the launch left through the lists (everything alive sits there): a fresh baseline, an empty window
@@ -2279,29 +2264,18 @@ static int greedy_mean_once(const RagArrays& rag, hipStream_t stream, uint32_t* 
     unsigned long long zero = ST_RUN;
     GLIA_HIP_TRY(hipMemcpyAsync(st.ctrl + 3, &zero, sizeof(zero), hipMemcpyHostToDevice, stream));
   }
-  GLIA_HIP_TRY(hipEventRecord(ev[2], stream));
-  GLIA_HIP_TRY(hipEventSynchronize(ev[2]));
-  float t01 = 0, t12 = 0;
-  (void)hipEventElapsedTime(&t01, ev[0], ev[1]);
-  (void)hipEventElapsedTime(&t12, ev[1], ev[2]);
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  *ms_table = t01; *ms_loop = t12;
-  const int64_t n = (int64_t)ctrl[0];
-  *n_scored = (int64_t)ctrl[1];
-  if (n > capacity) { set_error("merge_order: output capacity too small"); return GLIA_HMT_ERR_CAPACITY; }
-  if (n) {
-    if ((rc = copy_to_host_staged(h_order, st.order, sizeof(uint32_t) * 3 * n))) return rc;
-    if ((rc = copy_to_host_staged(h_sal, st.sal_out, sizeof(double) * n))) return rc;
-  }
-  *n_merges = n;
-  return GLIA_HMT_OK;
+  GLIA_HIP_TRY(hipEventRecord(ev.ev[2], stream));
+  GLIA_HIP_TRY(hipEventSynchronize(ev.ev[2]));
+  out->ms_table = ev.ms(0, 1); out->ms_loop = ev.ms(1, 2);
+  out->n_scored = (int64_t)ctrl[1];
+  return copy_merges(out, (int64_t)ctrl[0], st.order, st.sal_out);
 }
 
 
 // Every merge of a correct order joins two regions that still exist and creates region R + k (util/struct_merge.hxx:19-31: the loop
-// appends (r0, r1, key++) and erases both regions' items).  The pb / pre_merge loops replay their order against this rule on the host
-// before they return it -- an O(R) pass, ~1 ms at 262 144 regions -- and a violation is an ERROR (GLIA_HMT_ERR_INTERNAL), never a
-// silent second run: round 3 re-ran such calls (a net under the window kernel's race on its edge counter), which let a
+// appends (r0, r1, key++) and erases both regions' items).  Every merge loop replays its order against this rule on the host before
+// it returns it -- an O(R) pass, ~1 ms at 262 144 regions -- and a violation is an ERROR (GLIA_HMT_ERR_INTERNAL), never a silent
+// second run: round 3 re-ran such calls (a net under the window kernel's race on its edge counter), which let a
 // kernel defect pass every test.  glia_hmt_internal_errors() counts the calls that ended this way.
 static std::atomic<unsigned long long> g_internal_errors{0};
 unsigned long long internal_errors() { return g_internal_errors.load(); }
@@ -2315,17 +2289,18 @@ bool merge_order_is_consistent(const uint32_t* o, int64_t n, uint32_t R, int64_t
   }
   return true;
 }
-int greedy_mean(const RagArrays& rag, hipStream_t stream, uint32_t* h_order, double* h_sal, int64_t capacity,
-                int64_t* n_merges, double* ms_table, double* ms_loop, int64_t* n_scored, int cond_n,
-                const long long* cond_sizes, double cond_rpb, const VolumeRef* median_of, bool size_weight) {
-  int rc = greedy_mean_once(rag, stream, h_order, h_sal, capacity, n_merges, ms_table, ms_loop, n_scored, cond_n, cond_sizes, cond_rpb, median_of, size_weight);
+int finish_merge_order(int rc, const uint32_t* o, int64_t n, uint32_t R, hipStream_t stream) {
   int64_t bad = -1;
-  if (rc == GLIA_HMT_OK && !merge_order_is_consistent(h_order, *n_merges, (uint32_t)rag.R, &bad)) {
-    set_error("greedy: merge " + std::to_string(bad) + " of " + std::to_string(*n_merges) + " joins a region that does not exist (any more) or creates the wrong one (internal error)");
+  if (rc == GLIA_HMT_OK && !merge_order_is_consistent(o, n, R, &bad)) {
+    set_error("greedy: merge " + std::to_string(bad) + " of " + std::to_string(n) + " joins a region that does not exist (any more) or creates the wrong one (internal error)");
     rc = GLIA_HMT_ERR_INTERNAL;
   }
   if (rc == GLIA_HMT_ERR_INTERNAL) { count_internal_error(); (void)hipStreamSynchronize(stream); }
   return rc;
+}
+int greedy_mean(const RagArrays& rag, hipStream_t stream, const PbRequest& req, MergeResult* out) {
+  const int rc = run_pb_loop(rag, stream, req, out);
+  return finish_merge_order(rc, out->order.data(), out->n, (uint32_t)rag.R, stream);
 }
 
 }  // namespace glia

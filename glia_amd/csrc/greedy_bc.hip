@@ -1759,13 +1759,9 @@ __global__ void bc_first_keys(const uint32_t* rrec, uint32_t R, unsigned long lo
 #ifndef GLIA_BC_ENTRY
 #define GLIA_BC_ENTRY greedy_bc_generic        // (see hmt_internal.hpp: the Makefile builds two more instances with GLIA_LIBM_FIXED)
 #endif
-int GLIA_BC_ENTRY(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier& clf, hipStream_t stream,
-              uint32_t* h_order, double* h_sal, double* h_feats, int64_t capacity, int64_t* n_merges,
-              double* ms_table, double* ms_init, double* ms_loop, int64_t* n_scored, bool init_only,
-              const uint32_t* h_forced, int64_t n_forced, int shard, int n_shards, double* h_scores) {
+GLIA_DECLARE_GREEDY_BC(GLIA_BC_ENTRY) {
   const long long P = rag.P;
   const uint32_t R = (uint32_t)rag.R;
-  *n_merges = 0;
   if (R == 0 || P == 0) return GLIA_HMT_OK;
   // the vector is assembled at FULL length (bc_full_dim) and the simple selection compacted in place afterwards: the full length
   // is what the per-thread buffers (double x[kMaxFeat]) hold, not cfg.fdim
@@ -1773,15 +1769,15 @@ int GLIA_BC_ENTRY(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier
     set_error("merge_order_bc: feature vector too long (" + std::to_string(bc_full_dim(cfg)) + " columns before --simpf, limit " + std::to_string(kMaxFeat) + ")");
     return GLIA_HMT_ERR_ARG;
   }
-  hipEvent_t ev[4];
-  for (auto& e : ev) GLIA_HIP_TRY(hipEventCreate(&e));
-  GLIA_HIP_TRY(hipEventRecord(ev[0], stream));
-  DeviceBuffers buf;
+  CallEvents<4> ev;
   int rc;
+  if ((rc = ev.create())) return rc;
+  GLIA_HIP_TRY(hipEventRecord(ev.ev[0], stream));
+  DeviceBuffers buf;
   BcState st;
   memset(&st, 0, sizeof(st));
   st.R0 = R; st.P = P; st.cfg = cfg; st.clf = clf;
-  st.shard = (uint32_t)shard; st.n_shards = (uint32_t)(n_shards > 0 ? n_shards : 1);
+  st.shard = (uint32_t)req.shard; st.n_shards = (uint32_t)(req.n_shards > 0 ? req.n_shards : 1);
 
   // reference region-map iteration order (rmap_order.cpp): leaves sorted by first voxel on the device, the hashtable replay on the host
   std::vector<uint32_t> lab(R), by_first(R), rank;
@@ -1793,11 +1789,7 @@ int GLIA_BC_ENTRY(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier
     if ((rc = buf.get(&v0, R, false, stream))) return rc;
     if ((rc = buf.get(&v1, R, false, stream))) return rc;
     hipLaunchKernelGGL(bc_first_keys, dim3((R + 255) / 256), dim3(256), 0, stream, rag.d_rrec, R, k0, v0);
-    size_t tmp = 0;
-    GLIA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, k0, k1, v0, v1, (size_t)R, 0, 64, stream));
-    char* d_tmp;
-    if ((rc = buf.get(&d_tmp, tmp ? tmp : 16, false, stream))) return rc;
-    GLIA_HIP_TRY(rocprim::radix_sort_pairs((void*)d_tmp, tmp, k0, k1, v0, v1, (size_t)R, 0, 64, stream));
+    if ((rc = rocprim_run(buf, stream, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, k0, k1, v0, v1, (size_t)R, 0, 64, stream); }))) return rc;
     if ((rc = PinnedHost::mine().get((void**)&h_stage, sizeof(uint32_t) * 3 * (size_t)R))) return rc;
     GLIA_HIP_TRY(hipMemcpyAsync(h_stage, v1, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, stream));
     GLIA_HIP_TRY(hipMemcpyAsync(h_stage + R, rag.d_rlabel, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, stream));
@@ -1834,22 +1826,17 @@ int GLIA_BC_ENTRY(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier
                        cfg.cbins[c], cfg.T);
   hipLaunchKernelGGL(bc_leaf_starts, dim3((R + 256) / 256), dim3(256), 0, stream, st, rag.d_pa, rag.d_rlabel);
   hipLaunchKernelGGL(bc_record_flags, dim3(gP), dim3(256), 0, stream, st, rag.d_pa, rag.d_pb, flag);
-  {
-    size_t tmp = 0;
-    GLIA_HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, flag, eidx, 0u, (size_t)(P + 1), rocprim::plus<uint32_t>(), stream));
-    char* d_tmp;
-    if ((rc = buf.get(&d_tmp, tmp ? tmp : 16, false, stream))) return rc;
-    GLIA_HIP_TRY(rocprim::exclusive_scan((void*)d_tmp, tmp, flag, eidx, 0u, (size_t)(P + 1), rocprim::plus<uint32_t>(), stream));
-  }
+  if ((rc = rocprim_run(buf, stream, [&](void* t, size_t& b) {
+        return rocprim::exclusive_scan(t, b, flag, eidx, 0u, (size_t)(P + 1), rocprim::plus<uint32_t>(), stream); }))) return rc;
   uint32_t E0 = 0;
   GLIA_HIP_TRY(hipMemcpyAsync(&E0, eidx + P, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
   GLIA_HIP_TRY(hipStreamSynchronize(stream));
   if (trace) fprintf(stderr, "[trace] greedy_bc: leaf entries + record flags done at %.2f ms\n", tr_ms());
   if (E0 == 0) return GLIA_HMT_OK;
 
-  st.Ecap = (uint32_t)std::min<unsigned long long>(0xFFFFFF00ull, (unsigned long long)E0 * 6ull + (1u << 16));
-  st.pool_cap = (unsigned long long)E0 * 12ull + (1u << 16);
+  (void)initial_capacities(E0, 6, 12, &st.Ecap, &st.pool_cap);
   const size_t R2 = 2 * (size_t)R;
+  GrowList edges, entries;                      // the arrays indexed by edge slot, by list entry
   for (int c = 0; c < cfg.K; ++c) {
     BcChan& ch = st.ch[c];
     if ((rc = buf.get(&ch.pts, R2, false, stream))) return rc;
@@ -1859,32 +1846,28 @@ int GLIA_BC_ENTRY(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier
     if ((rc = buf.get(&ch.Bmx, R2, false, stream))) return rc;
     if ((rc = buf.get(&ch.entP, R2, false, stream))) return rc;
     if ((rc = buf.get(&ch.entB, R2, false, stream))) return rc;
-    if ((rc = buf.get(&ch.e_A, st.Ecap, false, stream))) return rc;
-    if ((rc = buf.get(&ch.e_NA, st.Ecap, false, stream))) return rc;
-    if ((rc = buf.get(&ch.e_dir, (size_t)st.Ecap * 4, false, stream))) return rc;
-    if ((rc = buf.get(&ch.pool_dir, (size_t)st.pool_cap, false, stream))) return rc;
+    if ((rc = edges.add(buf, &ch.e_A, st.Ecap, stream))) return rc;
+    if ((rc = edges.add(buf, &ch.e_NA, st.Ecap, stream))) return rc;
+    if ((rc = edges.add(buf, &ch.e_dir, st.Ecap, stream, false, 4))) return rc;
+    if ((rc = entries.add(buf, &ch.pool_dir, st.pool_cap, stream))) return rc;
   }
   if ((rc = buf.get(&st.parent, R2, false, stream))) return rc;
   if ((rc = buf.get(&st.adj_off, R2, true, stream))) return rc;
   if ((rc = buf.get(&st.adj_len, R2 + 1, true, stream))) return rc;
-  if ((rc = buf.get(&st.pool, st.pool_cap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_u, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_v, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_posu, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_posv, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_alive, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_table, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_orient, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_fhead, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.e_ftail, st.Ecap, false, stream))) return rc;
+  if ((rc = entries.add(buf, &st.pool, st.pool_cap, stream))) return rc;
+  if ((rc = edges.add(buf, &st.e_u, st.Ecap, stream)) || (rc = edges.add(buf, &st.e_v, st.Ecap, stream)) ||
+      (rc = edges.add(buf, &st.e_posu, st.Ecap, stream)) || (rc = edges.add(buf, &st.e_posv, st.Ecap, stream)) ||
+      (rc = edges.add(buf, &st.e_alive, st.Ecap, stream)) || (rc = edges.add(buf, &st.e_table, st.Ecap, stream)) ||
+      (rc = edges.add(buf, &st.e_orient, st.Ecap, stream)) || (rc = edges.add(buf, &st.e_fhead, st.Ecap, stream)) ||
+      (rc = edges.add(buf, &st.e_ftail, st.Ecap, stream)) || (rc = edges.add(buf, &st.pq.leaf_sal, st.Ecap, stream)) ||
+      (rc = edges.add(buf, &st.pq.leaf_seq, st.Ecap, stream)))
+    return rc;
   st.pq.nleaves = st.Ecap;
-  if ((rc = buf.get(&st.pq.leaf_sal, st.Ecap, false, stream))) return rc;
-  if ((rc = buf.get(&st.pq.leaf_seq, st.Ecap, false, stream))) return rc;
   if ((rc = buf.get(&st.mark0, R2, true, stream))) return rc;
   if ((rc = buf.get(&st.mark1, R2, true, stream))) return rc;
   if ((rc = buf.get(&st.order, 3 * (size_t)R, false, stream))) return rc;
   if ((rc = buf.get(&st.sal_out, (size_t)R, false, stream))) return rc;
-  if (h_feats) { if ((rc = buf.get(&st.feats_out, (size_t)R * cfg.fdim, false, stream))) return rc; }
+  if (req.rows) { if ((rc = buf.get(&st.feats_out, (size_t)R * cfg.fdim, false, stream))) return rc; }
   if ((rc = buf.get(&st.hctl, (size_t)kFlagReps * kFlagStride, true, stream))) return rc;
   if ((rc = buf.get(&st.hrec, (size_t)kJobMax * cfg.K * kRowWords, false, stream))) return rc;
   if ((rc = buf.get(&st.hadj, R2, true, stream))) return rc;
@@ -1910,7 +1893,7 @@ int GLIA_BC_ENTRY(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier
     const int resident = per_cu * prop.multiProcessorCount;
     if (resident < 1) { set_error("merge_order_bc: the loop kernel does not fit this device"); return GLIA_HMT_ERR_HIP; }
     if (nh > resident - 1) nh = resident - 1;
-    st.n_helpers = (clf.kind == 0 && !h_forced && !init_only) ? (uint32_t)nh : 0u;
+    st.n_helpers = (clf.kind == 0 && !req.forced && !req.init_only) ? (uint32_t)nh : 0u;
   }
   if ((rc = buf.get(&st.ctrl, 8, true, stream))) return rc;
   uint32_t* cursor;
@@ -1922,48 +1905,40 @@ int GLIA_BC_ENTRY(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier
     hipLaunchKernelGGL(bc_leaf_regions, dim3((R + 255) / 256), dim3(256), 0, stream, st, c, rag.c_rrec[c], cfg.cbins[c]);
     hipLaunchKernelGGL(bc_record_fill, dim3(gP), dim3(256), 0, stream, st, c, flag, eidx, partner, d_rank, st.adj_len);
   }
-  {
-    size_t tmp = 0;
-    GLIA_HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, st.adj_len, st.adj_off, 0u, (size_t)R, rocprim::plus<uint32_t>(), stream));
-    char* d_tmp;
-    if ((rc = buf.get(&d_tmp, tmp ? tmp : 16, false, stream))) return rc;
-    GLIA_HIP_TRY(rocprim::exclusive_scan((void*)d_tmp, tmp, st.adj_len, st.adj_off, 0u, (size_t)R, rocprim::plus<uint32_t>(), stream));
-  }
+  if ((rc = rocprim_run(buf, stream, [&](void* t, size_t& b) {
+        return rocprim::exclusive_scan(t, b, st.adj_len, st.adj_off, 0u, (size_t)R, rocprim::plus<uint32_t>(), stream); }))) return rc;
   hipLaunchKernelGGL(bc_adj_fill, dim3((E0 + 255) / 256), dim3(256), 0, stream, st, E0, cursor);
   hipLaunchKernelGGL(bc_hadj_fill, dim3((R + 255) / 256), dim3(256), 0, stream, st);
   GLIA_HIP_TRY(hipGetLastError());
-  GLIA_HIP_TRY(hipEventRecord(ev[1], stream));
-  if (!h_forced) hipLaunchKernelGGL(bc_init_score, dim3((E0 + 127) / 128), dim3(128), 0, stream, st, E0);
-  if (h_forced) {
+  GLIA_HIP_TRY(hipEventRecord(ev.ev[1], stream));
+  if (!req.forced) hipLaunchKernelGGL(bc_init_score, dim3((E0 + 127) / 128), dim3(128), 0, stream, st, E0);
+  if (req.forced) {
     uint32_t* d_forced;
-    if ((rc = buf.get(&d_forced, (size_t)2 * n_forced + 2, false, stream))) return rc;
-    GLIA_HIP_TRY(hipMemcpyAsync(d_forced, h_forced, sizeof(uint32_t) * 2 * (size_t)n_forced, hipMemcpyHostToDevice, stream));
-    st.forced = d_forced; st.forced_n = (unsigned long long)n_forced;
+    if ((rc = buf.get(&d_forced, (size_t)2 * req.n_forced + 2, false, stream))) return rc;
+    GLIA_HIP_TRY(hipMemcpyAsync(d_forced, req.forced, sizeof(uint32_t) * 2 * (size_t)req.n_forced, hipMemcpyHostToDevice, stream));
+    st.forced = d_forced; st.forced_n = (unsigned long long)req.n_forced;
   }
   GLIA_HIP_TRY(hipGetLastError());
   if ((rc = pq_setup(buf, st.pq, stream))) return rc;
   unsigned long long ctrl[4] = {0, E0, 2ull * E0, ST_RUN};
   GLIA_HIP_TRY(hipMemcpyAsync(st.ctrl, ctrl, sizeof(ctrl), hipMemcpyHostToDevice, stream));
-  GLIA_HIP_TRY(hipEventRecord(ev[2], stream));
+  GLIA_HIP_TRY(hipEventRecord(ev.ev[2], stream));
 
   if (trace) fprintf(stderr, "[trace] greedy_bc: kernels launched at %.2f ms\n", tr_ms());
   if (trace) { (void)hipStreamSynchronize(stream); fprintf(stderr, "[trace] greedy_bc: set-up + initial scores %.2f ms since the replay started; %zu of %zu device blocks (%.1f MB) were not in the block cache\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count(), buf.misses, buf.all.size(), (double)buf.miss_bytes / 1048576.0); }
-  if (init_only) {     // features + scores of the initial table edges only (TBoundaryTable::init)
-    uint32_t* d_cnt;
-    if ((rc = buf.get(&d_cnt, 1, true, stream))) return rc;
-    GLIA_HIP_TRY(hipEventSynchronize(ev[2]));
-    float t01 = 0, t12 = 0;
-    (void)hipEventElapsedTime(&t01, ev[0], ev[1]);
-    (void)hipEventElapsedTime(&t12, ev[1], ev[2]);
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    *ms_table = t01; *ms_init = t12; *ms_loop = 0;
+  if (req.init_only) {     // features + scores of the initial table edges only (TBoundaryTable::init)
+    GLIA_HIP_TRY(hipEventSynchronize(ev.ev[2]));
+    out->ms_table = ev.ms(0, 1); out->ms_init = ev.ms(1, 2); out->ms_loop = 0;
     std::vector<uint8_t> tab(E0);
     if ((rc = copy_to_host_staged(tab.data(), st.e_table, E0))) return rc;
     int64_t nt = 0;
     for (uint8_t t : tab) nt += t;
-    *n_scored = nt;
-    *n_merges = (int64_t)E0;            // init-only calls report the number of records here
-    if (h_scores && (rc = copy_to_host_staged(h_scores, st.pq.leaf_sal, sizeof(double) * E0))) return rc;
+    out->n_scored = nt;
+    out->n = (int64_t)E0;            // init-only calls report the number of records here
+    if (req.scores) {
+      out->sal.resize(E0);
+      if ((rc = copy_to_host_staged(out->sal.data(), st.pq.leaf_sal, sizeof(double) * E0))) return rc;
+    }
     return GLIA_HMT_OK;
   }
   st.max_iters = 1ull << 14;
@@ -1977,58 +1952,41 @@ int GLIA_BC_ENTRY(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier
     GLIA_HIP_TRY(hipGetLastError());
     GLIA_HIP_TRY(hipMemcpyAsync(ctrl, st.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
-    if (ctrl[3] == ST_RUN) continue;
     if (ctrl[3] == ST_DONE) break;
-    if (ctrl[3] == ST_NEED_POOL) {
-      const unsigned long long ncap = st.pool_cap * 2;
-      if ((rc = buf.grow(&st.pool, (size_t)st.pool_cap, (size_t)ncap, stream))) return rc;
-      for (int c = 0; c < cfg.K; ++c) if ((rc = buf.grow(&st.ch[c].pool_dir, (size_t)st.pool_cap, (size_t)ncap, stream))) return rc;
-      st.pool_cap = ncap;
-    } else if (ctrl[3] == ST_NEED_EDGES) {
-      if (st.Ecap >= 0xFFFFFF00u) { set_error("greedy: more than 2^32 edge slots needed"); return GLIA_HMT_ERR_ARG; }
-      const uint32_t ocap = st.Ecap;
-      const uint32_t ncap = (uint32_t)std::min<unsigned long long>(0xFFFFFF00ull, (unsigned long long)ocap * 2ull);
-      if ((rc = buf.grow(&st.e_u, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.e_v, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.e_posu, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.e_posv, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.e_alive, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.e_table, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.e_orient, ocap, ncap, stream))) return rc;
-      for (int c = 0; c < cfg.K; ++c) {
-        if ((rc = buf.grow(&st.ch[c].e_A, ocap, ncap, stream))) return rc;
-        if ((rc = buf.grow(&st.ch[c].e_NA, ocap, ncap, stream))) return rc;
-        if ((rc = buf.grow(&st.ch[c].e_dir, (size_t)ocap * 4, (size_t)ncap * 4, stream))) return rc;
+    switch (ctrl[3]) {
+      case ST_RUN: continue;                    // max_iters reached
+      case ST_BAD_SALIENCY:
+        // in this kernel: a helper workgroup did not answer within the spin limit, and the round's scores came from a stale
+        // vote buffer -- the order is wrong, and a second run would hide that
+        set_error("merge_order_bc: helper workgroups were lost (no answer within the spin limit), the order is not the reference's (internal error)");
+        return GLIA_HMT_ERR_INTERNAL;
+      case ST_NEED_POOL: {
+        const unsigned long long ncap = st.pool_cap * 2;
+        if ((rc = entries.grow(buf, (size_t)st.pool_cap, (size_t)ncap, stream))) return rc;
+        st.pool_cap = ncap;
+        break;
       }
-      if ((rc = buf.grow(&st.e_fhead, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.e_ftail, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.pq.leaf_sal, ocap, ncap, stream))) return rc;
-      if ((rc = buf.grow(&st.pq.leaf_seq, ocap, ncap, stream))) return rc;
-      st.Ecap = ncap; st.pq.nleaves = ncap;
-      hipLaunchKernelGGL(bc_init_dead, dim3((ncap - ocap + 255) / 256), dim3(256), 0, stream, st, ocap);
-      if ((rc = pq_setup(buf, st.pq, stream))) return rc;
+      case ST_NEED_EDGES: {
+        if (st.Ecap >= kMaxEdgeSlots) { set_error("greedy: more than 2^32 edge slots needed"); return GLIA_HMT_ERR_ARG; }
+        const uint32_t ocap = st.Ecap, ncap = (uint32_t)std::min<unsigned long long>(kMaxEdgeSlots, (unsigned long long)ocap * 2ull);
+        if ((rc = edges.grow(buf, ocap, ncap, stream))) return rc;
+        st.Ecap = ncap; st.pq.nleaves = ncap;
+        hipLaunchKernelGGL(bc_init_dead, dim3((ncap - ocap + 255) / 256), dim3(256), 0, stream, st, ocap);
+        if ((rc = pq_setup(buf, st.pq, stream))) return rc;
+        break;
+      }
+      default:
+        set_error("greedy_bc: the loop kernel stopped with status " + std::to_string(ctrl[3]) + ", which its driver does not handle (internal error)");
+        return GLIA_HMT_ERR_INTERNAL;
     }
     unsigned long long zero = ST_RUN;
     GLIA_HIP_TRY(hipMemcpyAsync(st.ctrl + 3, &zero, sizeof(zero), hipMemcpyHostToDevice, stream));
   }
-  GLIA_HIP_TRY(hipEventRecord(ev[3], stream));
-  GLIA_HIP_TRY(hipEventSynchronize(ev[3]));
-  float t01 = 0, t12 = 0, t23 = 0;
-  (void)hipEventElapsedTime(&t01, ev[0], ev[1]);
-  (void)hipEventElapsedTime(&t12, ev[1], ev[2]);
-  (void)hipEventElapsedTime(&t23, ev[2], ev[3]);
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  *ms_table = t01; *ms_init = t12; *ms_loop = t23;
-  const int64_t n = (int64_t)ctrl[0];
-  *n_scored = (int64_t)ctrl[1];
-  if (n > capacity) { set_error("merge_order_bc: output capacity too small"); return GLIA_HMT_ERR_CAPACITY; }
-  if (n) {
-    if ((rc = copy_to_host_staged(h_order, st.order, sizeof(uint32_t) * 3 * n))) return rc;
-    if ((rc = copy_to_host_staged(h_sal, st.sal_out, sizeof(double) * n))) return rc;
-    if (h_feats && (rc = copy_to_host_staged(h_feats, st.feats_out, sizeof(double) * (size_t)n * cfg.fdim))) return rc;
-  }
-  *n_merges = n;
-  return GLIA_HMT_OK;
+  GLIA_HIP_TRY(hipEventRecord(ev.ev[3], stream));
+  GLIA_HIP_TRY(hipEventSynchronize(ev.ev[3]));
+  out->ms_table = ev.ms(0, 1); out->ms_init = ev.ms(1, 2); out->ms_loop = ev.ms(2, 3);
+  out->n_scored = (int64_t)ctrl[1];
+  return copy_merges(out, (int64_t)ctrl[0], st.order, st.sal_out, req.rows ? st.feats_out : nullptr, (size_t)cfg.fdim);
 }
 
 }  // namespace glia

@@ -1,6 +1,7 @@
 // glia_amd/csrc/greedy_common.hpp -- pieces shared by the greedy merge kernels (pb-mean and classifier linkage):
 // the 64-ary tournament tree used as priority queue and small host helpers.
 #pragma once
+#include <algorithm>
 #include <cstring>
 #include <mutex>
 
@@ -496,16 +497,85 @@ struct DeviceBuffers {
     if (zero) GLIA_HIP_TRY(hipMemsetAsync(*p, 0, sizeof(T) * (n ? n : 1), s));
     return GLIA_HMT_OK;
   }
-  template <typename T> int grow(T** p, size_t old_n, size_t new_n, hipStream_t s) {
-    T* q = nullptr;
-    GLIA_HIP_TRY(hipMalloc((void**)&q, sizeof(T) * (new_n ? new_n : 1)));
-    GLIA_HIP_TRY(hipMemcpyAsync(q, *p, sizeof(T) * old_n, hipMemcpyDeviceToDevice, s));
+  // a block replaced by one of new_bytes that starts with its first old_bytes
+  int grow(void** p, size_t old_bytes, size_t new_bytes, hipStream_t s) {
+    void* q = nullptr;
+    GLIA_HIP_TRY(hipMalloc(&q, new_bytes));
+    GLIA_HIP_TRY(hipMemcpyAsync(q, *p, old_bytes, hipMemcpyDeviceToDevice, s));
     GLIA_HIP_TRY(hipStreamSynchronize(s));
-    for (size_t i = 0; i < all.size(); ++i) if (all[i] == (void*)*p) { (void)hipFree(all[i]); all[i] = q; sizes[i] = sizeof(T) * (new_n ? new_n : 1); }
+    for (size_t i = 0; i < all.size(); ++i) if (all[i] == *p) { (void)hipFree(all[i]); all[i] = q; sizes[i] = new_bytes; }
     *p = q;
     return GLIA_HMT_OK;
   }
 };
+
+// The arrays a loop kernel fills up to one capacity -- edge slots, list entries or values -- each registered once with the
+// elements it holds per unit of capacity; an ST_NEED_* handler grows them all with one call.
+struct GrowList {
+  struct Item { void** p; size_t unit_bytes; };
+  std::vector<Item> items;
+  template <typename T> int add(DeviceBuffers& buf, T** p, size_t cap, hipStream_t s, bool zero = false, size_t per_unit = 1) {
+    if (int rc = buf.get(p, cap * per_unit, zero, s)) return rc;
+    items.push_back({(void**)p, sizeof(T) * per_unit});
+    return GLIA_HMT_OK;
+  }
+  template <typename T> void remove(T** p) {
+    for (size_t i = 0; i < items.size(); ++i) if (items[i].p == (void**)p) { items.erase(items.begin() + (long)i); return; }
+  }
+  // every array to new_cap units, keeping its first keep units
+  int grow(DeviceBuffers& buf, size_t keep, size_t new_cap, hipStream_t s) {
+    for (const Item& it : items) if (int rc = buf.grow(it.p, it.unit_bytes * keep, it.unit_bytes * new_cap, s)) return rc;
+    return GLIA_HMT_OK;
+  }
+};
+
+// Initial capacities of a merge loop: edge slots and list entries proportional to the initial edges E0, plus slack.
+// GLIA_HMT_MINCAP (tests) starts at the smallest the set-up accepts -- one slot more than E0, the 2 E0 entries of the initial
+// lists -- so that every growth path runs on test-sized volumes; the results are the same.
+constexpr uint32_t kMaxEdgeSlots = 0xFFFFFF00u;
+// Returns whether GLIA_HMT_MINCAP is set.
+inline bool initial_capacities(uint32_t E0, unsigned long long slots_per_edge, unsigned long long entries_per_edge, uint32_t* Ecap,
+                               unsigned long long* pool_cap) {
+  const bool mincap = option("GLIA_HMT_MINCAP");
+  *Ecap = (uint32_t)std::min<unsigned long long>(kMaxEdgeSlots, mincap ? E0 + 1ull : (unsigned long long)E0 * slots_per_edge + (1u << 16));
+  *pool_cap = mincap ? 2ull * E0 : (unsigned long long)E0 * entries_per_edge + (1u << 16);
+  return mincap;
+}
+// the outputs of a loop's n merges into *out: order [n][3] and saliencies [n], feature rows [n][fdim] when d_rows is given
+inline int copy_merges(MergeResult* out, int64_t n, const uint32_t* d_order, const double* d_sal, const double* d_rows = nullptr, size_t fdim = 0) {
+  out->order.resize(3 * (size_t)n);
+  out->sal.resize((size_t)n);
+  if (d_rows) out->rows.resize((size_t)n * fdim);
+  int rc;
+  if (n) {
+    if ((rc = copy_to_host_staged(out->order.data(), d_order, sizeof(uint32_t) * out->order.size()))) return rc;
+    if ((rc = copy_to_host_staged(out->sal.data(), d_sal, sizeof(double) * out->sal.size()))) return rc;
+    if (d_rows && (rc = copy_to_host_staged(out->rows.data(), d_rows, sizeof(double) * out->rows.size()))) return rc;
+  }
+  out->n = n;
+  return GLIA_HMT_OK;
+}
+
+// The timing events of one call, destroyed on every return path.
+template <int N> struct CallEvents {
+  hipEvent_t ev[N] = {};
+  CallEvents() = default;
+  CallEvents(const CallEvents&) = delete;
+  ~CallEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+  int create() { for (hipEvent_t& e : ev) GLIA_HIP_TRY(hipEventCreate(&e)); return GLIA_HMT_OK; }
+  float ms(int from, int to) const { float t = 0; (void)hipEventElapsedTime(&t, ev[from], ev[to]); return t; }
+};
+
+// rocPRIM's two-call idiom: run(temp, bytes) returns the rocPRIM call's status; it is called once without storage to size the
+// scratch, which is then taken from `buf`, and once more to do the work.
+template <typename Run> int rocprim_run(DeviceBuffers& buf, hipStream_t s, Run&& run) {
+  size_t bytes = 0;
+  GLIA_HIP_TRY(run(nullptr, bytes));
+  char* tmp;
+  if (int rc = buf.get(&tmp, bytes ? bytes : 16, false, s)) return rc;
+  GLIA_HIP_TRY(run((void*)tmp, bytes));
+  return GLIA_HMT_OK;
+}
 
 // binary searches over the sorted compact RAG
 __device__ __forceinline__ long long find_pair(const uint32_t* pa, const uint32_t* pb, long long P, uint32_t a, uint32_t b) {

@@ -17,6 +17,8 @@ unsigned long long internal_errors();
 void count_internal_error();
 // dense ids: every merge k joins two regions that still exist and creates region R + k (util/struct_merge.hxx:19-31)
 bool merge_order_is_consistent(const uint32_t* dense_order, int64_t n, uint32_t R, int64_t* first_bad);
+// the end of every merge loop call: an order that fails the replay becomes GLIA_HMT_ERR_INTERNAL, and every internal error is counted
+int finish_merge_order(int rc, const uint32_t* dense_order, int64_t n, uint32_t R, hipStream_t stream);
 #define GLIA_HIP_TRY(expr)                                                                       \
   do {                                                                                           \
     hipError_t _e = (expr);                                                                      \
@@ -129,30 +131,47 @@ struct MedianFeatIn {
   const uint32_t* forced; int64_t n_merges;
 };
 int median_feature_stats(const MedianFeatIn& in, hipStream_t stream, std::vector<double>* reg, std::vector<double>* bnd, std::vector<unsigned long long>* area);
-int greedy_mean(const RagArrays& rag, hipStream_t stream, uint32_t* h_order, double* h_sal, int64_t capacity,
-                int64_t* n_merges, double* ms_table, double* ms_loop, int64_t* n_scored, int cond_n = 0,
-                const long long* cond_sizes = nullptr, double cond_rpb = 0.0, const VolumeRef* median_of = nullptr,
-                bool size_weight = false);
+// What a merge loop returns: the order in dense ids (leaf i = i-th label ascending, merged region R + k) -- [n][3] -- with the
+// saliencies, optionally the feature row of every merge, the edges scored, and the times of the table, the initial scores and
+// the loop.
+struct MergeResult {
+  std::vector<uint32_t> order;
+  std::vector<double> sal, rows;
+  int64_t n = 0, n_scored = 0;
+  double ms_table = 0.0, ms_init = 0.0, ms_loop = 0.0;
+};
+// the pb-mean, median and pre_merge loops
+struct PbRequest {
+  int cond_n = 0;                               // pre_merge condition (gadget/main_pre_merge.cxx:27-76): 0 = none, else 1 or 2 thresholds
+  long long cond_sizes[2] = {0, 0};
+  double cond_rpb = 0.0;
+  const VolumeRef* median_of = nullptr;         // median linkage: the volume the RAG was built from
+  bool size_weight = false;                     // ...AndMinSize linkage
+};
+int greedy_mean(const RagArrays& rag, hipStream_t stream, const PbRequest& req, MergeResult* out);
 struct BcCfg;
 struct DeviceClassifier;
+// the classifier loop
+struct BcRequest {
+  const uint32_t* forced = nullptr;             // a given order (bc_feat): dense region pairs [n_forced][2]; the classifier is not run
+  int64_t n_forced = 0;
+  bool rows = false;                            // MergeResult::rows wanted
+  bool init_only = false;                       // features + scores of the initial records only (TBoundaryTable::init): n = records
+  bool scores = false;                          // init_only: MergeResult::sal = the records' scores
+  int shard = 0, n_shards = 1;
+};
 // greedy_bc.hip is compiled five times: with the libm restatements of the feature code (glibc_math.hpp) selected at run time
 // (any combination, incl. "unpinned"), and with the two combinations real hosts have -- glibc's FMA build and its non-FMA
 // build -- fixed at compile time (a run-time choice between three logarithms at every call site costs the classifier loop
 // 5 %).  greedy_bc() picks the instance from cfg.libm_* (api.cpp).
-#define GLIA_DECLARE_GREEDY_BC(name)                                                                                          \
-  int name(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier& clf, hipStream_t stream, uint32_t* h_order,       \
-           double* h_sal, double* h_feats, int64_t capacity, int64_t* n_merges, double* ms_table, double* ms_init,           \
-           double* ms_loop, int64_t* n_scored, bool init_only, const uint32_t* h_forced, int64_t n_forced, int shard,        \
-           int n_shards, double* h_scores)
+#define GLIA_DECLARE_GREEDY_BC(name) \
+  int name(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier& clf, hipStream_t stream, const BcRequest& req, MergeResult* out)
 GLIA_DECLARE_GREEDY_BC(greedy_bc_generic);
 GLIA_DECLARE_GREEDY_BC(greedy_bc_fma);
 GLIA_DECLARE_GREEDY_BC(greedy_bc_sse2);
 GLIA_DECLARE_GREEDY_BC(greedy_bc_fma_common);      // + GLIA_BC_COMMON (bc_features.hpp): one image on the region and boundary lists, no --logs / --simpf / histogram columns
 GLIA_DECLARE_GREEDY_BC(greedy_bc_sse2_common);
-int greedy_bc(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier& clf, hipStream_t stream, uint32_t* h_order,
-              double* h_sal, double* h_feats, int64_t capacity, int64_t* n_merges, double* ms_table, double* ms_init,
-              double* ms_loop, int64_t* n_scored, bool init_only, const uint32_t* h_forced = nullptr,
-              int64_t n_forced = 0, int shard = 0, int n_shards = 1, double* h_scores = nullptr);
+GLIA_DECLARE_GREEDY_BC(greedy_bc);
 int compact_tables(const AccParams& p, uint32_t rcap, uint32_t pcap, RagArrays* out, hipStream_t stream);
 int transform_keys(const uint32_t* order, int64_t n, std::vector<uint32_t>* src, std::vector<uint32_t>* dst);
 int transform_image(uint32_t* d_lab, int64_t n, const uint32_t* h_src, const uint32_t* h_dst, int64_t m, const uint32_t* d_mask,

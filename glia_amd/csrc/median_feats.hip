@@ -153,11 +153,8 @@ int set_stats(const float* src, const std::vector<Run>& runs, const std::vector<
       GLIA_HIP_TRY(hipMemcpyAsync(d_dst, h_dst.data(), 8 * ((size_t)nr + 1), hipMemcpyHostToDevice, stream));
       GLIA_HIP_TRY(hipMemcpyAsync(d_seg, h_seg.data(), 4 * ((size_t)ns + 1), hipMemcpyHostToDevice, stream));
       hipLaunchKernelGGL(mf_expand, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src, d_src, d_dst, nr, total, d_a);
-      size_t tmp = 0;
-      GLIA_HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, tmp, d_a, d_b, (unsigned)total, ns, d_seg, d_seg + 1, 0, 32, stream));
-      char* d_tmp;
-      if ((rc = buf.get(&d_tmp, tmp ? tmp : 16, false, stream))) return rc;
-      GLIA_HIP_TRY(rocprim::segmented_radix_sort_keys((void*)d_tmp, tmp, d_a, d_b, (unsigned)total, ns, d_seg, d_seg + 1, 0, 32, stream));
+      if ((rc = rocprim_run(buf, stream, [&](void* t, size_t& b) {
+            return rocprim::segmented_radix_sort_keys(t, b, d_a, d_b, (unsigned)total, ns, d_seg, d_seg + 1, 0, 32, stream); }))) return rc;
       hipLaunchKernelGGL(mf_set_stats, dim3(ns), dim3(256), 0, stream, d_b, d_seg, ns, d_out);
       GLIA_HIP_TRY(hipGetLastError());
       GLIA_HIP_TRY(hipMemcpyAsync(out->data() + 3 * j0, d_out, sizeof(double) * 3 * (size_t)ns, hipMemcpyDeviceToHost, stream));

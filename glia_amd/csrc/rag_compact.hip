@@ -94,13 +94,8 @@ int sort_used(DeviceBuffers& buf, K* d_keys, uint32_t cap, K** d_sorted_keys, ui
   uint32_t* d_s2 = nullptr;
   if ((rc = buf.get(&d_k2, (size_t)(n ? n : 1), false, stream))) return rc;
   if ((rc = buf.get(&d_s2, (size_t)(n ? n : 1), false, stream))) return rc;
-  if (n) {
-    size_t tmp_bytes = 0;
-    GLIA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_k, d_k2, d_s, d_s2, (size_t)n, 0, sizeof(K) * 8, stream));
-    char* d_tmp = nullptr;
-    if ((rc = buf.get(&d_tmp, tmp_bytes ? tmp_bytes : 16, false, stream))) return rc;
-    GLIA_HIP_TRY(rocprim::radix_sort_pairs((void*)d_tmp, tmp_bytes, d_k, d_k2, d_s, d_s2, (size_t)n, 0, sizeof(K) * 8, stream));
-  }
+  if (n && (rc = rocprim_run(buf, stream, [&](void* t, size_t& b) {
+        return rocprim::radix_sort_pairs(t, b, d_k, d_k2, d_s, d_s2, (size_t)n, 0, sizeof(K) * 8, stream); }))) return rc;
   *d_sorted_keys = d_k2;
   *d_sorted_slots = d_s2;
   *n_out = n;

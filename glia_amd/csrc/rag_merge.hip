@@ -99,11 +99,8 @@ int gather_value_runs(const unsigned long long* src_off, const float* src_vals, 
     unsigned long long* cnt;
     if ((rc = buf.get(&cnt, (size_t)n + 1, false, stream))) return rc;
     hipLaunchKernelGGL(run_counts, dim3((n + 256) / 256), dim3(256), 0, stream, src_off, order, n, cnt);
-    size_t tmp = 0;
-    GLIA_HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, cnt, *out_off, 0ull, (size_t)n + 1, rocprim::plus<unsigned long long>(), stream));
-    char* d_tmp;
-    if ((rc = buf.get(&d_tmp, tmp ? tmp : 16, false, stream))) return rc;
-    GLIA_HIP_TRY(rocprim::exclusive_scan((void*)d_tmp, tmp, cnt, *out_off, 0ull, (size_t)n + 1, rocprim::plus<unsigned long long>(), stream));
+    if ((rc = rocprim_run(buf, stream, [&](void* t, size_t& b) {
+          return rocprim::exclusive_scan(t, b, cnt, *out_off, 0ull, (size_t)n + 1, rocprim::plus<unsigned long long>(), stream); }))) return rc;
     GLIA_HIP_TRY(hipMemcpyAsync(&total, *out_off + n, sizeof(total), hipMemcpyDeviceToHost, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
   } else GLIA_HIP_TRY(hipMemsetAsync(*out_off, 0, sizeof(unsigned long long), stream));
@@ -160,11 +157,8 @@ int collect_pair_values(RagArrays* rag, const VolumeRef& vol, hipStream_t stream
   if ((rc = buf.get(&cursor, (size_t)P + 1, true, stream))) return rc;
   GLIA_HIP_TRY(hipMalloc(&rag->d_pv_off, sizeof(unsigned long long) * ((size_t)P + 1)));
   hipLaunchKernelGGL(pair_counts_u64, dim3((P + 256) / 256), dim3(256), 0, stream, rag->d_prec, P, cnt);
-  size_t tmp = 0;
-  GLIA_HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, cnt, rag->d_pv_off, 0ull, (size_t)P + 1, rocprim::plus<unsigned long long>(), stream));
-  char* d_tmp;
-  if ((rc = buf.get(&d_tmp, tmp ? tmp : 16, false, stream))) return rc;
-  GLIA_HIP_TRY(rocprim::exclusive_scan((void*)d_tmp, tmp, cnt, rag->d_pv_off, 0ull, (size_t)P + 1, rocprim::plus<unsigned long long>(), stream));
+  if ((rc = rocprim_run(buf, stream, [&](void* t, size_t& b) {
+        return rocprim::exclusive_scan(t, b, cnt, rag->d_pv_off, 0ull, (size_t)P + 1, rocprim::plus<unsigned long long>(), stream); }))) return rc;
   unsigned long long total = 0;
   GLIA_HIP_TRY(hipMemcpyAsync(&total, rag->d_pv_off + P, sizeof(total), hipMemcpyDeviceToHost, stream));
   GLIA_HIP_TRY(hipStreamSynchronize(stream));
@@ -220,17 +214,10 @@ int merge_kind(const RagArrays* parts, int n_parts, RagArrays* out, hipStream_t 
   const int shift = REGION ? 8 : 0;
   uint32_t nout = 0;
   if (n) {
-    size_t tmp = 0;
-    GLIA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, k0, k1, i0, i1, (size_t)n, 0, 64, stream));
-    char* d_tmp;
-    if ((rc = buf.get(&d_tmp, tmp ? tmp : 16, false, stream))) return rc;
-    GLIA_HIP_TRY(rocprim::radix_sort_pairs((void*)d_tmp, tmp, k0, k1, i0, i1, (size_t)n, 0, 64, stream));
+    if ((rc = rocprim_run(buf, stream, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, k0, k1, i0, i1, (size_t)n, 0, 64, stream); }))) return rc;
     hipLaunchKernelGGL(head_flags, dim3((n + 255) / 256), dim3(256), 0, stream, k1, flag, n, shift);
-    size_t tmp2 = 0;
-    GLIA_HIP_TRY(rocprim::exclusive_scan(nullptr, tmp2, flag, oidx, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), stream));
-    char* d_tmp2;
-    if ((rc = buf.get(&d_tmp2, tmp2 ? tmp2 : 16, false, stream))) return rc;
-    GLIA_HIP_TRY(rocprim::exclusive_scan((void*)d_tmp2, tmp2, flag, oidx, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), stream));
+    if ((rc = rocprim_run(buf, stream, [&](void* t, size_t& b) {
+          return rocprim::exclusive_scan(t, b, flag, oidx, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), stream); }))) return rc;
     GLIA_HIP_TRY(hipMemcpyAsync(&nout, oidx + n, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
   }
@@ -344,11 +331,7 @@ int rag_cut_flags(const RagArrays& rag, const uint32_t* d_lab, int64_t nx, int64
   if ((rc = buf.get(&l1, (size_t)n, false, stream))) return rc;
   GLIA_HIP_TRY(hipMemcpyAsync(d_planes, planes, sizeof(long long) * np, hipMemcpyHostToDevice, stream));
   hipLaunchKernelGGL(gather_plane_labels, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_lab, pv, d_planes, np, l0);
-  size_t tmp = 0;
-  GLIA_HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp, l0, l1, (size_t)n, 0, 32, stream));
-  char* d_tmp;
-  if ((rc = buf.get(&d_tmp, tmp ? tmp : 16, false, stream))) return rc;
-  GLIA_HIP_TRY(rocprim::radix_sort_keys((void*)d_tmp, tmp, l0, l1, (size_t)n, 0, 32, stream));
+  if ((rc = rocprim_run(buf, stream, [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, l0, l1, (size_t)n, 0, 32, stream); }))) return rc;
   const uint32_t m = R > P ? R : P;
   if (m) hipLaunchKernelGGL(cut_flags_kernel, dim3((m + 255) / 256), dim3(256), 0, stream, l1, (uint32_t)n, rag.d_rlabel, R, rag.d_pa, rag.d_pb, P, d_rflag, d_pflag);
   GLIA_HIP_TRY(hipGetLastError());

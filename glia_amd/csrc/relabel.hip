@@ -13,6 +13,7 @@
 #include <rocprim/device/device_run_length_encode.hpp>
 
 #include "hmt_internal.hpp"
+#include "greedy_common.hpp"      // CallEvents
 
 namespace glia {
 
@@ -193,8 +194,8 @@ int transform_image(uint32_t* d_lab, int64_t n, const uint32_t* h_src, const uin
     GLIA_HIP_TRY(hipMemcpyAsync(db, d.data(), sizeof(uint32_t) * s.size(), hipMemcpyHostToDevice, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
   }
-  hipEvent_t e0, e1;
-  GLIA_HIP_TRY(hipEventCreate(&e0)); GLIA_HIP_TRY(hipEventCreate(&e1));
+  CallEvents<2> ev;
+  if (int rc = ev.create()) return rc;
   // The first launch of a kernel of this translation unit loads its code object (this file's holds rocPRIM's sorts since the sparse
   // relabelling path of round 3: several milliseconds) -- on the host, between the two events.  Asking for the kernel's attributes loads it
   // here, so that the reported time is the kernel's (round 3's closing set reported 12.0 ms for a 4 ms kernel; tools/transform_bench.py).
@@ -204,16 +205,13 @@ int transform_image(uint32_t* d_lab, int64_t n, const uint32_t* h_src, const uin
   }
   const long long threads = (n + 3) / 4;
   const unsigned blocks = (unsigned)((threads + 255) / 256);
-  GLIA_HIP_TRY(hipEventRecord(e0, stream));
+  GLIA_HIP_TRY(hipEventRecord(ev.ev[0], stream));
   if (dense) hipLaunchKernelGGL(transform_kernel<true>, dim3(blocks), dim3(256), 0, stream, d_lab, (long long)n, da, db, mm, d_mask, fill_missing);
   else hipLaunchKernelGGL(transform_kernel<false>, dim3(blocks), dim3(256), 0, stream, d_lab, (long long)n, da, db, mm, d_mask, fill_missing);
   GLIA_HIP_TRY(hipGetLastError());
-  GLIA_HIP_TRY(hipEventRecord(e1, stream));
-  GLIA_HIP_TRY(hipEventSynchronize(e1));
-  float t = 0;
-  (void)hipEventElapsedTime(&t, e0, e1);
-  if (ms) *ms = t;
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  GLIA_HIP_TRY(hipEventRecord(ev.ev[1], stream));
+  GLIA_HIP_TRY(hipEventSynchronize(ev.ev[1]));
+  if (ms) *ms = ev.ms(0, 1);
   (void)hipFree(da);
   if (db) (void)hipFree(db);
   return GLIA_HMT_OK;

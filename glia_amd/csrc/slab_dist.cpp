@@ -155,11 +155,8 @@ int sort_by_destination(const RagArrays& a, const uint8_t* d_rcut, const uint8_t
       if ((rc = buf.get(&k0, n, false, s)) || (rc = buf.get(&k1, n, false, s)) || (rc = buf.get(&i0, n, false, s)) || (rc = buf.get(&i1, n, false, s)) ||
           (rc = buf.get(&d_cnt, (size_t)world + 1, true, s))) return rc;
       hipLaunchKernelGGL(dest_keys, dim3((n + 255) / 256), dim3(256), 0, s, kind ? a.d_pa : a.d_rlabel, kind ? d_pcut : d_rcut, n, (uint32_t)world, k0, i0, d_cnt);
-      size_t tmp = 0;
-      GLIA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, k0, k1, i0, i1, (size_t)n, 0, 16, s));      // stable: the records of a destination keep their (sorted-by-key) order
-      char* d_tmp;
-      if ((rc = buf.get(&d_tmp, tmp ? tmp : 16, false, s))) return rc;
-      GLIA_HIP_TRY(rocprim::radix_sort_pairs((void*)d_tmp, tmp, k0, k1, i0, i1, (size_t)n, 0, 16, s));
+      // stable: the records of a destination keep their (sorted-by-key) order
+      if ((rc = rocprim_run(buf, s, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, k0, k1, i0, i1, (size_t)n, 0, 16, s); }))) return rc;
       hipLaunchKernelGGL(permute_rows, dim3((n + 255) / 256), dim3(256), 0, s, kind ? a.d_pa : a.d_rlabel, i1, n, 1, lab);
       if (kind) hipLaunchKernelGGL(permute_rows, dim3((n + 255) / 256), dim3(256), 0, s, a.d_pb, i1, n, 1, lab2);
       for (int c = 0; c < a.K; ++c) {
@@ -182,11 +179,7 @@ int sort_by_destination(const RagArrays& a, const uint8_t* d_rcut, const uint8_t
         if ((rc = buf2.get(&k0, n, false, s)) || (rc = buf2.get(&k1, n, false, s)) || (rc = buf2.get(&i0, n, false, s)) || (rc = buf2.get(&i1, n, false, s)) ||
             (rc = buf2.get(&d_cnt, (size_t)world + 1, true, s))) return rc;
         hipLaunchKernelGGL(dest_keys, dim3((n + 255) / 256), dim3(256), 0, s, a.d_pa, d_pcut, n, (uint32_t)world, k0, i0, d_cnt);
-        size_t tmp = 0;
-        GLIA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, k0, k1, i0, i1, (size_t)n, 0, 16, s));
-        char* d_tmp;
-        if ((rc = buf2.get(&d_tmp, tmp ? tmp : 16, false, s))) return rc;
-        GLIA_HIP_TRY(rocprim::radix_sort_pairs((void*)d_tmp, tmp, k0, k1, i0, i1, (size_t)n, 0, 16, s));
+        if ((rc = rocprim_run(buf2, s, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, k0, k1, i0, i1, (size_t)n, 0, 16, s); }))) return rc;
         if ((rc = gather_value_runs(a.d_pv_off, a.d_pv, i1, n, &out->arr.d_pv_off, &out->arr.d_pv, &out->arr.nV, s))) return rc;
         out->owned.push_back(out->arr.d_pv_off); out->owned.push_back(out->arr.d_pv);
         std::vector<unsigned long long> off((size_t)n + 1);
@@ -235,11 +228,8 @@ int block_value_offsets(Block* b, hipStream_t s, std::vector<void*>* scratch) {
   GLIA_HIP_TRY(hipMalloc(&b->pv_off, sizeof(unsigned long long) * ((size_t)P + 1)));
   scratch->push_back(b->pv_off);
   hipLaunchKernelGGL(block_counts, dim3((P + 256) / 256), dim3(256), 0, s, b->prec(0), P, cnt);
-  size_t tmp = 0;
-  GLIA_HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, cnt, b->pv_off, 0ull, (size_t)P + 1, rocprim::plus<unsigned long long>(), s));
-  char* d_tmp;
-  if ((rc = buf.get(&d_tmp, tmp ? tmp : 16, false, s))) return rc;
-  GLIA_HIP_TRY(rocprim::exclusive_scan((void*)d_tmp, tmp, cnt, b->pv_off, 0ull, (size_t)P + 1, rocprim::plus<unsigned long long>(), s));
+  if ((rc = rocprim_run(buf, s, [&](void* t, size_t& bytes) {
+        return rocprim::exclusive_scan(t, bytes, cnt, b->pv_off, 0ull, (size_t)P + 1, rocprim::plus<unsigned long long>(), s); }))) return rc;
   GLIA_HIP_TRY(hipStreamSynchronize(s));
   return GLIA_HMT_OK;
 }

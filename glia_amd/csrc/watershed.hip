@@ -308,7 +308,6 @@ int watershed_labels(int dim, const int64_t dims[3], const float* d_img, double 
   float* A = nullptr;
   unsigned long long* B = nullptr;
   uint32_t *haslower = nullptr, *changed = nullptr;
-  char* tmp = nullptr;
   int total_sweeps = 0;
   // the scratch blocks come from the process-wide block cache (greedy_common.hpp): hipMalloc / hipFree of gigabyte blocks cost
   // more than the kernels (measured: 160 ms of a 215 ms call at 512^3)
@@ -355,12 +354,8 @@ int watershed_labels(int dim, const int64_t dims[3], const float* d_img, double 
   WS_TRY(hipMemsetAsync(haslower, 0, 4 * (size_t)((n + 31) / 32), stream));
   hipLaunchKernelGGL(ws_lower_flag, dim3(blocks), dim3(256), 0, stream, G, g, comp, haslower);
   hipLaunchKernelGGL(ws_root_flag, dim3(blocks), dim3(256), 0, stream, G, comp, haslower, root);
-  {
-    size_t bytes = 0;
-    WS_TRY(rocprim::exclusive_scan(nullptr, bytes, root, rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    WS_GET(tmp, bytes ? bytes : 16);
-    WS_TRY(rocprim::exclusive_scan(tmp, bytes, root, rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
-  }
+  if (int rc = rocprim_run(buf, stream, [&](void* t, size_t& b) {
+        return rocprim::exclusive_scan(t, b, root, rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream); })) return fail(rc);
   uint32_t last[2] = {0, 0};                          // markers = rank[n-1] + root[n-1]
   WS_TRY(hipMemcpyAsync(&last[0], rank + (n - 1), 4, hipMemcpyDeviceToHost, stream));
   WS_TRY(hipMemcpyAsync(&last[1], root + (n - 1), 4, hipMemcpyDeviceToHost, stream));

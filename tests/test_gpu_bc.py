@@ -92,11 +92,12 @@ def test_random_forest_matches_oracle(ctx, shape, S, G, ntree, depth):
     assert (sal == s_ref).all()              # votes / ntree: exact
     assert _feat_close(feats, f_ref)
     # the forest is walked by helper workgroups (63 by default); the result may not depend on how many there are:
-    # 0 = the contraction workgroup walks the trees itself, 5 = every helper takes several records of a chunk
-    for nh in ("0", "5"):
-        with hmt.options(GLIA_HMT_HELPERS=nh):
+    # 0 = the contraction workgroup walks the trees itself, 5 = every helper takes several records of a chunk.
+    # GLIA_HMT_MINCAP: the smallest initial capacities, so that edge slots and list entries grow mid-run with helpers at work
+    for env in (dict(GLIA_HMT_HELPERS="0"), dict(GLIA_HMT_HELPERS="5"), dict(GLIA_HMT_MINCAP=1)):
+        with hmt.options(**env):
             o2, s2 = rm.merge_order_bc(clf)[:2]
-        assert (o2 == o_ref).all() and (s2 == s_ref).all(), "helpers=" + nh
+        assert (o2 == o_ref).all() and (s2 == s_ref).all(), env
 
 
 @pytest.mark.parametrize("shape,S,G,ntrees", [((32, 32, 32), 8, 16, (31, 31, 31)), ((40, 36, 28), 6, 12, (15, 63, 7)), ((64, 64), 4, 16, (7, 7, 31))])

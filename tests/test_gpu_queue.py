@@ -3,10 +3,12 @@
   tournament tree (greedy_pb_kernel, round 1)  ==  window queue, one contraction at a time (greedy_window_kernel)
                                                ==  window queue, batched contractions (greedy_batch_kernel, the default)
 under conditions that force every rare path of the window queue: a tiny window (spills, evictions, cells split by the bounded
-heap), frequent re-baselines, massive exact ties, launches that end early.  The switches are library options (glia_hmt_set_option,
-hmt.options): GLIA_HMT_PB_WINDOW=0 (tree), GLIA_HMT_PB_BATCH=0 (sequential window), GLIA_HMT_WINCAP, GLIA_HMT_REBASE, ...
-No loop is ever run twice: an order that breaks the invariant of glia_hmt_check_merge_order is GLIA_HMT_ERR_INTERNAL, and the
-session ends with a check that glia_hmt_internal_errors() stayed 0 (tests/conftest.py)."""
+heap), frequent re-baselines, massive exact ties, launches that end early, the smallest initial capacities (every array grows
+mid-run).  The switches are library options (glia_hmt_set_option, hmt.options): GLIA_HMT_PB_WINDOW=0 (tree), GLIA_HMT_PB_BATCH=0
+(sequential window), GLIA_HMT_WINCAP, GLIA_HMT_REBASE, GLIA_HMT_MINCAP, ...
+No loop is ever run twice: a launch that ends with a status its driver does not handle, or an order that breaks the invariant of
+glia_hmt_check_merge_order, is GLIA_HMT_ERR_INTERNAL, and the session ends with a check that glia_hmt_internal_errors() stayed 0
+(tests/conftest.py)."""
 import numpy as np
 import pytest
 
@@ -48,7 +50,8 @@ def test_three_queues_agree(ctx, shape, S, variant, levels):
     d_lab, d_pb = _volume(ctx, shape, S, variant, levels)
     tree = _order(ctx, d_lab, d_pb, GLIA_HMT_PB_WINDOW=0)
     assert len(tree[0]) > 500
-    for env in (dict(), dict(GLIA_HMT_PB_BATCH=0)):
+    for env in (dict(), dict(GLIA_HMT_PB_BATCH=0), dict(GLIA_HMT_PB_WINDOW=0, GLIA_HMT_MINCAP=1), dict(GLIA_HMT_MINCAP=1),
+                dict(GLIA_HMT_PB_BATCH=0, GLIA_HMT_MINCAP=1)):
         o, s = _order(ctx, d_lab, d_pb, **env)
         assert o.shape == tree[0].shape and (o == tree[0]).all() and (s == tree[1]).all(), env
 
@@ -111,7 +114,7 @@ def test_pre_merge_on_a_tiny_window(ctx):
     labels, pb = O.synth((48, 48, 48), 6, 12)
     d_lab, d_pb = torch.from_numpy(labels.view(np.int32)).cuda(), torch.from_numpy(pb).cuda()
     ro, rs = O.Rag(labels).pre_merge(pb, [150, 400], 0.3)
-    for env in (dict(), dict(GLIA_HMT_WINCAP=32), dict(GLIA_HMT_REBASE=200)):
+    for env in (dict(), dict(GLIA_HMT_WINCAP=32), dict(GLIA_HMT_REBASE=200), dict(GLIA_HMT_MINCAP=1)):
         with hmt.options(**env):
             rm = hmt.RegionMap(ctx, d_lab, pb=d_pb, only_contour=False)
             o, s = rm.pre_merge([150, 400], 0.3)
