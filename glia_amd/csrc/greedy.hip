@@ -1226,76 +1226,157 @@ struct BatchShared {
   uint32_t bad;
 };
 
+// The largest and the second-largest of the 64 lanes' (a1, a2) pairs of unsigned keys -- saliency images or seqs -- (a1 >= a2
+// in every lane; as a multiset: two equal values count twice) in lane 63: a butterfly that merges two pairs per step.  The rows a row_bcast step does not write receive an
+// empty pair (0, 0) -- merging a pair with itself, harmless for a plain maximum, would count its best twice.
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ void top2_ord_step(unsigned long long& a1, unsigned long long& a2) {
+  auto mv = [](unsigned long long v) {                                   // (old value: the lanes' own where every row is written, else 0)
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(ROW_MASK == 0xf ? (int)(uint32_t)v : 0, (int)(uint32_t)v, CTRL, ROW_MASK, 0xf, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(ROW_MASK == 0xf ? (int)(uint32_t)(v >> 32) : 0, (int)(uint32_t)(v >> 32), CTRL, ROW_MASK, 0xf, false);
+    return ((unsigned long long)hi << 32) | lo;
+  };
+  const unsigned long long b1 = mv(a1), b2 = mv(a2);
+  const bool g = b1 > a1;
+  const unsigned long long hi = g ? b1 : a1, lo = g ? a1 : b1, m2 = b2 > a2 ? b2 : a2;
+  a1 = hi; a2 = lo > m2 ? lo : m2;
+}
+__device__ __forceinline__ void wave_top2_ord(unsigned long long& a1, unsigned long long& a2) {
+  top2_ord_step<0xB1>(a1, a2);          // quad_perm [1,0,3,2]
+  top2_ord_step<0x4E>(a1, a2);          // quad_perm [2,3,0,1]
+  top2_ord_step<0x124>(a1, a2);         // row_ror 4
+  top2_ord_step<0x128>(a1, a2);         // row_ror 8: every lane holds its row's pair
+  top2_ord_step<0x142, 0xa>(a1, a2);    // row_bcast 15 into rows 1 and 3
+  top2_ord_step<0x143, 0xc>(a1, a2);    // row_bcast 31 into rows 2 and 3: lane 63 holds the wave's pair
+  a1 = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(a1 >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)a1, 63);
+  a2 = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(a2 >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)a2, 63);
+}
+
 // one pass over the window: applies the deaths of the last round, leaves every wave's best and second-best item
 #ifdef GLIA_HMT_PROFILE
 __device__ unsigned long long g_scanprof[8];
+__device__ unsigned long long g_scanfill[3][3];           // scans by what came before (reload or eviction / narrow round / wide contraction) x fill n (<= 512, <= 1024, more)
 #define SCAN_T(i) do { if (tid == 0) { const unsigned long long tn_ = __builtin_readcyclecounter(); g_scanprof[i] += tn_ - st_; st_ = tn_; } } while (0)
 #else
 #define SCAN_T(i) do {} while (0)
 #endif
-__device__ __forceinline__ void batch_scan(const WinState& st, WinShared& w, BatchShared& b, int tid) {
+enum { kScanOther = 0, kScanNarrow = 1, kScanWide = 2 };   // (profiling build: what the scan follows)
+__device__ __forceinline__ void batch_scan(const WinState& st, WinShared& w, BatchShared& b, int tid, [[maybe_unused]] int from) {
 #ifdef GLIA_HMT_PROFILE
   unsigned long long st_ = __builtin_readcyclecounter();
   if (tid == 0) g_scanprof[7] += 1;
 #endif
   const uint32_t n = w.n < st.wcap ? w.n : st.wcap, nk = b.nkill < kBatchKill ? b.nkill : kBatchKill, kovf = b.kovf;
+#ifdef GLIA_HMT_PROFILE
+  if (tid == 0) g_scanfill[from][n <= 512u ? 0 : n <= 1024u ? 1 : 2] += 1;
+#endif
   // Slot ownership is STRIPED over the waves (lane l of wave v scans the l-th slot of chunk (v + l) mod 8 in every block
   // of 512): a reload fills consecutive slots with consecutive keys, and the exact top of the queue is only as long as
   // the run of best items that sit with different waves.  (Bank pattern of a wave's reads: that of consecutive slots.)
   const uint32_t own = 64u * (uint32_t)(((tid >> 6) + (tid & 63)) & 7) + (uint32_t)(tid & 63);
-  unsigned long long q[kWinPer]; uint32_t e[kWinPer]; double sl[kWinPer];
-#pragma unroll
-  for (int j = 0; j < kWinPer; ++j) { const uint32_t i = own + (uint32_t)j * kGreedyThreads; q[j] = w.seq[i]; e[j] = w.e[i]; sl[j] = w.sal[i]; }
-  const uint4 ka = *reinterpret_cast<const uint4*>(&b.kill[0]), kb = *reinterpret_cast<const uint4*>(&b.kill[4]);
-  const uint32_t kl[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
   Key k1, k2;
   k1.sal = -__builtin_inf(); k1.seq = 0; k1.arg = 0; k2 = k1;
-  SCAN_T(0);
-  // deaths: branch-free for the first eight (a short-circuit || / && chain compiles to one branch per term), a uniform
-  // loop over the rest of the list, and -- only when the list overflowed -- a look at the edge records
-  uint32_t deadm[kWinPer];
+  // Only the blocks of 512 slots below the fill are read: slots at or above n hold nothing, and n is the same in every thread
+  // (no thread writes it between the barrier before the scan and the one that ends it), so the choice is a uniform branch
+  // and a skipped block costs neither LDS reads nor VALU work.  One instance of the pass per number of blocks.
+  auto pass = [&](auto nb_tag) {
+    constexpr int NB = decltype(nb_tag)::value;
+    unsigned long long q[NB]; uint32_t e[NB]; double sl[NB];
 #pragma unroll
-  for (int j = 0; j < kWinPer; ++j) {
-    uint32_t d = 0;
+    for (int j = 0; j < NB; ++j) { const uint32_t i = own + (uint32_t)j * kGreedyThreads; q[j] = w.seq[i]; e[j] = w.e[i]; sl[j] = w.sal[i]; }
+    const uint4 ka = *reinterpret_cast<const uint4*>(&b.kill[0]), kb = *reinterpret_cast<const uint4*>(&b.kill[4]);
+    const uint32_t kl[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
+    SCAN_T(0);
+    // deaths: branch-free for the first eight (a short-circuit || / && chain compiles to one branch per term), a uniform
+    // loop over the rest of the list, and -- only when the list overflowed -- a look at the edge records
+    uint32_t deadm[NB];
 #pragma unroll
-    for (uint32_t t = 0; t < 8; ++t) d |= (uint32_t)(t < nk) & (uint32_t)(kl[t] == e[j]);
-    deadm[j] = d;
-  }
-  if (nk > 8u) {                                                         // (uniform)
-    for (uint32_t t = 8; t < nk; ++t) {
-      const uint32_t kt = b.kill[t];
+    for (int j = 0; j < NB; ++j) {
+      uint32_t d = 0;
 #pragma unroll
-      for (int j = 0; j < kWinPer; ++j) deadm[j] |= (uint32_t)(kt == e[j]);
+      for (uint32_t t = 0; t < 8; ++t) d |= (uint32_t)(t < nk) & (uint32_t)(kl[t] == e[j]);
+      deadm[j] = d;
     }
-    if (kovf) {                                                          // more deaths than the list holds (rare): ask the edge records
-      full_barrier();                                                    // (the stores that mark them are performed)
+    if (nk > 8u) {                                                       // (uniform)
+      for (uint32_t t = 8; t < nk; ++t) {
+        const uint32_t kt = b.kill[t];
 #pragma unroll
-      for (int j = 0; j < kWinPer; ++j) {
-        const uint32_t i = own + (uint32_t)j * kGreedyThreads;
-        if (i < n && q[j] != 0) deadm[j] |= (uint32_t)(st.er[e[j]].seq == 0);
+        for (int j = 0; j < NB; ++j) deadm[j] |= (uint32_t)(kt == e[j]);
+      }
+      if (kovf) {                                                        // more deaths than the list holds (rare): ask the edge records
+        full_barrier();                                                  // (the stores that mark them are performed)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          const uint32_t i = own + (uint32_t)j * kGreedyThreads;
+          if (i < n && q[j] != 0) deadm[j] |= (uint32_t)(st.er[e[j]].seq == 0);
+        }
       }
     }
-  }
 #pragma unroll
-  for (int j = 0; j < kWinPer; ++j) {
-    const uint32_t i = own + (uint32_t)j * kGreedyThreads;
-    const bool was = (i < n) & (q[j] != 0);
-    const bool live = was & (deadm[j] == 0u);
-    if (was & !live) w.seq[i] = 0;
-    Key c; c.sal = live ? sl[j] : -__builtin_inf(); c.seq = live ? q[j] : 0ull; c.arg = i;
-    const bool b1 = better(c, k1), b2 = better(c, k2);
-    // new best: the old best becomes second; else new second if it beats the old second (field by field: selecting whole
-    // structs goes through private memory)
-    k2.sal = b1 ? k1.sal : (b2 ? c.sal : k2.sal); k2.seq = b1 ? k1.seq : (b2 ? c.seq : k2.seq); k2.arg = b1 ? k1.arg : (b2 ? c.arg : k2.arg);
-    k1.sal = b1 ? c.sal : k1.sal; k1.seq = b1 ? c.seq : k1.seq; k1.arg = b1 ? c.arg : k1.arg;
-  }
+    for (int j = 0; j < NB; ++j) {
+      const uint32_t i = own + (uint32_t)j * kGreedyThreads;
+      const bool was = (i < n) & (q[j] != 0);
+      const bool live = was & (deadm[j] == 0u);
+      if (was & !live) w.seq[i] = 0;
+      Key c; c.sal = live ? sl[j] : -__builtin_inf(); c.seq = live ? q[j] : 0ull; c.arg = i;
+      const bool b1 = better(c, k1), b2 = better(c, k2);
+      // new best: the old best becomes second; else new second if it beats the old second (field by field: selecting whole
+      // structs goes through private memory)
+      k2.sal = b1 ? k1.sal : (b2 ? c.sal : k2.sal); k2.seq = b1 ? k1.seq : (b2 ? c.seq : k2.seq); k2.arg = b1 ? k1.arg : (b2 ? c.arg : k2.arg);
+      k1.sal = b1 ? c.sal : k1.sal; k1.seq = b1 ? c.seq : k1.seq; k1.arg = b1 ? c.arg : k1.arg;
+    }
+  };
+  static_assert(kWinPer == 3, "batch_scan: one pass instance per number of blocks");
+  const uint32_t nu = (uint32_t)__builtin_amdgcn_readfirstlane((int)n);
+  if (nu > 2u * kGreedyThreads) pass(std::integral_constant<int, 3>{});
+  else if (nu > kGreedyThreads) pass(std::integral_constant<int, 2>{});
+  else pass(std::integral_constant<int, 1>{});
   SCAN_T(1);
-  const Key m1 = wave_max_sal_first(k1);
-  SCAN_T(2);
-  const bool mine = (k1.seq == m1.seq) & (k1.arg == m1.arg) & (m1.seq != 0);
-  Key kk; kk.sal = mine ? k2.sal : k1.sal; kk.seq = mine ? k2.seq : k1.seq; kk.arg = mine ? k2.arg : k1.arg;
-  const Key m2 = wave_max_sal_first(kk);
-  SCAN_T(3);
+  // The wave's best and second-best in ONE reduction: a butterfly over the (best, second) pair of saliency images per lane
+  // (wave_top2_ord), then a ballot for each of the two: a saliency that only one candidate holds names the winner's lane, whose
+  // key (seq, arg) is fetched with v_readlane.  Candidates for the second place: every lane's best but the winner's, and the
+  // winner's second.  A saliency several live candidates share (exact ties: common, the saliencies are means of 8-bit
+  // values) is decided by seq in one more reduction (uniform branches).  Live items have distinct seqs; empty keys (seq 0)
+  // are all (-inf, 0, 0): any of them is the answer.
+  const int lane = tid & 63;
+  const unsigned long long o1 = f64_ord(k1.sal), o2 = f64_ord(k2.sal);
+  unsigned long long M1 = o1, M2 = o2;
+  wave_top2_ord(M1, M2);
+  const unsigned long long t1 = __ballot(o1 == M1), t1l = __ballot((o1 == M1) & (k1.seq != 0ull));
+  const int l1 = (int)__builtin_ctzll(t1);                               // (some lane holds the maximum)
+  const bool win1 = lane == l1;
+  Key kk; kk.sal = win1 ? k2.sal : k1.sal; kk.seq = win1 ? k2.seq : k1.seq; kk.arg = win1 ? k2.arg : k1.arg;
+  const unsigned long long oc = win1 ? o2 : o1;
+  const unsigned long long t2 = __ballot(oc == M2), t2l = __ballot((oc == M2) & (kk.seq != 0ull));
+  Key m1, m2;
+  if (__popcll(t1) == 1 || t1l == 0ull) {                                // (uniform) one lane holds the largest saliency, or no lane a live item
+    m1 = win_lane_key(k1, l1);
+    int src = (int)__builtin_ctzll(t2);
+    if (__popcll(t2) != 1 && t2l != 0ull) {                              // (uniform) live candidates share the second saliency: the largest seq
+#ifdef GLIA_HMT_PROFILE
+      if (tid == 0) g_scanprof[5] += 1;
+#endif
+      const unsigned long long ms = wave_max_u64(oc == M2 ? kk.seq : 0ull);
+      src = (int)__builtin_ctzll(__ballot((oc == M2) & (kk.seq == ms)));
+    }
+    m2 = win_lane_key(kk, src);
+    SCAN_T(2);
+  } else {
+    // (uniform) several live bests share the largest saliency, so the second place has it too: the two largest seqs among the
+    // items of that saliency decide both (a lane's best has the larger seq of its two when they tie: s1 >= s2 holds)
+#ifdef GLIA_HMT_PROFILE
+    if (tid == 0) g_scanprof[6] += 1;
+#endif
+    unsigned long long S1 = o1 == M1 ? k1.seq : 0ull, S2 = o2 == M1 ? k2.seq : 0ull;
+    wave_top2_ord(S1, S2);
+    const int w1 = (int)__builtin_ctzll(__ballot((o1 == M1) & (k1.seq == S1)));
+    const bool winr = lane == w1;
+    Key kc; kc.sal = winr ? k2.sal : k1.sal; kc.seq = winr ? k2.seq : k1.seq; kc.arg = winr ? k2.arg : k1.arg;
+    const unsigned long long occ = winr ? o2 : o1;
+    m1 = win_lane_key(k1, w1);
+    m2 = win_lane_key(kc, (int)__builtin_ctzll(__ballot((occ == M1) & (kc.seq == S2))));
+    SCAN_T(3);
+  }
   if ((tid & 63) == 0) { b.part1[tid >> 6] = m1; b.part2[tid >> 6] = m2; }
   full_barrier();                  // ... and are performed here, before the next round loads the lists they rewrote
   SCAN_T(4);
@@ -1500,9 +1581,12 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_batch_kernel(WinState s
 #ifdef GLIA_HMT_PROFILE
   unsigned long long bph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, blast = __builtin_readcyclecounter(), brounds = 0, bmembers = 0, bvalid = 0, bwide = 0, bcut_sal = 0, bcut_dep = 0;
   unsigned long long bw_n[4] = {0, 0, 0, 0}, bw_cyc[4] = {0, 0, 0, 0}, bw_ent[4] = {0, 0, 0, 0}, bw_new[4] = {0, 0, 0, 0};
+  unsigned long long bsel[2] = {0, 0}, bsel_n[2] = {0, 0};      // loop-top cycles (the select bucket, BPH(0)) of narrow rounds / wide pops, and their number
+#define BPH0(wide) do { if (tid == 0) { unsigned long long tn = __builtin_readcyclecounter(); bph[0] += tn - blast; bsel[wide] += tn - blast; bsel_n[wide] += 1; blast = tn; } } while (0)
 #define BPH(i) do { if (tid == 0) { unsigned long long tn = __builtin_readcyclecounter(); bph[i] += tn - blast; blast = tn; } } while (0)
 #else
 #define BPH(i) do {} while (0)
+#define BPH0(wide) do {} while (0)
 #endif
 
   for (unsigned long long it = 0; it < st.max_iters; ++it) {
@@ -1528,7 +1612,7 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_batch_kernel(WinState s
       if (r == 1) { status = ST_DONE; break; }
       if (r == 2) { status = ST_NEED_TREE; break; }
       if (r == 3) { status = ST_REBASE; break; }                          // the queue continues below the horizon: new baseline
-      batch_scan(st, w, b, tid);
+      batch_scan(st, w, b, tid, kScanOther);
       continue;
     }
     // the candidate this wave is responsible for: the one of rank `wave`
@@ -1548,7 +1632,7 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_batch_kernel(WinState s
     const Key top = b.part1[__builtin_ctzll(firstmask)];
     const uint2 th0 = w.hu[top.arg], th1 = w.hv[top.arg];
     const uint32_t top_total = th0.y + th1.y;
-    BPH(0);
+    BPH0(top_total > kMemMax ? 1 : 0);
     if (top_total > kMemMax) {
       if (ne + top_total > st.Ecap) { status = ST_NEED_EDGES; break; }
       if (pool_used + top_total > st.pool_cap) { status = ST_NEED_POOL; break; }
@@ -1563,8 +1647,8 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_batch_kernel(WinState s
       bwide += 1;
       { const int cls = tt <= 512u ? 0 : tt <= kMarkMax ? 1 : tt <= 8192u ? 2 : 3; bw_n[cls] += 1; bw_cyc[cls] += __builtin_readcyclecounter() - tw0; bw_ent[cls] += tt; bw_new[cls] += newcount; }
 #endif
-      batch_scan(st, w, b, tid);
-      if (w.spill_ord) { if (pend_e != kNone) { st.er[pend_e].next = pend_old; pend_e = kNone; } win_evict(st, w, tid); batch_scan(st, w, b, tid); }
+      batch_scan(st, w, b, tid, kScanWide);
+      if (w.spill_ord) { if (pend_e != kNone) { st.er[pend_e].next = pend_old; pend_e = kNone; } win_evict(st, w, tid); batch_scan(st, w, b, tid, kScanOther); }
       BPH(4);
       continue;
     }
@@ -1757,15 +1841,18 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_batch_kernel(WinState s
     brounds += 1; bmembers += M; bvalid += V;
 #endif
     k += V; ne += ne_off; pool_used += pool_off;
-    batch_scan(st, w, b, tid);
-    if (w.spill_ord) { if (pend_e != kNone) { st.er[pend_e].next = pend_old; pend_e = kNone; } win_evict(st, w, tid); batch_scan(st, w, b, tid); }
+    batch_scan(st, w, b, tid, kScanNarrow);
+    if (w.spill_ord) { if (pend_e != kNone) { st.er[pend_e].next = pend_old; pend_e = kNone; } win_evict(st, w, tid); batch_scan(st, w, b, tid, kScanOther); }
     BPH(4);
   }
 #ifdef GLIA_HMT_PROFILE
   if (tid == 0) printf("[batch profile] merges %llu: select %llu  compute %llu  validate %llu  commit %llu  scan %llu  loop-top %llu  reload %llu (cycles); rounds %llu candidates %llu committed %llu (cut by saliency %llu, by adjacency %llu) wide %llu\n",
                        k, bph[0], bph[1], bph[2], bph[3], bph[4], bph[5], bph[6], brounds, bmembers, bvalid, bcut_sal, bcut_dep, bwide);
-  if (tid == 0) printf("[batch profile] scan phases (cumulative cycles, wave 0): loads %llu  compare %llu  max1 %llu  max2 %llu  barrier %llu  calls %llu\n",
-                       g_scanprof[0], g_scanprof[1], g_scanprof[2], g_scanprof[3], g_scanprof[4], g_scanprof[7]);
+  if (tid == 0) printf("[batch profile] scan phases (cumulative cycles, wave 0): loads %llu  compare %llu  top2 %llu  top2 with a tied best %llu  barrier %llu  calls %llu  tied second %llu  tied best %llu\n",
+                       g_scanprof[0], g_scanprof[1], g_scanprof[2], g_scanprof[3], g_scanprof[4], g_scanprof[7], g_scanprof[5], g_scanprof[6]);
+  if (tid == 0) printf("[batch profile] scan fill (cumulative; n <= 512, <= 1024, more): after reload/evict %llu %llu %llu  after narrow round %llu %llu %llu  after wide %llu %llu %llu\n",
+                       g_scanfill[0][0], g_scanfill[0][1], g_scanfill[0][2], g_scanfill[1][0], g_scanfill[1][1], g_scanfill[1][2], g_scanfill[2][0], g_scanfill[2][1], g_scanfill[2][2]);
+  if (tid == 0) printf("[batch profile] loop top (this launch): narrow rounds %llu cycles %llu  wide pops %llu cycles %llu\n", bsel_n[0], bsel[0], bsel_n[1], bsel[1]);
   if (tid == 0) printf("[batch profile] wide phases (cumulative cycles): entry-barrier %llu  lists+table %llu  compact %llu  main loop (wave 0) %llu  loop barrier %llu  tail %llu\n",
                        g_wideprof[0], g_wideprof[1], g_wideprof[2], g_wideprof[3], g_wideprof[4], g_wideprof[5]);
   if (tid == 0) printf("[batch profile] wide by entries (<=512, <=1408, <=8192, more): n %llu %llu %llu %llu  cycles %llu %llu %llu %llu  entries %llu %llu %llu %llu  new edges %llu %llu %llu %llu\n",
