@@ -2,6 +2,7 @@
 // operators each entry point replaces).
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1237,6 +1238,73 @@ int glia_hmt_score_initial_edges_shard(glia_hmt_ctx* c, glia_hmt_rag* rag, const
     if (res.n > capacity) { set_error("score_initial_edges_shard: output capacity too small"); return GLIA_HMT_ERR_CAPACITY; }
     std::copy(res.sal.begin(), res.sal.begin() + res.n, h_scores);
   }
+  return GLIA_HMT_OK;
+}
+
+// hmt/main_bc_label_ri.cxx:27-153 (F1 / RI, --optSplit, --opt) and hmt/main_bc_label_vi.cxx:27-128 (VI, majority over truths, --opt):
+// one counting pass per truth volume on the device (truth_overlap.hip), per-node values and the label rules on the host (bc_label.cpp)
+int glia_hmt_bc_label(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t* const* d_truth, int n_truth, const uint32_t* h_order,
+                      int64_t n_merges, const glia_hmt_bc_label_opts* opts, int32_t* h_labels) {
+  glia_hmt_bc_label_opts o = {GLIA_HMT_BC_LABEL_F1, 0, 1.0, 0, 0};         // the tools' defaults (main_bc_label_ri.cxx:19-23)
+  if (opts) o = *opts;
+  if (!c || !rag || rag->ctx != c || !d_truth || n_truth < 1 || n_merges < 0 || (n_merges && (!h_order || !h_labels))) {
+    set_error("bc_label: invalid argument");
+    return GLIA_HMT_ERR_ARG;
+  }
+  for (int t = 0; t < n_truth; ++t) if (!d_truth[t]) { set_error("bc_label: null truth volume"); return GLIA_HMT_ERR_ARG; }
+  if (o.metric < GLIA_HMT_BC_LABEL_F1 || o.metric > GLIA_HMT_BC_LABEL_VI) { set_error("bc_label: unknown metric"); return GLIA_HMT_ERR_ARG; }
+  if (o.global_opt < 0 || o.global_opt > 2) { set_error("Error: unsupported globalOpt type..."); return GLIA_HMT_ERR_ARG; }   // :147
+  if (n_truth > 1 && o.metric != GLIA_HMT_BC_LABEL_VI) { set_error("bc_label: several truth volumes need the VI metric (bc_label_vi)"); return GLIA_HMT_ERR_ARG; }
+  if (o.metric == GLIA_HMT_BC_LABEL_VI && (o.tweak || o.opt_split || o.max_prec_drop < 1.0)) {
+    set_error("bc_label: tweak, mpd and optSplit are options of bc_label_ri, not of bc_label_vi");
+    return GLIA_HMT_ERR_ARG;
+  }
+  if (rag->only_contour) { set_error("bc_label: the region map must hold region points (only_contour = 0)"); return GLIA_HMT_ERR_ARG; }
+  if (!rag->vol.lab) { set_error("bc_label: needs the volumes the region map was built from (whole-volume build)"); return GLIA_HMT_ERR_UNSUPPORTED; }
+  const int64_t R = rag->arr.R;
+  if (n_merges && n_merges >= R) { set_error("bc_label: more merges than regions"); return GLIA_HMT_ERR_ARG; }
+  // keys -> dense ids, validated as bc_feat does
+  std::vector<uint32_t> lab((size_t)R);
+  if (R) GLIA_HIP_TRY(hipMemcpy(lab.data(), rag->arr.d_rlabel, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
+  std::unordered_map<uint32_t, uint32_t> id;
+  id.reserve((size_t)R * 2);
+  for (int64_t i = 0; i < R; ++i) id[lab[i]] = (uint32_t)i;
+  std::vector<uint32_t> forced((size_t)2 * n_merges);
+  std::vector<uint8_t> used((size_t)R + n_merges, 0);
+  for (int64_t i = 0; i < n_merges; ++i) {
+    for (int s2 = 0; s2 < 2; ++s2) {
+      auto it = id.find(h_order[3 * i + s2]);
+      if (it == id.end() || used[it->second]) { set_error("bc_label: merge order refers to an unknown or already merged region"); return GLIA_HMT_ERR_ARG; }
+      used[it->second] = 1;
+      forced[2 * i + s2] = it->second;
+    }
+    if (id.count(h_order[3 * i + 2])) { set_error("bc_label: merge order reuses a region key"); return GLIA_HMT_ERR_ARG; }
+    id[h_order[3 * i + 2]] = (uint32_t)(R + i);
+  }
+  rag->bcl = glia_hmt_bc_label_timing{0, 0, 0, 0, 0, 0};
+  if (n_merges == 0) return GLIA_HMT_OK;
+  GLIA_HIP_TRY(hipSetDevice(c->device));
+  std::vector<NodeTruthStats> st((size_t)n_truth);
+  for (int t = 0; t < n_truth; ++t) {
+    std::vector<TruthCount> cnt;
+    float ms = 0;
+    if (int rc = truth_overlap(rag->vol, rag->arr.d_rlabel, (uint32_t)R, d_truth[t], c->stream, &cnt, &ms)) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    int64_t moves = 0, pairs = 0;
+    node_truth_stats(cnt, (uint32_t)R, forced.data(), n_merges, &st[t], &moves, &pairs);
+    rag->bcl.ms_count += ms;
+    rag->bcl.ms_nodes += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    rag->bcl.entries += (int64_t)cnt.size(); rag->bcl.moves += moves; rag->bcl.node_pairs += pairs;
+  }
+  const auto t1 = std::chrono::steady_clock::now();
+  int rc = bc_label_rules(st, (uint32_t)R, forced.data(), n_merges, o, h_labels);
+  rag->bcl.ms_rules = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+  return rc;
+}
+
+int glia_hmt_last_bc_label_timing(const glia_hmt_rag* r, glia_hmt_bc_label_timing* out) {
+  if (!r || !out) return GLIA_HMT_ERR_ARG;
+  *out = r->bcl;
   return GLIA_HMT_OK;
 }
 

@@ -131,6 +131,20 @@ struct MedianFeatIn {
   const uint32_t* forced; int64_t n_merges;
 };
 int median_feature_stats(const MedianFeatIn& in, hipStream_t stream, std::vector<double>* reg, std::vector<double>* bnd, std::vector<unsigned long long>* area);
+// bc_label (truth_overlap.hip, bc_label.cpp): the voxels of dense leaf `leaf` with truth label `truth` (0 included), sorted by
+// (leaf, truth); *ms = device time of the counting pass
+struct TruthCount { uint32_t leaf, truth; unsigned long long count; };
+int truth_overlap(const VolumeRef& vol, const uint32_t* d_rlabel, uint32_t R, const uint32_t* d_truth, hipStream_t stream,
+                  std::vector<TruthCount>* out, float* ms);
+// per tree node (leaves 0 .. R-1, merge k = R + k) and one truth volume: n = voxels with truth != 0, size = all voxels,
+// Q = sum_t c_t^2, E = sum_t c_t log2 c_t (t != 0); *moves = map entries moved by the small-to-large merging, *node_pairs = the
+// (node, truth) pairs of the tree (what a walk that visits each of them once would do)
+struct NodeTruthStats { std::vector<unsigned long long> n, size, Q; std::vector<long double> E; };
+void node_truth_stats(const std::vector<TruthCount>& cnt, uint32_t R, const uint32_t* forced, int64_t M, NodeTruthStats* out, int64_t* moves,
+                      int64_t* node_pairs);
+// the labels of main_bc_label_ri / _vi from the per-node values of every truth volume (options already validated)
+int bc_label_rules(const std::vector<NodeTruthStats>& st, uint32_t R, const uint32_t* forced, int64_t M, const glia_hmt_bc_label_opts& o,
+                   int32_t* labels);
 // What a merge loop returns: the order in dense ids (leaf i = i-th label ascending, merged region R + k) -- [n][3] -- with the
 // saliencies, optionally the feature row of every merge, the edges scored, and the times of the table, the initial scores and
 // the loop.

@@ -467,6 +467,15 @@ def build_distributed(ctx, comm, slabs, nz_global, only_contour=False, loop_owne
     return rm, st
 
 
+class BcLabelOpts(C.Structure):
+    _fields_ = [("metric", C.c_int), ("tweak", C.c_int), ("max_prec_drop", C.c_double), ("opt_split", C.c_int), ("global_opt", C.c_int)]
+
+
+class BcLabelTiming(C.Structure):
+    _fields_ = [("ms_count", C.c_double), ("ms_nodes", C.c_double), ("ms_rules", C.c_double), ("entries", C.c_int64),
+                ("moves", C.c_int64), ("node_pairs", C.c_int64)]
+
+
 class RegionMap:
     """Device-resident region adjacency structure with sufficient statistics.
     Mirrors TRegionMap(image, mask, onlyContour) (type/region_map.hxx:38-40)."""
@@ -648,6 +657,31 @@ class RegionMap:
         _check(lib().glia_hmt_bc_feat_saliency(self.ctx.h, self.h, _np(order), C.c_int64(len(order)), _np(sal),
                                                C.c_double(init_sal), C.c_double(sal_bias), _np(feats)))
         return feats
+
+    BC_METRICS = {"f1": 0, "ri": 1, "vi": 2}
+
+    def bc_label(self, truths, order, metric="f1", tweak=False, mpd=1.0, opt_split=False, opt=0):
+        """hmt/main_bc_label_ri.cxx (metric "f1" / "ri": --f1, --tweak, --mpd, --optSplit, --opt) and main_bc_label_vi.cxx
+        (metric "vi", one or more truths: --opt): int32 label per merge, -1 merge / +1 split.  truths: one CUDA u32 tensor of the
+        map's shape or a list of them; the map needs only_contour=False and its mask is the tools' -n / -m."""
+        if not isinstance(truths, (list, tuple)):
+            truths = [truths]
+        for t in truths:
+            assert t.is_cuda and t.is_contiguous() and t.element_size() == 4
+            _fence(t)
+        order = np.ascontiguousarray(order, dtype=np.uint32).reshape(-1, 3)
+        ptrs = (C.c_void_p * max(len(truths), 1))(*[t.data_ptr() for t in truths])
+        opts = BcLabelOpts(self.BC_METRICS[metric], int(bool(tweak)), float(mpd), int(bool(opt_split)), int(opt))
+        out = np.empty(max(len(order), 1), np.int32)
+        _check(lib().glia_hmt_bc_label(self.ctx.h, self.h, ptrs, C.c_int(len(truths)), _np(order), C.c_int64(len(order)),
+                                       C.byref(opts), _np(out)))
+        return out[:len(order)].copy()
+
+    def last_bc_label_timing(self):
+        """stages of the last bc_label call: ms_count (device), ms_nodes, ms_rules (host), entries, moves, node_pairs"""
+        t = BcLabelTiming()
+        _check(lib().glia_hmt_last_bc_label_timing(self.h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in BcLabelTiming._fields_}
 
     def score_initial_edges(self, classifier):
         n, ms = C.c_int64(0), C.c_double(0)

@@ -294,6 +294,40 @@ int glia_hmt_bc_feat_saliency(glia_hmt_ctx* ctx, glia_hmt_rag* rag, const uint32
                               const double* h_saliencies, double init_saliency, double saliency_bias, double* h_feats);
 int glia_hmt_bc_feat_dim(const glia_hmt_rag* rag, int with_saliency);
 
+/* Replaces hmt/main_bc_label_ri.cxx:27-153 and hmt/main_bc_label_vi.cxx:27-128 for a GIVEN merge order: the label of every merge,
+ * GLIA_HMT_BC_MERGE (-1) or GLIA_HMT_BC_SPLIT (+1), decided against truth volumes (genBoundaryClassificationLabelF1 / RI / VI,
+ * hmt/bc_label.hxx:16-109; stats::pairStats / pairF1 / randIndex / vi, util/image_stats.hxx:69-110,173-245, util/stats.hxx:189-261;
+ * truth label 0 excluded).  The region sets are those of RegionMap(seg, mask, order, false): the map must be a whole-volume build
+ * with only_contour = 0 (else GLIA_HMT_ERR_UNSUPPORTED / GLIA_HMT_ERR_ARG); the mask given to the build is the tools' -n / -m.
+ * d_truth: n_truth device volumes of the map's shape (u32); several only for GLIA_HMT_BC_LABEL_VI (majority, util/container.hxx:356).
+ * h_order: n_merges triples validated as glia_hmt_bc_feat does; h_labels: [n_merges], row i = merge i (with global_opt: the inner
+ * nodes of genTree, which are the merges in order).  opts NULL = the tools' defaults.  Labels are exact; the F1 / RI values behind
+ * them are too up to counts beyond 2^53 (converted to double rounded to nearest; the reference's int512_t conversion is not pinned),
+ * VI values are sums in another order than the reference's hash order. */
+enum { GLIA_HMT_BC_LABEL_F1 = 0, GLIA_HMT_BC_LABEL_RI = 1, GLIA_HMT_BC_LABEL_VI = 2 };
+#define GLIA_HMT_BC_MERGE (-1)
+#define GLIA_HMT_BC_SPLIT 1
+typedef struct {
+  int metric;              /* GLIA_HMT_BC_LABEL_F1 (bc_label_ri, --f1 true), _RI (bc_label_ri --f1 false), _VI (bc_label_vi) */
+  int tweak;               /* bc_label_ri --tweak (-w): F1 only */
+  double max_prec_drop;    /* bc_label_ri --mpd (-d), >= 1 disables: F1 only */
+  int opt_split;           /* bc_label_ri --optSplit (-p): F1 only (ignored with RI, as by the reference) */
+  int global_opt;          /* --opt (-g): 0 none, 1 path consistency by merging, 2 by splitting; with 1 / 2 the RI tool compares
+                              pair F1 whatever the metric (main_bc_label_ri.cxx:121-124) and ignores tweak / mpd / optSplit */
+} glia_hmt_bc_label_opts;
+int glia_hmt_bc_label(glia_hmt_ctx* ctx, glia_hmt_rag* rag, const uint32_t* const* d_truth, int n_truth, const uint32_t* h_order,
+                      int64_t n_merges, const glia_hmt_bc_label_opts* opts, int32_t* h_labels);
+/* the stages of the last glia_hmt_bc_label call on this map */
+typedef struct {
+  double ms_count;         /* device time of the counting pass(es), all truth volumes (truth_overlap.hip) */
+  double ms_nodes;         /* host: per-node values (small-to-large merging) */
+  double ms_rules;         /* host: the label rules */
+  int64_t entries;         /* (leaf, truth) entries of the contingency tables, truth 0 included */
+  int64_t moves;           /* map entries moved by the small-to-large merging */
+  int64_t node_pairs;      /* (tree node, truth != 0) pairs: the visits of a per-node walk */
+} glia_hmt_bc_label_timing;
+int glia_hmt_last_bc_label_timing(const glia_hmt_rag* rag, glia_hmt_bc_label_timing* out);
+
 /* ---- the step after the merge path: tree resolution (hmt/main_segment_greedy.cxx:33-86), host-only ----
  * glia_hmt_tree_potentials = genTree / genTreeWithNodePotentials (hmt/tree_build.hxx:12-63): array tree of the merge
  * order plus a potential per node -- merge probability of the node, times (1 - p) of its parent; leaves: (1 - p_parent)^2;
