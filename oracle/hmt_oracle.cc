@@ -912,30 +912,48 @@ void orc_rag_region_stats(const orc_rag* h, const float* img, double* sum, doubl
 
 // Dump the leaf maps + pb in the text format oracle/ref_engine_driver.cc reads, so that the
 // reference's own engine headers can be run on exactly this RAG (tests/test_oracle_vs_ref.py).
-int orc_rag_dump(const orc_rag* h, const float* pb, int type, int update_region, const char* path) {
+// compact != 0: only voxels that occur in a point, border or boundary list get an id (dense, in raster order, so every comparison of
+// two ids comes out as before) and a pb value; the engine reads pb[id] and nothing else of a voxel, so its output is the same bytes.
+int orc_rag_dump2(const orc_rag* h, const float* pb, int type, int update_region, const char* path, int compact) {
   FILE* f = fopen(path, "w");
   if (!f) return -1;
   auto const& rm = h->rmap;
-  fprintf(f, "%lld %zu %zu %zu %d %d\n", (long long)h->vol.size(), rm.pPointMap->size(), rm.pBorderMap->size(),
+  const int64_t N = h->vol.size();
+  std::vector<int64_t> id;
+  int64_t used = N;
+  if (compact) {
+    id.assign(N, 0);
+    for (auto const& pp : *rm.pPointMap) for (auto p : pp.second) id[p] = 1;
+    for (auto const& pp : *rm.pBorderMap) for (auto p : pp.second) id[p] = 1;
+    for (auto const& pp : *rm.pBoundaryMap) for (auto p : pp.second) id[p] = 1;
+    used = 0;
+    for (int64_t i = 0; i < N; ++i) id[i] = id[i] ? used++ : -1;
+  }
+  auto put = [&](int64_t p) { fprintf(f, " %lld", (long long)(compact ? id[p] : p)); };
+  fprintf(f, "%lld %zu %zu %zu %d %d\n", (long long)used, rm.pPointMap->size(), rm.pBorderMap->size(),
           rm.pBoundaryMap->size(), type, update_region);
   for (auto const& pp : *rm.pPointMap) {
     fprintf(f, "%u %zu", pp.first, pp.second.size());
-    for (auto p : pp.second) fprintf(f, " %lld", (long long)p);
+    for (auto p : pp.second) put(p);
     fprintf(f, "\n");
   }
   for (auto const& pp : *rm.pBorderMap) {
     fprintf(f, "%u %zu", pp.first, pp.second.size());
-    for (auto p : pp.second) fprintf(f, " %lld", (long long)p);
+    for (auto p : pp.second) put(p);
     fprintf(f, "\n");
   }
   for (auto const& pp : *rm.pBoundaryMap) {
     fprintf(f, "%u %u %zu", pp.first.first, pp.first.second, pp.second.size());
-    for (auto p : pp.second) fprintf(f, " %lld", (long long)p);
+    for (auto p : pp.second) put(p);
     fprintf(f, "\n");
   }
-  for (int64_t i = 0; i < h->vol.size(); ++i) fprintf(f, "%.9g\n", (double)pb[i]);
+  for (int64_t i = 0; i < N; ++i) if (!compact || id[i] >= 0) fprintf(f, "%.9g\n", (double)pb[i]);
   fclose(f);
   return 0;
+}
+
+int orc_rag_dump(const orc_rag* h, const float* pb, int type, int update_region, const char* path) {
+  return orc_rag_dump2(h, pb, type, update_region, path, 0);
 }
 
 static int64_t emit(std::vector<Triple> const& order, std::vector<double> const& sal, orc_label* o, double* s,

@@ -105,6 +105,8 @@ void orc_rag_region_stats(const orc_rag*, const float* img, double* sum, double*
 
 // text dump consumed by oracle/_ref/ref_engine (the reference's own engine headers built in place)
 int orc_rag_dump(const orc_rag*, const float* pb, int type, int update_region, const char* path);
+// the same with compact != 0: voxels that no list mentions get neither an id nor a pb line (ids renumbered densely)
+int orc_rag_dump2(const orc_rag*, const float* pb, int type, int update_region, const char* path, int compact);
 
 // ---- greedy merge orders ------------------------------------------------------------
 // type 1 = median, 2 = mean (hmt/main_merge_order_pb.cxx:10).  order: 3 labels per merge.

@@ -191,8 +191,9 @@ class Rag:
         lib().orc_rag_region_stats(self.h, _p(img), *[_p(o) for o in out], _p(lo), _p(hi))
         return out + [lo, hi]
 
-    def dump(self, pb, type, update_region, path):
-        rc = lib().orc_rag_dump(self.h, _p(pb), C.c_int(type), C.c_int(int(update_region)), path.encode())
+    def dump(self, pb, type, update_region, path, compact=False):
+        """text input of oracle/_ref/ref_engine; compact: only voxels that a point, border or boundary list names get an id and a pb value"""
+        rc = lib().orc_rag_dump2(self.h, _p(pb), C.c_int(type), C.c_int(int(update_region)), path.encode(), C.c_int(int(compact)))
         assert rc == 0
 
     def merge_order_pb(self, pb, type=1, update_region=False):

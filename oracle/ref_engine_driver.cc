@@ -20,7 +20,8 @@
 //         R lines:  label nPoints  p0 p1 ...          (voxel ids, raster order)
 //         P lines:  label nBorder  p0 p1 ...
 //         B lines:  a b n  p0 p1 ...                  (directed boundary voxel ids)
-//         then N pb values (N = number of voxels, first line gives N)
+//         then N pb values (N = number of voxels, first line gives N).  A voxel id is only ever an index into these values, so
+//         the compact dump (orc_rag_dump2: ids renumbered densely over the voxels some list names, N = their number) reads the same
 //         optionally:  nThresholds t0 [t1] rpbThreshold      (type 2 only: the pre_merge condition, updateRegion is forced on)
 // stdout: one "x0 x1 x2 saliency" line per merge (saliency printed with %.17g), then one "K src dst" line per entry of
 //         transformKeys(order), sorted by src
