@@ -142,9 +142,8 @@ __device__ __forceinline__ BcChan chan_of(const BcState& st, int c) {
 // stores the flag, and sc1 loads -- which bypass the reader's L1 -- for EVERY load of such bytes by the consumer
 // (cdna_hip_programming.md Guideline 16, form R1 with sc1 loads in place of the acquire).  A release / acquire fence pair at
 // agent scope would write back and invalidate whole caches at every hand-off (measured in round 1: -12 % loop time without).
-__device__ __forceinline__ uint32_t ld_relaxed(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_release(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+using glia::st_agent;        // (uint32_t*, greedy_common.hpp) next to the overloads below
 __device__ __forceinline__ void st_agent(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_agent(float* p, float v) { __hip_atomic_store(reinterpret_cast<uint32_t*>(p), __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_agent(uint8_t* p, uint8_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -1213,11 +1212,6 @@ __device__ __forceinline__ void top2_merge(unsigned long long& b, unsigned long 
   unsigned long long ns = s2 < os ? s2 : os;
   ns = mx < ns ? mx : ns;
   b = nb; s2 = ns;
-}
-template <int CTRL>
-__device__ __forceinline__ unsigned long long dpp64(unsigned long long v) {
-  const uint32_t lo = dpp_u32<CTRL, 0xf>((uint32_t)v), hi = dpp_u32<CTRL, 0xf>((uint32_t)(v >> 32));
-  return ((unsigned long long)hi << 32) | lo;
 }
 __device__ __forceinline__ unsigned long long xor64(unsigned long long v, int m) {
   const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);

@@ -41,22 +41,57 @@ __device__ __forceinline__ bool better(const Key& a, const Key& b) {
   return (a.sal > b.sal) | ((a.sal == b.sal) & (a.seq > b.seq));      // no short-circuit: three compares, no branches
 }
 
+// A barrier behind which every global store and atomic of the workgroup has been performed.  (__syncthreads() is NOT that on
+// gfx950: the workgroup-scope fence of a workgroup that is not split over CUs waits for lgkmcnt only -- found in round 3, when
+// a merge order differed once in ~30 000 runs; the comments of rounds 1-2 that say "vmcnt(0) inside" were wishful.)
+__device__ __forceinline__ void full_barrier(const int line = __builtin_LINE()) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); GLIA_SKEW_DELAY(line); }
+__device__ __forceinline__ void lds_barrier(const int line = __builtin_LINE()) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); GLIA_SKEW_DELAY(line); }   // global stores stay in flight
+
+// relaxed agent-scope accesses: the load bypasses the reader's L1, the store is written through to L2
+__device__ __forceinline__ uint32_t ld_relaxed(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_agent(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// order-preserving image of a double: ascending doubles <-> ascending unsigned integers
+__host__ __device__ __forceinline__ unsigned long long f64_ord(double d) {
+  unsigned long long b = __builtin_bit_cast(unsigned long long, d);
+  return b ^ ((b >> 63) ? ~0ull : 0x8000000000000000ull);
+}
+__host__ __device__ __forceinline__ double f64_unord(unsigned long long o) {
+  o ^= (o >> 63) ? 0x8000000000000000ull : ~0ull;
+  return __builtin_bit_cast(double, o);
+}
+
+// DPP moves.  ZERO_REST: the rows ROW_MASK leaves unwritten receive 0 instead of keeping the lane's own value.
+template <int CTRL, int ROW_MASK, bool ZERO_REST = false>
+__device__ __forceinline__ uint32_t dpp_u32(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(ZERO_REST ? 0 : (int)v, (int)v, CTRL, ROW_MASK, 0xf, false);
+}
+template <int CTRL, int ROW_MASK = 0xf, bool ZERO_REST = false>
+__device__ __forceinline__ unsigned long long dpp64(unsigned long long v) {
+  const uint32_t lo = dpp_u32<CTRL, ROW_MASK, ZERO_REST>((uint32_t)v), hi = dpp_u32<CTRL, ROW_MASK, ZERO_REST>((uint32_t)(v >> 32));
+  return ((unsigned long long)hi << 32) | lo;
+}
+// lane l's 64-bit value / key in every lane (l uniform): v_readlane per 32-bit half
+__device__ __forceinline__ unsigned long long lane_u64(unsigned long long v, int l) {
+  return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+}
+__device__ __forceinline__ Key lane_key(const Key& k, int l) {
+  Key out;
+  out.sal = __longlong_as_double((long long)lane_u64((unsigned long long)__double_as_longlong(k.sal), l));
+  out.seq = lane_u64(k.seq, l);
+  out.arg = (uint32_t)__builtin_amdgcn_readlane((int)k.arg, l);
+  return out;
+}
+
 // 64-lane maximum by (saliency, seq), returned to every lane.  Hand-written over DPP: a generic reduction of the 20-byte
 // key selects between two structs through private memory (a scratch round trip per step, ~4000 cycles per call);
 // here every step is five v_mov_dpp plus compares and selects on registers.  max is idempotent, so the lanes a
 // row_bcast step does not write (row_mask) simply combine with themselves.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_u32(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
 template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ void key_max_step(Key& k) {
-  const unsigned long long sb = (unsigned long long)__double_as_longlong(k.sal);
-  const uint32_t s_lo = dpp_u32<CTRL, ROW_MASK>((uint32_t)sb), s_hi = dpp_u32<CTRL, ROW_MASK>((uint32_t)(sb >> 32));
-  const uint32_t q_lo = dpp_u32<CTRL, ROW_MASK>((uint32_t)k.seq), q_hi = dpp_u32<CTRL, ROW_MASK>((uint32_t)(k.seq >> 32));
+  const double osal = __longlong_as_double((long long)dpp64<CTRL, ROW_MASK>((unsigned long long)__double_as_longlong(k.sal)));
+  const unsigned long long oseq = dpp64<CTRL, ROW_MASK>(k.seq);
   const uint32_t a = dpp_u32<CTRL, ROW_MASK>(k.arg);
-  const double osal = __longlong_as_double((long long)(((unsigned long long)s_hi << 32) | s_lo));
-  const unsigned long long oseq = ((unsigned long long)q_hi << 32) | q_lo;
   const bool b = (osal > k.sal) | ((osal == k.sal) & (oseq > k.seq));
   k.sal = b ? osal : k.sal;
   k.seq = b ? oseq : k.seq;
@@ -69,14 +104,7 @@ __device__ __forceinline__ Key wave_max(Key k) {
   key_max_step<0x128>(k);         // row_ror 8: every lane holds its row's maximum
   key_max_step<0x142, 0xa>(k);    // row_bcast 15 into rows 1 and 3
   key_max_step<0x143, 0xc>(k);    // row_bcast 31 into rows 2 and 3: lane 63 holds the wave's maximum
-  const unsigned long long sb = (unsigned long long)__double_as_longlong(k.sal);
-  const uint32_t s_lo = __builtin_amdgcn_readlane((int)(uint32_t)sb, 63), s_hi = __builtin_amdgcn_readlane((int)(uint32_t)(sb >> 32), 63);
-  const uint32_t q_lo = __builtin_amdgcn_readlane((int)(uint32_t)k.seq, 63), q_hi = __builtin_amdgcn_readlane((int)(uint32_t)(k.seq >> 32), 63);
-  Key out;
-  out.sal = __longlong_as_double((long long)(((unsigned long long)s_hi << 32) | s_lo));
-  out.seq = ((unsigned long long)q_hi << 32) | q_lo;
-  out.arg = (uint32_t)__builtin_amdgcn_readlane((int)k.arg, 63);
-  return out;
+  return lane_key(k, 63);
 }
 
 // The same maximum, cheaper when saliency ties inside a wave are uncommon: reduce the order-preserving integer image of the
@@ -85,8 +113,7 @@ __device__ __forceinline__ Key wave_max(Key k) {
 // second reduction over their seq decides.  Same result as wave_max for keys whose (sal, seq) pairs are distinct or empty.
 template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ void u64_max_step(unsigned long long& v) {
-  const uint32_t lo = dpp_u32<CTRL, ROW_MASK>((uint32_t)v), hi = dpp_u32<CTRL, ROW_MASK>((uint32_t)(v >> 32));
-  const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+  const unsigned long long o = dpp64<CTRL, ROW_MASK>(v);
   v = o > v ? o : v;
 }
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
@@ -96,27 +123,17 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
   u64_max_step<0x128>(v);
   u64_max_step<0x142, 0xa>(v);
   u64_max_step<0x143, 0xc>(v);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
-  return ((unsigned long long)hi << 32) | lo;
+  return lane_u64(v, 63);
 }
 __device__ __forceinline__ Key wave_max_sal_first(const Key& k) {
-  unsigned long long ord = (unsigned long long)__double_as_longlong(k.sal);
-  ord ^= (ord >> 63) ? ~0ull : 0x8000000000000000ull;                   // ascending doubles <-> ascending integers
+  const unsigned long long ord = f64_ord(k.sal);
   const unsigned long long m = wave_max_u64(ord);
   unsigned long long tied = __ballot(ord == m);
   if (__popcll(tied) > 1) {                                              // (uniform) equal saliencies: the largest seq among them
     const unsigned long long ms = wave_max_u64(ord == m ? k.seq : 0ull);
     tied = __ballot((ord == m) & (k.seq == ms));
   }
-  const int src = (int)__builtin_ctzll(tied);                            // (at least one lane holds the maximum)
-  const unsigned long long sb = (unsigned long long)__double_as_longlong(k.sal);
-  Key out;
-  const uint32_t s_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)sb, src), s_hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(sb >> 32), src);
-  const uint32_t q_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)k.seq, src), q_hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(k.seq >> 32), src);
-  out.sal = __longlong_as_double((long long)(((unsigned long long)s_hi << 32) | s_lo));
-  out.seq = ((unsigned long long)q_hi << 32) | q_lo;
-  out.arg = (uint32_t)__builtin_amdgcn_readlane((int)k.arg, src);
-  return out;
+  return lane_key(k, (int)__builtin_ctzll(tied));                        // (at least one lane holds the maximum)
 }
 
 
@@ -268,8 +285,8 @@ __device__ __forceinline__ void pq_top(const PqTree& t, PqWork& w, int tid, cons
 #ifdef GLIA_HMT_PROFILE
   const unsigned long long tt2 = __builtin_readcyclecounter();
 #endif
-  if ((tid & 63) == 0) w.part[tid >> 6] = k;
-  __syncthreads();
+  if ((tid & 63) == 0) w.part[tid >> 6] = k;   // [W:part]
+  __syncthreads();   // [B:top]
 #ifdef GLIA_HMT_PROFILE
   if (tid == 0) { g_pqprof[24] += tt1 - tt0; g_pqprof[25] += tt2 - tt1; g_pqprof[26] += __builtin_readcyclecounter() - tt2; g_pqprof[27] += 1; }
 #endif
@@ -300,11 +317,11 @@ __device__ __forceinline__ void pq_propagate(const PqTree& t, PqWork& w, int tid
   const int lane = tid & 63, wave = tid >> 6;
   constexpr int nwaves = THREADS / 64;
   static_assert(nwaves <= 16, "PqWork::fast");
-  __syncthreads();
+  __syncthreads();   // [B:prop-enter]
 #ifdef GLIA_HMT_PROFILE
   if (tid == 0) { const uint32_t nd = w.wln[0]; g_pqprof[28 + (nd <= (uint32_t)nwaves ? 0 : (nd <= 2u * nwaves ? 1 : 2))] += 1; }
 #endif
-  if (w.wln[0] <= (uint32_t)nwaves && !w.spill && !w.ovf) {
+  if (w.wln[0] <= (uint32_t)nwaves && !w.spill && !w.ovf) {   // [R:prop-mode]
     // The usual case -- at most one dirty node per wave: every wave walks its node up the tree, one barrier per
     // level; waves whose node did not change, or whose parent is taken by a lower wave, drop out.
     const uint32_t n0 = w.wln[0];
@@ -323,12 +340,12 @@ __device__ __forceinline__ void pq_propagate(const PqTree& t, PqWork& w, int tid
 #ifdef GLIA_HMT_PROFILE
       const unsigned long long tf1 = __builtin_readcyclecounter();
 #endif
-      if (lane == 0) w.fast[l & 1][wave] = parent;
-      __syncthreads();
+      if (lane == 0) w.fast[l & 1][wave] = parent;   // [W:fast]
+      __syncthreads();   // [B:fast-level]
 #ifdef GLIA_HMT_PROFILE
       if (tid == 0) { g_pqprof[l] += tf1 - tf0; g_pqprof[8 + l] += __builtin_readcyclecounter() - tf1; g_pqprof[16 + l] += (node != kNone); }
 #endif
-      if (parent != kNone) for (int j = 0; j < wave; ++j) if (w.fast[l & 1][j] == parent) { parent = kNone; break; }
+      if (parent != kNone) for (int j = 0; j < wave; ++j) if (w.fast[l & 1][j] == parent) { parent = kNone; break; }   // [R:fast]
       node = parent;
     }
     if (node0 != kNone && lane == 0) {      // consume the worklist entry's membership slot (off the loads' critical path)
@@ -336,7 +353,7 @@ __device__ __forceinline__ void pq_propagate(const PqTree& t, PqWork& w, int tid
       while (w.set[0][h] != node0 + 1u) h = (h + 1) & (kSetSlots - 1);
       w.set[0][h] = 0;
     }
-    if (tid == 0) w.wln[0] = 0;
+    if (tid == 0) w.wln[0] = 0;   // [W:wln-fast]
     pq_top<THREADS>(t, w, tid, topk);
     return;
   }
@@ -345,9 +362,9 @@ __device__ __forceinline__ void pq_propagate(const PqTree& t, PqWork& w, int tid
 #ifdef GLIA_HMT_PROFILE
     const unsigned long long tl0 = __builtin_readcyclecounter();
 #endif
-    __syncthreads();
+    __syncthreads();   // [B:slow-level]
     const bool ovf = w.ovf != 0;
-    const uint32_t n = ovf ? t.lv[l].size : w.wln[cur];
+    const uint32_t n = ovf ? t.lv[l].size : w.wln[cur];   // [R:slow-count]
     const uint32_t ng = (ovf || !w.spill) ? 0u : t.gcount[cur];
     for (uint32_t i = wave; i < n; i += nwaves) {
       const uint32_t j = ovf ? i : w.wl[cur][i];
@@ -365,8 +382,8 @@ __device__ __forceinline__ void pq_propagate(const PqTree& t, PqWork& w, int tid
         if (changed && l + 1 < t.nlevels) pq_touch(t, w, l + 1, cur ^ 1, j);
       }
     }
-    __syncthreads();
-    if (tid == 0 && ng) t.gcount[cur] = 0u;
+    __syncthreads();   // [B:slow-done]
+    if (tid == 0 && ng) t.gcount[cur] = 0u;   // [W:gcount]
     // consume the list: empty it and its membership set
     if (ovf) { for (int i = tid; i < kSetSlots; i += THREADS) { w.set[0][i] = 0; w.set[1][i] = 0; } }
     else {
@@ -377,15 +394,15 @@ __device__ __forceinline__ void pq_propagate(const PqTree& t, PqWork& w, int tid
         w.set[cur][h] = 0;
       }
     }
-    __syncthreads();
-    if (tid == 0) w.wln[cur] = 0;
+    __syncthreads();   // [B:slow-consumed]
+    if (tid == 0) w.wln[cur] = 0;   // [W:wln-slow]
 #ifdef GLIA_HMT_PROFILE
     if (tid == 0) { g_pqprof[l] += __builtin_readcyclecounter() - tl0; g_pqprof[8 + l] += n; g_pqprof[16 + l] += ng; }
 #endif
     cur ^= 1;
   }
-  __syncthreads();
-  if (tid == 0) { w.ovf = 0; w.spill = 0; w.wln[0] = w.wln[1] = 0; }
+  __syncthreads();   // [B:prop-exit]
+  if (tid == 0) { w.ovf = 0; w.spill = 0; w.wln[0] = w.wln[1] = 0; }   // [W:prop-reset]
   pq_top<THREADS>(t, w, tid, topk);
 }
 
