@@ -27,7 +27,7 @@ void set_error(const std::string& msg) { g_err = msg; }
 // when the table is first used -- no entry point calls getenv() per call.
 static const char* const kOptionKeys[] = {"GLIA_HMT_PB_WINDOW", "GLIA_HMT_PB_BATCH", "GLIA_HMT_WINCAP", "GLIA_HMT_REBASE", "GLIA_HMT_HORIZON",
                                           "GLIA_HMT_FORCE_TREE", "GLIA_HMT_HELPERS", "GLIA_HMT_TRACE", "GLIA_HMT_LIBM", "GLIA_HMT_BC_NOCOMMON",
-                                          "GLIA_HMT_BC_GENERIC", "GLIA_HMT_DEBUG", "GLIA_HMT_MAXITERS", "GLIA_HMT_MINCAP"};
+                                          "GLIA_HMT_BC_GENERIC", "GLIA_HMT_DEBUG", "GLIA_HMT_MAXITERS", "GLIA_HMT_MINCAP", "GLIA_HMT_MEDIAN_BATCH"};
 static std::mutex g_opt_mu;
 static std::unordered_map<std::string, std::string> g_opt;
 static bool g_opt_init = false;
@@ -146,6 +146,7 @@ GLIA_DECLARE_GREEDY_BC(greedy_bc) {
 using namespace glia;
 
 #include "api_types.hpp"
+#include "median_layout.hpp"
 
 static std::atomic<int> g_live_contexts{0};
 
@@ -897,14 +898,10 @@ static bool make_bc_cfg(const glia_hmt_rag* rag, BcCfg* c) {
   return true;
 }
 
-// GLIA_USE_MEDIAN_AS_FEATS (type/feat.hxx:677-722, 772-808; hmt/bc_feat.hxx:252-268): one more column per real-feature block -- the
-// diff block of every region-list image, the shared-boundary block of every boundary-list image, and both kinds of block in each of
-// the three region blocks; the simple selection carries the shared boundary's median beside its mean.
-static int median_extra_cols(const glia_hmt_rag* rag, const BcCfg& c) {
-  if (!rag->cfg.use_median_features) return 0;
-  return c.use_simple ? c.n_boundary : 4 * c.n_region + 4 * c.n_boundary;
-}
-// the greedy loop keeps mergeable statistics, not value multisets: with this layout only bc_feat (a given order) is implemented
+// GLIA_USE_MEDIAN_AS_FEATS: the columns the layout adds (median_layout.hpp), 0 for a map built without it
+static int median_extra_cols(const glia_hmt_rag* rag, const BcCfg& c) { return rag->cfg.use_median_features ? median_extra_cols(c) : 0; }
+// the greedy loop keeps mergeable statistics, not value multisets: with this layout bc_feat (a given order) and the scores of the
+// initial edges (both regions are leaves: median_init.hip) are implemented, the loop itself is not
 static int refuse_median_in_loop(const glia_hmt_rag* rag, const char* who) {
   if (!rag->has_cfg || !rag->cfg.use_median_features) return GLIA_HMT_OK;
   set_error(std::string(who) + ": the GLIA_USE_MEDIAN_AS_FEATS layout (type/feat.hxx:677-722) is implemented for a given merge order only (glia_hmt_bc_feat): "
@@ -919,15 +916,23 @@ int glia_hmt_feat_dim(const glia_hmt_rag* rag) {
 }
 
 // What the classifier entry points check before a run of the loop (`who` prefixes the messages).  forest == nullptr: a given
-// order (bc_feat), where the median features are implemented and no classifier reads the vector.
-static int bc_setup(glia_hmt_ctx* c, const glia_hmt_rag* rag, const glia_hmt_forest* forest, const char* who, BcCfg* cfg) {
+// order (bc_feat), where no classifier reads the vector.  The median layout is accepted where `median` is given -- bc_feat and the
+// initial scores, which get the images and the volume of the map there -- and refused by the loop.
+static int bc_setup(glia_hmt_ctx* c, const glia_hmt_rag* rag, const glia_hmt_forest* forest, const char* who, BcCfg* cfg, MedianFeatIn* median = nullptr) {
   if (!make_bc_cfg(rag, cfg) || rag->only_contour) {
     set_error(std::string(who) + ": the region map must be built with a feature configuration and with region points");
     return GLIA_HMT_ERR_ARG;
   }
-  if (forest) {
-    if (int rm = refuse_median_in_loop(rag, who)) return rm;
-    if (forest->max_var >= cfg->fdim) { set_error(std::string(who) + ": the classifier reads features beyond the vector"); return GLIA_HMT_ERR_ARG; }
+  if (!median) { if (int rm = refuse_median_in_loop(rag, who)) return rm; }
+  if (forest && forest->max_var >= cfg->fdim + median_extra_cols(rag, *cfg)) { set_error(std::string(who) + ": the classifier reads features beyond the vector"); return GLIA_HMT_ERR_ARG; }
+  if (median && rag->cfg.use_median_features) {
+    if (forest && !rag->vol.lab) { set_error(std::string(who) + " (median features): needs the volumes the region map was built from (whole-volume build)"); return GLIA_HMT_ERR_UNSUPPORTED; }
+    const glia_hmt_feat_config& g = rag->cfg;
+    memset(median, 0, sizeof(*median));
+    median->rag = &rag->arr; median->vol = rag->vol;
+    median->n_r = g.n_region; median->n_b = g.n_boundary;
+    for (int i = 0; i < g.n_region; ++i) median->r_img[i] = (const float*)g.region[i].d_image;
+    for (int i = 0; i < g.n_boundary; ++i) median->b_img[i] = (const float*)g.boundary[i].d_image;
   }
   GLIA_HIP_TRY(hipSetDevice(c->device));
   return GLIA_HMT_OK;
@@ -993,7 +998,8 @@ int glia_hmt_bc_feat_saliency(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t
   if (!c || !rag || !h_order || !h_feats || n_merges < 0 || rag->ctx != c) { set_error("bc_feat: invalid argument"); return GLIA_HMT_ERR_ARG; }
   BcCfg cfg;
   int rc;
-  if ((rc = bc_setup(c, rag, nullptr, "bc_feat", &cfg))) return rc;
+  MedianFeatIn in;
+  if ((rc = bc_setup(c, rag, nullptr, "bc_feat", &cfg, &in))) return rc;
   const int64_t R = rag->arr.R;
   if (n_merges == 0) return GLIA_HMT_OK;
   if (n_merges >= R) { set_error("bc_feat: more merges than regions"); return GLIA_HMT_ERR_ARG; }
@@ -1030,64 +1036,25 @@ int glia_hmt_bc_feat_saliency(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t
   int bfdim = cfg.bfdim, rfdim = cfg.rfdim, fdim = cfg.fdim;
   if (rag->cfg.use_median_features) {
     // GLIA_USE_MEDIAN_AS_FEATS: the kernel's rows (built from the statistics monoids) + the medians, means and standard deviations
-    // of the value multisets (median_feats.hip), spliced into the reference's layout
-    const glia_hmt_feat_config& g = rag->cfg;
-    MedianFeatIn in;
-    memset(&in, 0, sizeof(in));
-    in.rag = &rag->arr; in.vol = rag->vol; in.forced = forced.data(); in.n_merges = n_merges;
-    in.n_r = g.n_region; in.n_b = g.n_boundary;
-    for (int i = 0; i < g.n_region; ++i) in.r_img[i] = (const float*)g.region[i].d_image;
-    for (int i = 0; i < g.n_boundary; ++i) in.b_img[i] = (const float*)g.boundary[i].d_image;
+    // of the value multisets (median_feats.hip), spliced into the reference's layout (median_layout.hpp)
+    in.forced = forced.data(); in.n_merges = n_merges;
     std::vector<double> reg, bnd;
     std::vector<unsigned long long> marea;
     if ((rc = median_feature_stats(in, c->stream, &reg, &bnd, &marea))) return rc;
-    const int nr = g.n_region, nl = g.n_rlabel, nb = g.n_boundary, T = cfg.T, D = cfg.D;
-    const int extra = median_extra_cols(rag, cfg);
-    const int nd = cfg.fdim + extra;
+    const int nr = in.n_r, nb = in.n_b;
+    const int nd = cfg.fdim + median_extra_cols(rag, cfg);
     std::vector<double> rows((size_t)n * nd);
-    auto hb = [&](int kind, int i) { return cfg.use_hist ? cfg.cbins[kind == 0 ? cfg.rc[i] : kind == 1 ? cfg.lc[i] : cfg.bc[i]] : 0; };
     for (int64_t i = 0; i < n; ++i) {
       const bool swap = sdivide_host((double)marea[forced[2 * i]], cfg.norm_area) > sdivide_host((double)marea[forced[2 * i + 1]], cfg.norm_area);
       // x1 = the smaller region (main_bc_feat.cxx:84-88): k of the statistics arrays for block b of the row
       const int kreg[3] = {swap ? 1 : 0, swap ? 0 : 1, 2};
       auto RS = [&](int blk, int img, int q) { return reg[(((size_t)i * 3 + kreg[blk]) * nr + img) * 3 + q]; };
       auto BS = [&](int blk, int img, int q) { return bnd[(((size_t)i * 4 + (blk < 3 ? kreg[blk] : 3)) * nb + img) * 3 + q]; };
-      const double* in_row = &feats[(size_t)i * cfg.fdim];
-      double* out = &rows[(size_t)i * nd];
-      int p = 0, k = 0;
-      if (cfg.use_simple) {                                         // hmt/bc_feat.hxx:247-279
-        for (int q = 0; q < 5; ++q) out[k++] = in_row[p++];
-        for (int j = 0; j < nb; ++j) { out[k++] = BS(3, j, 1); out[k++] = BS(3, j, 0); ++p; }
-        for (int j = 0; j < nr; ++j) { out[k++] = std::fabs(RS(0, j, 1) - RS(1, j, 1)); out[k++] = in_row[p + 1]; out[k++] = in_row[p + 2]; out[k++] = in_row[p + 3]; p += 4; }
-        for (int j = 0; j < 2 * nl; ++j) out[k++] = in_row[p++];
-      } else {
-        for (int q = 0; q < 11 + 4 * T; ++q) out[k++] = in_row[p++];
-        for (int j = 0; j < nr; ++j) {                               // feat.hxx:782-808: l1, x2, |d entropy|, |d median|, |d mean|, |d std|, |d min|, |d max|
-          out[k++] = in_row[p]; out[k++] = in_row[p + 1]; out[k++] = in_row[p + 2];
-          out[k++] = std::fabs(RS(0, j, 0) - RS(1, j, 0)); out[k++] = std::fabs(RS(0, j, 1) - RS(1, j, 1)); out[k++] = std::fabs(RS(0, j, 2) - RS(1, j, 2));
-          out[k++] = in_row[p + 5]; out[k++] = in_row[p + 6];
-          p += 7;
-        }
-        for (int q = 0; q < 3 * nl; ++q) out[k++] = in_row[p++];
-        auto real_block = [&](int h, double med, double mean, double sd) {     // [histogram] entropy | median mean std | min max
-          for (int q = 0; q < h + 1; ++q) out[k++] = in_row[p++];
-          out[k++] = med; out[k++] = mean; out[k++] = sd;
-          out[k++] = in_row[p + 2]; out[k++] = in_row[p + 3];
-          p += 4;
-        };
-        for (int j = 0; j < nb; ++j) real_block(hb(2, j), BS(3, j, 0), BS(3, j, 1), BS(3, j, 2));
-        for (int blk = 0; blk < 3; ++blk) {
-          for (int q = 0; q < 4 + D + 2 * T; ++q) out[k++] = in_row[p++];
-          for (int j = 0; j < nr; ++j) real_block(hb(0, j), RS(blk, j, 0), RS(blk, j, 1), RS(blk, j, 2));
-          for (int j = 0; j < nl; ++j) for (int q = 0; q < hb(1, j) + 1; ++q) out[k++] = in_row[p++];
-          for (int j = 0; j < nb; ++j) real_block(hb(2, j), BS(blk, j, 0), BS(blk, j, 1), BS(blk, j, 2));
-        }
-      }
-      if (p != cfg.fdim || k != nd) { set_error("bc_feat: internal error, median feature layout"); return GLIA_HMT_ERR_INTERNAL; }
+      if (median_splice(cfg, &feats[(size_t)i * cfg.fdim], &rows[(size_t)i * nd], RS, BS) != nd) { set_error("bc_feat: internal error, median feature layout"); return GLIA_HMT_ERR_INTERNAL; }
     }
     feats.swap(rows);
     fdim = nd;
-    if (!cfg.use_simple) { bfdim = cfg.bfdim + nr + nb; rfdim = cfg.rfdim + nr + nb; }
+    if (!cfg.use_simple) { bfdim = cfg.bfdim + in.n_r + in.n_b; rfdim = cfg.rfdim + in.n_r + in.n_b; }
   }
   if (!h_saliencies || cfg.use_simple) {       // selectFeatures carries no saliency (hmt/bc_feat.hxx:247-279)
     memcpy(h_feats, feats.data(), sizeof(double) * (size_t)n * fdim);
@@ -1207,9 +1174,11 @@ int glia_hmt_score_initial_edges(glia_hmt_ctx* c, glia_hmt_rag* rag, const glia_
   if (!c || !rag || !forest || rag->ctx != c) { set_error("score_initial_edges: invalid argument"); return GLIA_HMT_ERR_ARG; }
   BcCfg cfg;
   int rc;
-  if ((rc = bc_setup(c, rag, forest, "score_initial_edges", &cfg))) return rc;
+  MedianFeatIn median;
+  if ((rc = bc_setup(c, rag, forest, "score_initial_edges", &cfg, &median))) return rc;
   BcRequest req;
   req.init_only = true;
+  if (rag->cfg.use_median_features) req.median = &median;
   MergeResult res;
   if ((rc = greedy_bc(rag->arr, cfg, forest->dc, c->stream, req, &res))) return rc;
   keep_timing(rag, res);
@@ -1226,10 +1195,12 @@ int glia_hmt_score_initial_edges_shard(glia_hmt_ctx* c, glia_hmt_rag* rag, const
   }
   BcCfg cfg;
   int rc;
-  if ((rc = bc_setup(c, rag, forest, "score_initial_edges", &cfg))) return rc;
+  MedianFeatIn median;
+  if ((rc = bc_setup(c, rag, forest, "score_initial_edges", &cfg, &median))) return rc;
   // one record per unordered leaf pair; the count is needed before the scores can be copied out
   BcRequest req;
   req.init_only = true; req.scores = h_scores != nullptr; req.shard = shard; req.n_shards = n_shards;
+  if (rag->cfg.use_median_features) req.median = &median;
   MergeResult res;
   if ((rc = greedy_bc(rag->arr, cfg, forest->dc, c->stream, req, &res))) return rc;
   keep_timing(rag, res);

@@ -35,6 +35,7 @@
 #include "bc_features.hpp"
 #include "forest.hpp"
 #include "greedy_common.hpp"
+#include "median_layout.hpp"
 #include "rmap_order.hpp"
 
 namespace glia {
@@ -581,6 +582,34 @@ __global__ void bc_init_score(BcState st, uint32_t E0) {
   double x[kMaxFeat];
   edge_features_global(st, first, second, e, ex, x);
   st.pq.leaf_sal[e] = classify_serial(st.clf, x);
+}
+
+// The same with the GLIA_USE_MEDIAN_AS_FEATS layout, for the records [e0, e1): the statistics-based vector as above, expanded with
+// the medians, means and standard deviations median_init.hip has filed at slot e - e0 (reg / bnd, hmt_internal.hpp), then classified.
+// x1 / x2: the feature code puts `first` into the x1 block unless it is the larger region (edge_features; main_bc_feat.cxx:84-88).
+__global__ void bc_init_score_median(BcState st, uint32_t e0, uint32_t e1, const double* reg, const double* bnd) {
+  const uint32_t e = e0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= e1 || !st.e_table[e] || e % st.n_shards != st.shard) return;
+  const uint32_t u = st.e_u[e], v = st.e_v[e];
+  const uint32_t first = st.e_orient[e] ? u : v, second = st.e_orient[e] ? v : u;
+  float ex[4 * kMaxChannels];
+#pragma unroll
+  for (int c = 0; c < kMaxChannels; ++c) {
+    if (c < st.cfg.K) { excl_minmax(st, c, first, e, ex[4 * c + 0], ex[4 * c + 1]); excl_minmax(st, c, second, e, ex[4 * c + 2], ex[4 * c + 3]); }
+    else { ex[4 * c + 0] = ex[4 * c + 1] = ex[4 * c + 2] = ex[4 * c + 3] = 0.f; }
+  }
+  double x[kMaxFeat], y[kMaxFeat];
+  edge_features_global(st, first, second, e, ex, x);
+  const uint32_t n_first = st.ch[0].pts[first].n, n_second = st.ch[0].pts[second].n;
+  const bool swap = feat::sdiv((double)n_first, st.cfg.norm_area, 0.0) > feat::sdiv((double)n_second, st.cfg.norm_area, 0.0);
+  const uint32_t x1 = swap ? second : first;
+  const int kreg[3] = {x1 == u ? 0 : 1, x1 == u ? 1 : 0, 2};          // block of the row -> set of the record (u | v | u + v)
+  const size_t slot = e - e0;
+  const int nr = st.cfg.n_region, nb = st.cfg.n_boundary;
+  const int k = median_splice(st.cfg, x, y,
+                              [&](int blk, int img, int q) { return reg[((slot * 3 + kreg[blk]) * nr + img) * 3 + q]; },
+                              [&](int blk, int img, int q) { return bnd[((slot * 4 + (blk < 3 ? kreg[blk] : 3)) * nb + img) * 3 + q]; });
+  st.pq.leaf_sal[e] = k < 0 ? __builtin_nan("") : classify_serial(st.clf, y);      // (k < 0: a layout error; the driver has checked the lengths)
 }
 
 // ---- the loop ----------------------------------------------------------------------------------------------
@@ -1763,6 +1792,10 @@ GLIA_DECLARE_GREEDY_BC(GLIA_BC_ENTRY) {
     set_error("merge_order_bc: feature vector too long (" + std::to_string(bc_full_dim(cfg)) + " columns before --simpf, limit " + std::to_string(kMaxFeat) + ")");
     return GLIA_HMT_ERR_ARG;
   }
+  if (req.median && cfg.fdim + median_extra_cols(cfg) > kMaxFeat) {
+    set_error("score_initial_edges: feature vector too long with the median columns (" + std::to_string(cfg.fdim + median_extra_cols(cfg)) + " columns, limit " + std::to_string(kMaxFeat) + ")");
+    return GLIA_HMT_ERR_ARG;
+  }
   CallEvents<4> ev;
   int rc;
   if ((rc = ev.create())) return rc;
@@ -1905,7 +1938,27 @@ GLIA_DECLARE_GREEDY_BC(GLIA_BC_ENTRY) {
   hipLaunchKernelGGL(bc_hadj_fill, dim3((R + 255) / 256), dim3(256), 0, stream, st);
   GLIA_HIP_TRY(hipGetLastError());
   GLIA_HIP_TRY(hipEventRecord(ev.ev[1], stream));
-  if (!req.forced) hipLaunchKernelGGL(bc_init_score, dim3((E0 + 127) / 128), dim3(128), 0, stream, st, E0);
+  if (!req.forced && !req.median) hipLaunchKernelGGL(bc_init_score, dim3((E0 + 127) / 128), dim3(128), 0, stream, st, E0);
+  if (!req.forced && req.median) {
+    // the median layout: per batch of records the medians / means / standard deviations of their sets (median_init.hip), then the
+    // scores.  A batch's side table stays below 1 GiB; more than one batch sorts the images once per batch (GLIA_HMT_MEDIAN_BATCH:
+    // records per batch, tests).
+    const size_t per_rec = 3 * sizeof(double) * (size_t)(3 * cfg.n_region + 4 * cfg.n_boundary);
+    uint32_t batch = (uint32_t)std::min<size_t>(E0, std::max<size_t>(1, ((size_t)1 << 30) / std::max<size_t>(per_rec, 1)));
+    std::string env;
+    if (option("GLIA_HMT_MEDIAN_BATCH", &env) && atoi(env.c_str()) > 0) batch = (uint32_t)std::min<long long>(E0, atoll(env.c_str()));
+    double *d_reg, *d_bnd;
+    if ((rc = buf.get(&d_reg, (size_t)batch * 3 * cfg.n_region * 3, false, stream)) || (rc = buf.get(&d_bnd, (size_t)batch * 4 * cfg.n_boundary * 3, false, stream))) return rc;
+    const MedianInitRecords recs{st.e_u, st.e_v, st.e_table, st.shard, st.n_shards, st.le_start, st.le_dst};
+    MedianInitTiming mt;
+    for (uint32_t e0 = 0; e0 < E0; e0 += batch) {
+      const uint32_t e1 = (uint32_t)std::min<unsigned long long>(E0, (unsigned long long)e0 + batch);
+      if ((rc = median_init_stats(*req.median, recs, e0, e1, stream, d_reg, d_bnd, &mt))) return rc;
+      hipLaunchKernelGGL(bc_init_score_median, dim3((e1 - e0 + 127) / 128), dim3(128), 0, stream, st, e0, e1, d_reg, d_bnd);
+    }
+    if (trace) fprintf(stderr, "[trace] greedy_bc: median layout, %u records in batches of %u: sort stage %.2f ms, selection %.2f ms, %.1f MB of run buffers + %.1f MB side table\n",
+                       E0, batch, mt.ms_sort, mt.ms_select, (double)mt.bytes / 1048576.0, (double)((size_t)batch * per_rec) / 1048576.0);
+  }
   if (req.forced) {
     uint32_t* d_forced;
     if ((rc = buf.get(&d_forced, (size_t)2 * req.n_forced + 2, false, stream))) return rc;

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/glia_hmt.h"
+#include "median_select.hpp"   // float_ord / ord_float, the order-preserving 32-bit image of an f32
 
 namespace glia {
 
@@ -131,6 +132,20 @@ struct MedianFeatIn {
   const uint32_t* forced; int64_t n_merges;
 };
 int median_feature_stats(const MedianFeatIn& in, hipStream_t stream, std::vector<double>* reg, std::vector<double>* bnd, std::vector<unsigned long long>* area);
+// GLIA_USE_MEDIAN_AS_FEATS for the INITIAL edges (median_init.hip): every leaf's values and every directed pair's boundary values are
+// sorted once per listed image, and the sets of a record (u, v) -- both leaves -- are selections over those runs.  The records are the
+// ones of the classifier loop's state (greedy_bc.hip); records [e0, e1) that are table edges of the shard get, at slot e - e0,
+//   reg[((slot * 3 + k) * n_r + c) * 3 + q]   k = P(u) | P(v) | P(u + v),               q = median | mean | stddev
+//   bnd[((slot * 4 + k) * n_b + c) * 3 + q]   k = B(u) | B(v) | B(u + v) | shared boundary
+// (device arrays; u < v are the record's dense leaf ids, NOT the x1 / x2 of the row).  forced / n_merges of `in` are not read.
+struct MedianInitRecords {
+  const uint32_t *e_u, *e_v; const uint8_t* e_table; uint32_t shard, n_shards;
+  const uint32_t* le_start;      // [R + 1] first directed entry of each leaf (entries ascend by (source, target))
+  const uint32_t* le_dst;        // [P] target leaf of each entry
+};
+struct MedianInitTiming { double ms_sort = 0, ms_select = 0; unsigned long long bytes = 0; };   // sort stage (grouping + sort + run sums) | selection kernels | device memory taken
+int median_init_stats(const MedianFeatIn& in, const MedianInitRecords& rec, uint32_t e0, uint32_t e1, hipStream_t stream, double* d_reg, double* d_bnd,
+                      MedianInitTiming* timing);
 // bc_label (truth_overlap.hip, bc_label.cpp): the voxels of dense leaf `leaf` with truth label `truth` (0 included), sorted by
 // (leaf, truth); *ms = device time of the counting pass
 struct TruthCount { uint32_t leaf, truth; unsigned long long count; };
@@ -172,6 +187,7 @@ struct BcRequest {
   bool rows = false;                            // MergeResult::rows wanted
   bool init_only = false;                       // features + scores of the initial records only (TBoundaryTable::init): n = records
   bool scores = false;                          // init_only: MergeResult::sal = the records' scores
+  const MedianFeatIn* median = nullptr;         // init_only: score the median layout (GLIA_USE_MEDIAN_AS_FEATS) -- the images and the volume of the map
   int shard = 0, n_shards = 1;
 };
 // greedy_bc.hip is compiled five times: with the libm restatements of the feature code (glibc_math.hpp) selected at run time
@@ -207,14 +223,5 @@ int gather_value_runs(const unsigned long long* src_off, const float* src_vals, 
                       float** out_vals, unsigned long long* nV, hipStream_t stream);
 int rag_cut_flags(const RagArrays& rag, const uint32_t* d_lab, int64_t nx, int64_t ny, int64_t nzl, int64_t zb, int64_t ze,
                   uint8_t* d_rflag, uint8_t* d_pflag, hipStream_t stream);
-
-__host__ __device__ inline uint32_t float_ord(float f) {
-  uint32_t u = __builtin_bit_cast(uint32_t, f);
-  return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__host__ __device__ inline float ord_float(uint32_t o) {
-  uint32_t u = o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu);
-  return __builtin_bit_cast(float, u);
-}
 
 }  // namespace glia

@@ -23,10 +23,8 @@
 // The greedy LOOP with this layout (sets that change with every contraction) is not implemented: GLIA_HMT_ERR_UNSUPPORTED.
 #include <algorithm>
 #include <cmath>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_segmented_radix_sort.hpp>
 
-#include "greedy_common.hpp"
+#include "median_runs.hpp"
 
 namespace glia {
 
@@ -34,52 +32,6 @@ namespace {
 
 constexpr unsigned long long kBatchValues = 1ull << 27;      // values gathered, sorted and reduced at a time
 constexpr unsigned long long kSetLimit = 1ull << 30;         // one set
-
-__global__ void mf_gather_u32(const uint32_t* rec, long long n, int words, int word, uint32_t* out) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = rec[(size_t)i * words + word];
-}
-
-// voxel values grouped by leaf: dst = leaf_off[leaf] + running count (the order inside a leaf does not matter: the sets are sorted)
-__global__ void mf_scatter_regions(VolumeRef vol, const float* img, const uint32_t* rlabel, uint32_t R, const unsigned long long* leaf_off, uint32_t* cursor, float* out) {
-  const long long N = vol.nx * vol.ny * vol.nz;
-  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= N) return;
-  const uint32_t t = vol.lab[p];
-  if (t == kMaskedLabel) return;                          // masked-out centre (point-map mode: util/struct.hxx:86-91)
-  const uint32_t leaf = find_label(rlabel, R, t);
-  if (leaf >= R || rlabel[leaf] != t) return;
-  out[leaf_off[leaf] + atomicAdd(&cursor[leaf], 1u)] = img[p];
-}
-
-// boundary-voxel values grouped by directed pair, the neighbour rule of type/neighbor.hxx:109-126 (masked-out neighbours are invalid)
-__global__ void mf_scatter_pairs(VolumeRef vol, const float* img, const uint32_t* pa, const uint32_t* pb, long long P, const unsigned long long* off, uint32_t* cursor,
-                                 float* out) {
-  const long long N = vol.nx * vol.ny * vol.nz;
-  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= N) return;
-  const long long x = p % vol.nx, y = (p / vol.nx) % vol.ny, z = p / (vol.nx * vol.ny);
-  const uint32_t t = vol.lab[p];
-  if (t == kMaskedLabel) return;
-  uint32_t nb = t;
-  const long long sy = vol.nx, sz = vol.nx * vol.ny;
-  const uint32_t* L = vol.lab_nb;
-  do {
-    uint32_t q;
-    if (x > 0 && (q = L[p - 1]) != t && q != kMaskedLabel) { nb = q; break; }
-    if (x + 1 < vol.nx && (q = L[p + 1]) != t && q != kMaskedLabel) { nb = q; break; }
-    if (y > 0 && (q = L[p - sy]) != t && q != kMaskedLabel) { nb = q; break; }
-    if (y + 1 < vol.ny && (q = L[p + sy]) != t && q != kMaskedLabel) { nb = q; break; }
-    if (vol.dim == 3) {
-      if (z > 0 && (q = L[p - sz]) != t && q != kMaskedLabel) { nb = q; break; }
-      if (z + 1 < vol.nz && (q = L[p + sz]) != t && q != kMaskedLabel) { nb = q; break; }
-    }
-  } while (false);
-  if (nb == t) return;
-  const long long i = find_pair(pa, pb, P, t, nb);
-  if (i < 0) return;
-  out[off[i] + atomicAdd(&cursor[i], 1u)] = img[p];
-}
 
 // the runs of a batch of sets into one buffer: element k of the buffer belongs to the run r with dst[r] <= k < dst[r + 1]
 __global__ void mf_expand(const float* src, const unsigned long long* run_src, const unsigned long long* run_dst, uint32_t n_runs, unsigned long long total, float* out) {

@@ -217,7 +217,8 @@ def make_config(pb, rb=(), r=(), rl=(), b=(), thresholds=(0.2, 0.5, 0.8), normal
                 normalizing_length=1.0, use_log_shape=False, use_simple_features=False, use_histogram_features=False,
                 use_median_features=False):
     """Builds the image lists the way prepareImages does (hmt/hmt_util.hxx:17-56).
-    rb/r/rl/b: sequences of (device tensor, bins, lo, hi)."""
+    rb/r/rl/b: sequences of (device tensor, bins, lo, hi).  use_median_features (GLIA_USE_MEDIAN_AS_FEATS): supported by bc_feat
+    and score_initial_edges / score_initial_edges_shard, refused by merge_order_bc."""
     cfg = FeatConfig()
     keep = [pb]
 
@@ -684,12 +685,15 @@ class RegionMap:
         return {k: getattr(t, k) for k, _ in BcLabelTiming._fields_}
 
     def score_initial_edges(self, classifier):
+        """features + scores of the initial table edges (TBoundaryTable::init) -> (edges scored, device ms).  With
+        use_median_features the medians come from sorted value runs of every leaf and directed pair (whole-volume maps only)."""
         n, ms = C.c_int64(0), C.c_double(0)
         _check(lib().glia_hmt_score_initial_edges(self.ctx.h, self.h, classifier.h, C.byref(n), C.byref(ms)))
         return n.value, ms.value
 
     def score_initial_edges_shard(self, classifier, shard, n_shards):
-        """scores of the initial records e with e % n_shards == shard (-inf elsewhere); max over shards = all scores"""
+        """scores of the initial records e with e % n_shards == shard (-inf elsewhere); max over shards = all scores.  Works with
+        use_median_features as well (whole-volume maps; merge_order_bc still refuses that layout)."""
         cap = max(self.num_pairs, 1)
         out = np.empty(cap, np.float64)
         n = C.c_int64(0)

@@ -124,9 +124,13 @@ typedef struct {
    * the MEDIAN of its voxel set ahead of the mean, mean / standard deviation come from the value vector (stats::mean, stats::var),
    * the diff blocks gain |median0 - median1|, --simpf carries the shared boundary's median beside its mean (hmt/bc_feat.hxx:252-268).
    * Implemented for a GIVEN merge order (glia_hmt_bc_feat / _saliency: glia_amd/csrc/median_feats.hip; the value multisets of one
-   * order are processed in batches of 2^27 values, one set may hold at most 2^30); the greedy loop (glia_hmt_merge_order_bc,
-   * glia_hmt_score_initial_edges) returns GLIA_HMT_ERR_UNSUPPORTED with this layout.  Median columns are bit-exact, the mean / stddev
-   * columns comparable to 1e-12 (the reference sums in an order that depends on rand(), util/stats.hxx:87). */
+   * order are processed in batches of 2^27 values, one set may hold at most 2^30) and for the scores of the INITIAL edges
+   * (glia_hmt_score_initial_edges / _shard with a forest, an ensemble or the stub: glia_amd/csrc/median_init.hip sorts every leaf's
+   * and every directed pair's values once per listed image and selects each median over those runs; < 2^32 values per image).  Both
+   * need the volumes the map was built from (glia_hmt_rag_build; a slab / distributed map gives GLIA_HMT_ERR_UNSUPPORTED).  The
+   * greedy loop (glia_hmt_merge_order_bc) returns GLIA_HMT_ERR_UNSUPPORTED with this layout.  Median columns are bit-exact (the
+   * radix sort's order is the ordering rule: -0.0 sorts below +0.0), the mean / stddev columns comparable to 1e-12 (the reference
+   * sums in an order that depends on rand(), util/stats.hxx:87). */
   int use_histogram_features;
   int use_median_features;
 } glia_hmt_feat_config;
