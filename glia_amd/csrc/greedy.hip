@@ -94,6 +94,45 @@ __global__ void win_collect_kernel(const EdgeRec* er, uint32_t n_edges, const ui
   const uint32_t i = atomicAdd(counter, 1u);
   kseq[i] = q; vals[i] = e;
 }
+// The same for the batch kernel, from the LISTS of the live regions: one wave per region r < n_regions that has not been merged away
+// walks its incident-edge list and takes every entry with a live edge, a smaller neighbour (entry.rs < r picks every live edge
+// exactly once, from the list of its larger region: u < v for an initial edge, and r2 is the newest region when its edges are made)
+// and a live partner.  The records of 30 M created edges are not read -- the live edges sit in at most 2 x E0 entries -- and need
+// not all exist: an edge created below the horizon of the interval that just ended (slot >= ne_base, cell < wch: store_new_edge's
+// predicate, with the interval's values still in st) gets its record here, rebuilt from the entry (edge_record.hpp); every other
+// edge has one.  counter[0] = items (cap = room in kseq / vals), counter[1] = records rebuilt.
+__global__ void win_collect_lists_kernel(WinState st, uint32_t n_regions, unsigned long long* kseq, uint32_t* vals, uint32_t cap, uint32_t* counter) {
+  const uint32_t r = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+  if (r >= n_regions || st.rdead[r]) return;                             // (uniform per wave)
+  const uint32_t off = st.adj_off[r], len = st.adj_len[r];
+  const double smin = st.wrange[0], scale = st.wrange[1];
+  uint32_t rebuilt = 0;
+  for (uint32_t base = 0; base < len; base += 64u) {
+    const uint32_t i = base + lane;
+    unsigned long long q = 0;
+    uint32_t e = kNone;
+    if (i < len) {
+      const FatEntry fe = st.fpool[off + i];
+      if (fe.eid != kNone && fe.rs < r && !st.rdead[fe.rs]) {
+        e = fe.eid;
+        if ((unsigned long long)e >= st.ne_base && win_cell(-fe.mean, smin, scale, st.wB) < st.wch) {
+          const EdgeRec rec = rebuild_edge_record(fe, i, r, off, len, st.ecat[e], st.R0);
+          st.er[e] = rec;
+          q = rec.seq; ++rebuilt;
+        } else q = st.er[e].seq;
+      }
+    }
+    const unsigned long long m = __ballot(q != 0);
+    if (m == 0) continue;
+    const int first = (int)__builtin_ctzll(m);
+    uint32_t b0 = 0;
+    if ((int)lane == first) b0 = atomicAdd(&counter[0], (uint32_t)__popcll(m));
+    b0 = (uint32_t)__shfl((int)b0, first);
+    const uint32_t o = b0 + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (q != 0 && o < cap) { kseq[o] = q; vals[o] = e; }                 // (more than cap items: the host stops on the count)
+  }
+  if (rebuilt) atomicAdd(&counter[1], rebuilt);
+}
 __global__ void win_salkey_kernel(const EdgeRec* er, const uint32_t* vals, uint32_t n, unsigned long long* ksal) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) ksal[i] = f64_ord(er[vals[i]].sal);
@@ -141,6 +180,17 @@ __global__ void edge_unpack(GreedyState g, const EdgeRec* er, const uint8_t* rde
   const EdgeRec r = er[e];
   g.e_u[e] = r.u; g.e_v[e] = r.v; g.e_posu[e] = r.posu; g.e_posv[e] = r.posv; g.e_mean[e] = r.mean; g.e_n[e] = r.n;
   g.pq.leaf_sal[e] = r.sal; g.pq.leaf_seq[e] = (rdead[r.u] | rdead[r.v]) ? 0ull : r.seq;
+}
+
+// ... after a batch launch: only the n live edges the collection pass listed (vals) have records for certain, and only they are ever
+// looked at again (a live region's list holds live edges and tombstones); every other leaf has been marked dead beforehand
+__global__ void edge_unpack_live(GreedyState g, const EdgeRec* er, const uint32_t* vals, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t e = vals[i];
+  const EdgeRec r = er[e];
+  g.e_u[e] = r.u; g.e_v[e] = r.v; g.e_posu[e] = r.posu; g.e_posv[e] = r.posv; g.e_mean[e] = r.mean; g.e_n[e] = r.n;
+  g.pq.leaf_sal[e] = r.sal; g.pq.leaf_seq[e] = r.seq;
 }
 
 // ---- edge table construction --------------------------------------------------------------------------
@@ -271,6 +321,8 @@ struct WinBaseline {
   long long prev_top_cell = -1;
   unsigned long long prev_ne = 0;
   double horizon_factor = 0.0;                                           // 0 = no horizon (set for the batch kernel)
+  bool from_lists = false;                                               // the batch kernel: collect from the lists of the live regions (win_collect_lists_kernel)
+  unsigned long long rebuilt_last = 0;                                   // records the last collection rebuilt
 
   // the queue's device arrays for B saliency cells, and the saliency range of the n_initial initial edges
   int init(DeviceBuffers& buf, WinState& ws, const double* leaf_sal, uint32_t n_initial, uint32_t B, uint32_t R, hipStream_t stream) {
@@ -291,7 +343,7 @@ struct WinBaseline {
     if ((rc = buf.get(&ksal2, E0, false, stream))) return rc;
     if ((rc = buf.get(&vals, E0, false, stream))) return rc;
     if ((rc = buf.get(&vals2, E0, false, stream))) return rc;
-    if ((rc = buf.get(&counter, 1, true, stream))) return rc;
+    if ((rc = buf.get(&counter, 2, true, stream))) return rc;
     GLIA_HIP_TRY(rocprim::radix_sort_pairs_desc(nullptr, tmp_bytes, kseq, kseq2, vals, vals2, (size_t)E0, 0, 64, stream));
     if ((rc = buf.get((char**)&tmp, tmp_bytes ? tmp_bytes : 16, false, stream))) return rc;
     ws.wrange = range; ws.isort = isort; ws.isort_seq = iseq; ws.ige = ige;
@@ -304,14 +356,26 @@ struct WinBaseline {
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
     return GLIA_HMT_OK;
   }
-  // a fresh baseline of the first n_edges edge records; the threshold words of ctrl are reset to "everything is below it"
-  int rebaseline(WinState& ws, uint32_t n_edges, unsigned long long* ctrl, hipStream_t stream) {
-    GLIA_HIP_TRY(hipMemsetAsync(counter, 0, sizeof(uint32_t), stream));
-    hipLaunchKernelGGL(win_collect_kernel, dim3((n_edges + 255) / 256), dim3(256), 0, stream, ws.er, n_edges, ws.rdead, kseq, vals, counter);
-    uint32_t n = 0;
-    GLIA_HIP_TRY(hipMemcpyAsync(&n, counter, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  // every live queue item (seq, edge) into kseq / vals, in any order: from the first n_edges edge records, or from the lists of the
+  // live regions among the first n_regions, rebuilding the records the batch kernel did not write (ws still holds the horizon and
+  // the edge count of the interval that just ended)
+  int collect(const WinState& ws, uint32_t n_edges, uint32_t n_regions, hipStream_t stream, uint32_t* n_out) {
+    GLIA_HIP_TRY(hipMemsetAsync(counter, 0, 2 * sizeof(uint32_t), stream));
+    if (from_lists) hipLaunchKernelGGL(win_collect_lists_kernel, dim3((unsigned)(((unsigned long long)n_regions * 64ull + 255ull) / 256ull)), dim3(256), 0, stream, ws, n_regions, kseq, vals, E0, counter);
+    else hipLaunchKernelGGL(win_collect_kernel, dim3((n_edges + 255) / 256), dim3(256), 0, stream, ws.er, n_edges, ws.rdead, kseq, vals, counter);
+    GLIA_HIP_TRY(hipGetLastError());
+    uint32_t h[2] = {0, 0};
+    GLIA_HIP_TRY(hipMemcpyAsync(h, counter, sizeof(h), hipMemcpyDeviceToHost, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
-    if (n > E0) { set_error("greedy: more live edges than initial edges (internal error)"); return GLIA_HMT_ERR_INTERNAL; }
+    if (h[0] > E0) { set_error("greedy: more live edges than initial edges (internal error)"); return GLIA_HMT_ERR_INTERNAL; }
+    *n_out = h[0]; rebuilt_last = h[1];
+    return GLIA_HMT_OK;
+  }
+  // a fresh baseline of the first n_edges edges (the lists of the first R0 + merges regions); the threshold words of ctrl are reset to
+  // "everything is below it"
+  int rebaseline(WinState& ws, uint32_t n_edges, unsigned long long* ctrl, hipStream_t stream) {
+    uint32_t n = 0;
+    if (int rc = collect(ws, n_edges, ws.R0 + (uint32_t)ctrl[CTRL_MERGES], stream, &n)) return rc;
     if (n) {
       size_t bytes = tmp_bytes;
       GLIA_HIP_TRY(rocprim::radix_sort_pairs_desc(tmp, bytes, kseq, kseq2, vals, vals2, (size_t)n, 0, 64, stream));
@@ -393,6 +457,7 @@ static int run_pb_loop(const RagArrays& rag, hipStream_t stream, const PbRequest
   if (window) {
     if ((rc = entries.add(buf, &ws.fpool, st.pool_cap, stream))) return rc;
     if ((rc = edges.add(buf, &ws.er, st.Ecap, stream))) return rc;
+    if ((rc = edges.add(buf, &ws.ecat, st.Ecap, stream))) return rc;
   }
   else if ((rc = entries.add(buf, &st.pool, st.pool_cap, stream))) return rc;
   if ((rc = edges.add(buf, &st.e_u, st.Ecap, stream)) || (rc = edges.add(buf, &st.e_v, st.Ecap, stream)) ||
@@ -477,6 +542,10 @@ static int run_pb_loop(const RagArrays& rag, hipStream_t stream, const PbRequest
     if ((rc = base.init(buf, ws, st.pq.leaf_sal, E0, B, R, stream))) return rc;
     // the horizon: 0 = off; else the factor on the measured descent (swept 0.05 .. 8 at 1024^3: flat from 0.1 to 0.5, +1 % at 2, +2 % at 4)
     if (req.cond_n <= 0 && !batch_off) base.horizon_factor = option("GLIA_HMT_HORIZON", &o_txt) ? atof(o_txt.c_str()) : 0.5;
+    // the batch kernel keeps rdead and writes no record below its horizon: its baselines come from the lists of the live regions.  The
+    // one-at-a-time kernel (pre_merge, GLIA_HMT_PB_BATCH=0) has neither -- a rejected edge stays in the lists with seq == 0 -- and
+    // keeps the scan of the records
+    base.from_lists = req.cond_n <= 0 && !batch_off;
     if ((rc = base.rebaseline(ws, E0, ctrl, stream))) return rc;
   } else if ((rc = pq_setup(buf, st.pq, stream))) return rc;
   GLIA_HIP_TRY(hipMemcpyAsync(st.ctrl, ctrl, sizeof(ctrl), hipMemcpyHostToDevice, stream));
@@ -503,7 +572,8 @@ static int run_pb_loop(const RagArrays& rag, hipStream_t stream, const PbRequest
     GLIA_HIP_TRY(hipGetLastError());
     GLIA_HIP_TRY(hipMemcpyAsync(ctrl, st.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
-    if (trace) fprintf(stderr, "[trace] merge loop launch ended: status %llu, merges %llu of %u regions, edges %llu, list entries %llu\n", ctrl[CTRL_STATUS], ctrl[CTRL_MERGES], R, ctrl[CTRL_EDGES], ctrl[CTRL_ENTRIES]);
+    if (trace) fprintf(stderr, "[trace] merge loop launch ended: status %llu, merges %llu of %u regions, edges %llu, list entries %llu, records rebuilt %llu\n", ctrl[CTRL_STATUS], ctrl[CTRL_MERGES], R, ctrl[CTRL_EDGES], ctrl[CTRL_ENTRIES], base.rebuilt_last);      // (rebuilt: by the baseline or hand-over in front of this launch)
+    base.rebuilt_last = 0;
     if (ctrl[CTRL_STATUS] == ST_DONE) break;
     switch (ctrl[CTRL_STATUS]) {
       case ST_RUN:                              // max_iters reached: the tree kernel goes on from its state, the window queue re-baselines
@@ -526,8 +596,17 @@ static int run_pb_loop(const RagArrays& rag, hipStream_t stream, const PbRequest
         if (!window) return unhandled();
         entries.remove(&ws.fpool);
         edges.remove(&ws.er);
+        edges.remove(&ws.ecat);
         if ((rc = entries.add(buf, &st.pool, st.pool_cap, stream))) return rc;
         hipLaunchKernelGGL(fat_to_thin, dim3((unsigned)((ctrl[CTRL_ENTRIES] + 255) / 256)), dim3(256), 0, stream, ws.fpool, st.pool, ctrl[CTRL_ENTRIES]);
+        if (base.from_lists) {
+          // the batch kernel's edges below the horizon have no records yet: the collection pass of a baseline rebuilds those of the
+          // live ones and lists every live edge; the rest of the leaves are dead
+          uint32_t n_live = 0;
+          if ((rc = base.collect(ws, (uint32_t)ctrl[CTRL_EDGES], R + (uint32_t)ctrl[CTRL_MERGES], stream, &n_live))) return rc;
+          hipLaunchKernelGGL(fill_leaves_dead, dim3((st.Ecap + 255) / 256), dim3(256), 0, stream, st.pq, 0u);
+          if (n_live) hipLaunchKernelGGL(edge_unpack_live, dim3((n_live + 255) / 256), dim3(256), 0, stream, st, ws.er, base.vals, n_live);
+        } else
         hipLaunchKernelGGL(edge_unpack, dim3((unsigned)((ctrl[CTRL_EDGES] + 255) / 256)), dim3(256), 0, stream, st, ws.er, ws.rdead, (uint32_t)ctrl[CTRL_EDGES]);
         GLIA_HIP_TRY(hipGetLastError());
         if ((rc = pq_setup(buf, st.pq, stream))) return rc;

@@ -7,6 +7,8 @@
 //   * b.kill[] / b.nkill are filled by committing waves in front of the commit barrier and consumed (then cleared by thread 0)
 //     behind the scan's closing barrier; a kill that matches no window item is harmless.
 //   * Below the horizon (WinState::wch) an edge is neither queued nor counted nor marked dead: WinState::rdead speaks for it.
+//     It has no record either (store_new_edge<true>): a record exists iff the edge was created at or above the horizon, or has
+//     been through a baseline.  Both callers of store_new_edge here go through BATCH = true: the commit and batch_contract_wide.
 #pragma once
 #include "greedy_window.hpp"
 
@@ -200,6 +202,7 @@ __device__ __forceinline__ void batch_scan(const WinState& st, WinShared& w, Bat
 
 #ifdef GLIA_HMT_PROFILE
 __device__ unsigned long long g_wideprof[8];
+__device__ unsigned long long g_edgeprof[3][2];           // created edges (narrow commit / wide on the LDS table / wide on the global marks) x (at or above the horizon / below it), cumulative
 #define WIDE_T(i) do { if (tid == 0) { const unsigned long long tn_ = __builtin_readcyclecounter(); g_wideprof[i] += tn_ - wt_; wt_ = tn_; } } while (0)
 #else
 #define WIDE_T(i) do {} while (0)
@@ -238,6 +241,9 @@ __device__ __forceinline__ uint32_t batch_contract_wide(const WinState& st, WinS
   const uint32_t lenR2 = small ? nwork : 0u;        // small case: every table item becomes exactly one new edge, so r2's list length is known here
   bool bad = false;
   uint32_t pend_e = kNone, pend_old = kNone;
+#ifdef GLIA_HMT_PROFILE
+  uint32_t ep_above = 0, ep_below = 0;
+#endif
   // Two instances of the loop: the LDS-table case must not share code with the one that loads from global memory -- where
   // the two meet the compiler waits for "every memory operation", and that counter includes the stores of earlier rounds.
   auto rounds = [&](auto small_tag) {
@@ -258,8 +264,12 @@ __device__ __forceinline__ uint32_t batch_contract_wide(const WinState& st, WinS
       if (h0 && h1) st.fpool[offRs + f1.pos].eid = kNone;
       const unsigned long long seq = update_seq(k, rs, r0, h0);
       const double sal = -first;
-      store_new_edge(st, newE, rs, r2, posRs, idx, first, second, sal, seq, offRs, lenRs, r2off, lenR2);      // (wide case: r2's length is stored below)
-      win_queue_edge<true>(st, w, tau, newE, sal, seq, rs, r2, make_uint2(offRs, lenRs), make_uint2(r2off, lenR2), pend_e, pend_old);
+      const uint32_t cell = win_cell(sal, tau.smin, tau.scale, st.wB);
+#ifdef GLIA_HMT_PROFILE
+      if (cell < st.wch) ++ep_below; else ++ep_above;
+#endif
+      store_new_edge<true>(st, newE, rs, r2, posRs, idx, first, second, sal, seq, offRs, lenRs, r2off, lenR2, cell);      // (wide case: r2's length is stored below)
+      win_queue_edge<true>(st, w, tau, newE, sal, seq, rs, r2, make_uint2(offRs, lenRs), make_uint2(r2off, lenR2), cell, pend_e, pend_old);
       if (h0) win_retire_edge<true, false, kBatchKill>(st, tau, f0.eid, -f0.mean, &b.nkill, b.kill, &b.kovf);
       if (h1) win_retire_edge<true, false, kBatchKill>(st, tau, f1.eid, -f1.mean, &b.nkill, b.kill, &b.kovf);
     }
@@ -270,12 +280,16 @@ __device__ __forceinline__ uint32_t batch_contract_wide(const WinState& st, WinS
   if (small) lds_barrier(); else full_barrier();      // (wide case: r2's new list entries are read back below, by other threads than wrote them)   // [B:wide-build]
   WIDE_T(4);
   const uint32_t newcount = s.newcount;   // [R:newcount]
-  if (!small) win_complete_r2(st, tid, (uint32_t)ne, r2off, newcount);
+  if (!small) win_complete_r2<true>(st, tid, (uint32_t)ne, r2off, newcount, smin, scale);
   if (!small) for (uint32_t i = tid; i < (w.n < st.wcap ? w.n : st.wcap); i += kGreedyThreads) if (w.v[i] == r2) w.hv[i].y = newcount;      // window items of r2: its list length
   if (pend_e != kNone) st.er[pend_e].next = pend_old;
   if (tid == 0) { st.adj_off[r2] = r2off; st.adj_len[r2] = newcount; }
   lds_barrier();                   // (the scan that follows ends with the full barrier)   // [B:wide-end]
   WIDE_T(5);
+#ifdef GLIA_HMT_PROFILE
+  if (ep_above) atomicAdd(&g_edgeprof[small ? 1 : 2][0], (unsigned long long)ep_above);
+  if (ep_below) atomicAdd(&g_edgeprof[small ? 1 : 2][1], (unsigned long long)ep_below);
+#endif
   if (tid == 0) { s.nitems = 0; s.newcount = 0; }   // [W:wide-clear]
   *newcount_out = newcount;
   return total;
@@ -307,6 +321,7 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_batch_kernel(WinState s
 #ifdef GLIA_HMT_PROFILE
   unsigned long long bph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, blast = __builtin_readcyclecounter(), brounds = 0, bmembers = 0, bvalid = 0, bwide = 0, bcut_sal = 0, bcut_dep = 0;
   unsigned long long bw_n[4] = {0, 0, 0, 0}, bw_cyc[4] = {0, 0, 0, 0}, bw_ent[4] = {0, 0, 0, 0}, bw_new[4] = {0, 0, 0, 0};
+  uint32_t bep_above = 0, bep_below = 0;                        // (per thread) edges this thread's commits created at or above / below the horizon
   unsigned long long bsel[2] = {0, 0}, bsel_n[2] = {0, 0};      // loop-top cycles (the select bucket, BPH(0)) of narrow rounds / wide pops, and their number
 #define BPH0(wide) do { if (tid == 0) { unsigned long long tn = __builtin_readcyclecounter(); bph[0] += tn - blast; bsel[wide] += tn - blast; bsel_n[wide] += 1; blast = tn; } } while (0)
 #define BPH(i) do { if (tid == 0) { unsigned long long tn = __builtin_readcyclecounter(); bph[i] += tn - blast; blast = tn; } } while (0)
@@ -513,8 +528,12 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_batch_kernel(WinState s
         if (both[p]) st.fpool[offRs + p_pos[p]].eid = kNone;             // rs held two entries: the other becomes a tombstone
         const unsigned long long seq = update_seq(kk, rs, r0, h0);
         const double sal = -first[p];
-        store_new_edge(st, newE, rs, r2, posRs, idx[p], first[p], second[p], sal, seq, offRs, lenRs, r2off, newcount);
-        win_queue_edge<true>(st, w, tau, newE, sal, seq, rs, r2, make_uint2(offRs, lenRs), make_uint2(r2off, newcount), pend_e, pend_old);
+        const uint32_t cell = win_cell(sal, tau.smin, tau.scale, st.wB);
+#ifdef GLIA_HMT_PROFILE
+        if (cell < st.wch) ++bep_below; else ++bep_above;
+#endif
+        store_new_edge<true>(st, newE, rs, r2, posRs, idx[p], first[p], second[p], sal, seq, offRs, lenRs, r2off, newcount, cell);
+        win_queue_edge<true>(st, w, tau, newE, sal, seq, rs, r2, make_uint2(offRs, lenRs), make_uint2(r2off, newcount), cell, pend_e, pend_old);
         // the replaced edges leave the queue: this lane's entry, and the (r1,rs) entry that waited in the table for it
         win_retire_edge<true, false, kBatchKill>(st, tau, fe[p].eid, -fe[p].mean, &b.nkill, b.kill, &b.kovf);
         if (both[p]) win_retire_edge<true, false, kBatchKill>(st, tau, p_eid[p], -p_mean[p], &b.nkill, b.kill, &b.kovf);
@@ -531,6 +550,12 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_batch_kernel(WinState s
     BPH(4);
   }
 #ifdef GLIA_HMT_PROFILE
+  if (bep_above) atomicAdd(&g_edgeprof[0][0], (unsigned long long)bep_above);
+  if (bep_below) atomicAdd(&g_edgeprof[0][1], (unsigned long long)bep_below);
+  full_barrier();
+  if (tid == 0) printf("[batch profile] created edges at or above / below the horizon (cumulative): narrow commit %llu / %llu  wide on the LDS table %llu / %llu  wide on the global marks %llu / %llu\n",
+                       atomicAdd(&g_edgeprof[0][0], 0ull), atomicAdd(&g_edgeprof[0][1], 0ull), atomicAdd(&g_edgeprof[1][0], 0ull), atomicAdd(&g_edgeprof[1][1], 0ull),
+                       atomicAdd(&g_edgeprof[2][0], 0ull), atomicAdd(&g_edgeprof[2][1], 0ull));
   if (tid == 0) printf("[batch profile] merges %llu: select %llu  compute %llu  validate %llu  commit %llu  scan %llu  loop-top %llu  reload %llu (cycles); rounds %llu candidates %llu committed %llu (cut by saliency %llu, by adjacency %llu) wide %llu\n",
                        k, bph[0], bph[1], bph[2], bph[3], bph[4], bph[5], bph[6], brounds, bmembers, bvalid, bcut_sal, bcut_dep, bwide);
   if (tid == 0) printf("[batch profile] scan phases (cumulative cycles, wave 0): loads %llu  compare %llu  top2 %llu  top2 with a tied best %llu  barrier %llu  calls %llu  tied second %llu  tied best %llu\n",

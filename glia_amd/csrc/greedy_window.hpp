@@ -10,26 +10,17 @@
 //   * Cell counts (wcnt) are upper bounds of the live items of a cell below tau: a reload walks a list whenever its count is not
 //     zero and resets a count that turns out too high; the batch paths never discount a tie with tau (win_retire_edge).
 //   * Global stores of a contraction are fire-and-forget; whoever reads them from another wave does so behind a full_barrier().
+//   * A record exists iff the edge was created at or above the horizon, or has been through a baseline (edge_record.hpp): the batch
+//     kernel writes none for an edge below the horizon (store_new_edge<true>), and nothing reads one before the next baseline -- the
+//     kovf look-up and win_take only see window or list items, which lie at or above the horizon; win_take_initial only sees baseline
+//     members.  Record slots of such edges that die are never touched.
 //   * k / ne / pool_used are private copies in every thread (see greedy_tree.hpp); s.newcount is read by all behind a barrier and
 //     cleared by thread 0 only behind the next one.  Audit table: DESIGN 3.3; tags [B:..] barrier, [R:..] read, [W:..] rewrite.
 #pragma once
 #include "greedy_tree.hpp"
+#include "edge_record.hpp"       // FatEntry (list entry), EdgeRec (edge record) and the rule that rebuilds the one from the other
 
 namespace glia {
-
-// An incident-edge list entry of the window kernel: everything a contraction needs from the edge and from the
-// neighbour, so that one 32-byte load replaces the second dependent round trip (edge record, neighbour's list offset).
-// All of it is immutable for the lifetime of the edge / region.
-struct __attribute__((aligned(16))) FatEntry {
-  uint32_t eid;      // edge slot, kNone = tombstone
-  uint32_t rs;       // the neighbour this entry leads to
-  uint32_t n;        // boundary voxels of the edge
-  uint32_t pos;      // position of the edge's other entry, in rs's list
-  uint32_t off;      // adj_off[rs]
-  uint32_t len;      // adj_len[rs]
-  double mean;       // boundary mean of the edge
-};
-
 namespace {
 
 // =====================================================================================================================
@@ -59,15 +50,10 @@ namespace {
 // With the fat list entries (FatEntry) and the list headers carried in the window a contraction is ONE dependent global
 // round trip -- the two incident-edge lists -- plus LDS work; its stores are fire-and-forget: the next contraction only
 // waits for them when it touches a region whose list they rewrite (a bitmap of the touched regions decides).
-// Edge state is one 64-byte record (EdgeRec) instead of twelve arrays: four wide stores per new edge, one base pointer.
+// Edge state is one 64-byte record (EdgeRec, edge_record.hpp) instead of twelve arrays: four wide stores per new edge, one base
+// pointer -- and none at all for an edge the batch kernel creates below its horizon (see WinState::wch).
 // =====================================================================================================================
-struct __attribute__((aligned(16))) EdgeRec {
-  uint32_t u, v, posu, posv;                // regions (u < v) and the positions of the edge's entries in their lists
-  double mean; int n; uint32_t next;        // linkage data; link of the cell list
-  uint2 hu, hv;                             // (offset, length) of u's and v's incident-edge lists
-  double sal; unsigned long long seq;       // queue key; seq == 0: not in the queue
-};
-static_assert(sizeof(EdgeRec) == 64, "EdgeRec layout");
+static_assert(kRecNone == kNone, "edge_record.hpp");
 struct WinState {
   EdgeRec* er; FatEntry* fpool;
   uint32_t* whead;                          // [wB] newest created edge of the cell's list (kNone = empty); atomics only
@@ -86,9 +72,10 @@ struct WinState {
   uint32_t wcap, wbudget;                   // window slots in use (<= kWinCap) and the items a reload brings at most (tests shrink them: GLIA_HMT_WINCAP)
   int cond_n;
   // HORIZON (batch kernel): cells below wch are out of the queue's reach until the next baseline.  An edge created there is
-  // neither linked into its cell's list nor counted, an edge dying there is not counted either: its record and its two list
-  // entries are all that is written (the baseline is rebuilt from the records).  A reload that would have to go below the
-  // horizon ends the launch with ST_REBASE instead.  0 = no horizon.
+  // neither linked into its cell's list nor counted, an edge dying there is not counted either: its two list entries and the
+  // two cat bits of its seq (ecat) are all that is written -- no record; the baseline walks the lists of the live regions and
+  // rebuilds the records of the edges that are still alive.  A reload that would have to go below the horizon ends the launch
+  // with ST_REBASE instead.  0 = no horizon.
   uint32_t wch;
   // regions that have been merged away (batch kernel).  An edge that dies BELOW the horizon is not marked in its record (one
   // scattered store per dying edge less in the contraction's store stream): no reload can reach it before the next baseline,
@@ -97,6 +84,7 @@ struct WinState {
   // tests (GLIA_HMT_FORCE_TREE=k): hand the queue over to the tournament-tree kernel at the first empty window after k merges --
   // the path of ST_NEED_TREE, which no data set reaches by itself any more (oversized cells are split)
   unsigned long long force_tree;
+  uint8_t* ecat;                            // [Ecap] cat bits of the seq of an edge created below the horizon (update_seq); grows with the records
 };
 constexpr uint32_t kWinCap = 1536;          // window slots (live items + holes)
 constexpr uint32_t kWinBudget = 768;        // a reload stops before exceeding this many items ...
@@ -477,16 +465,22 @@ __device__ __forceinline__ bool win_match(const WinState& st, WinWork& s, uint32
   return true;
 }
 // The new edge newE = (rs, r2): its record (four 16-byte stores), rs's reused list entry and r2's new one.  lenR2 = 0: r2's list
-// length is not known yet, the caller completes the headers (win_complete_r2).
+// length is not known yet, the caller completes the headers (win_complete_r2).  cell = win_cell(sal).
+// BATCH = true and cell below the horizon: no record (nobody reads it before the next baseline, which rebuilds it from r2's entry if
+// the edge is still alive then: rebuild_edge_record) -- the two entries and the cat bits of the seq, one byte, are all that is stored.
+template <bool BATCH>
 __device__ __forceinline__ void store_new_edge(const WinState& st, uint32_t newE, uint32_t rs, uint32_t r2, uint32_t posRs, uint32_t idx, double first, int second,
-                                               double sal, unsigned long long seq, uint32_t offRs, uint32_t lenRs, uint32_t r2off, uint32_t lenR2) {
-  uint4* pq4 = reinterpret_cast<uint4*>(&st.er[newE]);
-  pq4[0] = make_uint4(rs, r2, posRs, idx);
-  const unsigned long long mb = (unsigned long long)__double_as_longlong(first);
-  pq4[1] = make_uint4((uint32_t)mb, (uint32_t)(mb >> 32), (uint32_t)second, kNone);
-  pq4[2] = make_uint4(offRs, lenRs, r2off, lenR2);
-  const unsigned long long sbits = (unsigned long long)__double_as_longlong(sal);
-  pq4[3] = make_uint4((uint32_t)sbits, (uint32_t)(sbits >> 32), (uint32_t)seq, (uint32_t)(seq >> 32));
+                                               double sal, unsigned long long seq, uint32_t offRs, uint32_t lenRs, uint32_t r2off, uint32_t lenR2, uint32_t cell) {
+  if (BATCH && cell < st.wch) st.ecat[newE] = (uint8_t)((uint32_t)(seq >> 30) & 3u);
+  else {
+    uint4* pq4 = reinterpret_cast<uint4*>(&st.er[newE]);
+    pq4[0] = make_uint4(rs, r2, posRs, idx);
+    const unsigned long long mb = (unsigned long long)__double_as_longlong(first);
+    pq4[1] = make_uint4((uint32_t)mb, (uint32_t)(mb >> 32), (uint32_t)second, kNone);
+    pq4[2] = make_uint4(offRs, lenRs, r2off, lenR2);
+    const unsigned long long sbits = (unsigned long long)__double_as_longlong(sal);
+    pq4[3] = make_uint4((uint32_t)sbits, (uint32_t)(sbits >> 32), (uint32_t)seq, (uint32_t)(seq >> 32));
+  }
   FatEntry a; a.eid = newE; a.rs = r2; a.n = (uint32_t)second; a.pos = idx; a.off = r2off; a.len = lenR2; a.mean = first;
   st.fpool[offRs + posRs] = a;
   FatEntry b; b.eid = newE; b.rs = rs; b.n = (uint32_t)second; b.pos = posRs; b.off = offRs; b.len = lenRs; b.mean = first;
@@ -496,11 +490,11 @@ __device__ __forceinline__ void store_new_edge(const WinState& st, uint32_t newE
 // NEXT push or after its loop (pend_e / pend_old: nobody waits for the atomic).
 // BATCH = false (one-at-a-time kernel): the caller has made room beforehand (compaction / flush), so every slot number is valid, and
 //   there is no horizon.  BATCH = true: a full window spills the item to its list and raises w.spill_ord (win_evict follows), and an
-//   item below the horizon st.wch is not queued at all.
+//   item below the horizon st.wch is not queued at all (it has no record either: an item above tau is never below the horizon --
+//   tau's cell is at least wch - 1, and there only with tsal = +inf).  cell = win_cell(sal), shared with store_new_edge.
 template <bool BATCH>
 __device__ __forceinline__ void win_queue_edge(const WinState& st, WinShared& w, const WinTau& tau, uint32_t newE, double sal, unsigned long long seq, uint32_t rs, uint32_t r2,
-                                               uint2 hrs, uint2 hr2, uint32_t& pend_e, uint32_t& pend_old) {
-  const uint32_t cell = win_cell(sal, tau.smin, tau.scale, st.wB);
+                                               uint2 hrs, uint2 hr2, uint32_t cell, uint32_t& pend_e, uint32_t& pend_old) {
   const bool above = win_above(tau.cthr, tau.tsal, tau.tseq, (int)cell, sal, seq);
   uint32_t sl = kWinCap;
   if (above) {
@@ -536,11 +530,13 @@ __device__ __forceinline__ void win_retire_edge(const WinState& st, const WinTau
   } else atomicSub(&st.wcnt[dc], 1u);
 }
 // r2's list length is known only after a contraction on the global marks: complete the headers that point at it and clear the marks
-__device__ __forceinline__ void win_complete_r2(const WinState& st, int tid, uint32_t ne, uint32_t r2off, uint32_t newcount) {
+// (BATCH: an edge below the horizon has no record to complete -- store_new_edge's predicate on the entry's mean)
+template <bool BATCH>
+__device__ __forceinline__ void win_complete_r2(const WinState& st, int tid, uint32_t ne, uint32_t r2off, uint32_t newcount, double smin, double scale) {
   for (uint32_t j = tid; j < newcount; j += kGreedyThreads) {
     const FatEntry fb = st.fpool[r2off + j];
     st.fpool[fb.off + fb.pos].len = newcount;
-    st.er[ne + j].hv.y = newcount;
+    if (!BATCH || win_cell(-fb.mean, smin, scale, st.wB) >= st.wch) st.er[ne + j].hv.y = newcount;
     st.mark0[fb.rs] = 0; st.mark1[fb.rs] = 0;
   }
 }
@@ -699,9 +695,10 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_window_kernel(WinState 
       if (h0 && h1) st.fpool[offRs + f1.pos].eid = kNone; // rs held two entries: the other becomes a tombstone
       const unsigned long long seq = update_seq(k, rs, r0, h0);
       const double sal = -first;
-      store_new_edge(st, newE, rs, r2, posRs, idx, first, second, sal, seq, offRs, lenRs, r2off, 0u);
+      const uint32_t cell = win_cell(sal, tau.smin, tau.scale, st.wB);
+      store_new_edge<false>(st, newE, rs, r2, posRs, idx, first, second, sal, seq, offRs, lenRs, r2off, 0u, cell);
       if (small) { s.items[i] = offRs + posRs; s.newidx[i] = idx; }      // (this thread comes back to them below)
-      win_queue_edge<false>(st, w, tau, newE, sal, seq, rs, r2, make_uint2(offRs, lenRs), make_uint2(r2off, 0u), pend_e, pend_old);
+      win_queue_edge<false>(st, w, tau, newE, sal, seq, rs, r2, make_uint2(offRs, lenRs), make_uint2(r2off, 0u), cell, pend_e, pend_old);
       // the replaced edges leave the queue
       if (h0) win_retire_edge<false, COND, kKillMax>(st, tau, f0.eid, -f0.mean, &w.nk, w.kill, &w.kovf);
       if (h1) win_retire_edge<false, COND, kKillMax>(st, tau, f1.eid, -f1.mean, &w.nk, w.kill, &w.kovf);
@@ -715,7 +712,7 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_window_kernel(WinState 
     if (small) {
       for (uint32_t i = tid; i < nwork; i += kGreedyThreads) { st.fpool[s.items[i]].len = newcount; st.er[(uint32_t)ne + s.newidx[i]].hv.y = newcount; }
     } else {
-      win_complete_r2(st, tid, (uint32_t)ne, r2off, newcount);
+      win_complete_r2<false>(st, tid, (uint32_t)ne, r2off, newcount, smin, scale);
     }
     // Every wave has to have READ s.newcount (above) before thread 0 clears it for the next contraction.  Rounds 2-3 cleared it here
     // without a barrier in between: a wave that came out of the last barrier a few hundred cycles late read 0, completed its headers
