@@ -1,7 +1,9 @@
 """-m gpu: watershed over-segmentation (gadget/main_watershed.cxx, util/image_alg.hxx:9-21), the step before the RAG.
 ITK (MorphologicalWatershedImageFilter) is not in this image: parity with it is UNPINNED.  The device code and the oracle's
 sequential restatement (worklist reconstruction, breadth-first plateaus, Dijkstra flooding) implement the same order-free tie
-rules by different algorithms and must give identical label volumes."""
+rules by different algorithms and must give identical label volumes.  The oracle is not the sole reference: it is pinned to
+closed-form answers in tests/test_oracle_watershed.py, and tests/test_gpu_watershed_edges.py compares the device code with those
+answers directly (and drives the tile iteration caps, the dirty lists and the union-find, which the smooth noise here never does)."""
 import os
 import subprocess
 
