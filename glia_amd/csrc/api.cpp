@@ -880,6 +880,53 @@ void glia_hmt_forest_free(glia_hmt_forest* f) {
   delete f;
 }
 
+// ---- batch prediction (forest_predict.hip) ----
+static int check_predict_args(const char* who, const glia_hmt_ctx* c, const glia_hmt_forest* f, const void* rows, int64_t n_rows, int dim,
+                              int64_t row_stride, const void* pred) {
+  if (!c || !f) { set_error(std::string(who) + ": NULL context or forest"); return GLIA_HMT_ERR_ARG; }
+  if (n_rows < 0 || dim < 1 || row_stride < dim || (n_rows > 0 && (!rows || !pred))) { set_error(std::string(who) + ": invalid argument"); return GLIA_HMT_ERR_ARG; }
+  if (dim <= f->max_var) {
+    set_error(std::string(who) + ": rows of " + std::to_string(dim) + " columns, but the classifier reads column " + std::to_string(f->max_var));
+    return GLIA_HMT_ERR_ARG;
+  }
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_forest_predict_tile_rows(int64_t n_rows, int dim) {
+  if (n_rows < 0 || dim < 1) { set_error("forest_predict_tile_rows: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  return forest_predict_tile_rows(n_rows, dim);
+}
+
+int glia_hmt_forest_predict_device(glia_hmt_ctx* c, const glia_hmt_forest* f, const double* d_rows, int64_t n_rows, int dim, int64_t row_stride,
+                                   double* d_pred) {
+  const int rc = check_predict_args("forest_predict_device", c, f, d_rows, n_rows, dim, row_stride, d_pred);
+  if (rc || n_rows == 0) return rc;
+  GLIA_HIP_TRY(hipSetDevice(c->device));
+  return launch_forest_predict(f->dc, d_rows, n_rows, dim, row_stride, d_pred, c->stream);
+}
+
+int glia_hmt_forest_predict(glia_hmt_ctx* c, const glia_hmt_forest* f, const double* h_rows, int64_t n_rows, int dim, double* h_pred) {
+  int rc = check_predict_args("forest_predict", c, f, h_rows, n_rows, dim, dim, h_pred);
+  if (rc || n_rows == 0) return rc;
+  GLIA_HIP_TRY(hipSetDevice(c->device));
+  // rows stream through device buffers of at most 128 MiB (GLIA_HMT_MINCAP: 256 rows, so that tests cross chunk boundaries)
+  const int64_t chunk = std::min<int64_t>(n_rows, option("GLIA_HMT_MINCAP") ? 256 : std::max<int64_t>(1, (int64_t)(1 << 24) / dim));
+  double *d_rows = nullptr, *d_pred = nullptr;
+  GLIA_HIP_TRY(hipMalloc(&d_rows, sizeof(double) * (size_t)chunk * dim));
+  hipError_t e = hipMalloc(&d_pred, sizeof(double) * (size_t)chunk);
+  for (int64_t r0 = 0; e == hipSuccess && rc == GLIA_HMT_OK && r0 < n_rows; r0 += chunk) {
+    const int64_t n = std::min(chunk, n_rows - r0);
+    e = hipMemcpyAsync(d_rows, h_rows + r0 * dim, sizeof(double) * (size_t)n * dim, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) rc = launch_forest_predict(f->dc, d_rows, n, dim, dim, d_pred, c->stream);
+    if (e == hipSuccess && rc == GLIA_HMT_OK) e = hipMemcpyAsync(h_pred + r0, d_pred, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  }
+  (void)hipFree(d_rows);
+  if (d_pred) (void)hipFree(d_pred);
+  if (e != hipSuccess) { set_error(std::string("forest_predict: ") + hipGetErrorString(e)); return GLIA_HMT_ERR_HIP; }
+  return rc;
+}
+
 static inline double sdivide_host(double l, double r) { return std::fabs(r) >= 2.22e-16 ? l / r : 0.0; }   // glia_base.hxx:77-78
 
 static bool make_bc_cfg(const glia_hmt_rag* rag, BcCfg* c) {

@@ -54,6 +54,11 @@ struct DeviceClassifier {
 };
 
 int load_forest_file(const char* path, int predict_label, HostForest* out);
+// forest_predict.hip: pred[i] = the classifier's value for row i (device arrays; row i starts at d_rows + i * row_stride)
+// rows of the LDS tile the kernel takes for this input (64, 32, 16 or 8); 0: rows of `dim` columns are walked from global memory
+int forest_predict_tile_rows(long long n_rows, int dim);
+int launch_forest_predict(const DeviceClassifier& clf, const double* d_rows, long long n_rows, int dim, long long row_stride, double* d_pred,
+                          hipStream_t stream);
 
 }  // namespace glia
 

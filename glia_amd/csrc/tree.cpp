@@ -4,7 +4,10 @@
 // 76-152 (pickTreeNode / resolveTreeGreedy with comp = potential <), hmt/tree_segment.hxx:10-21 (genLabelTransform),
 // hmt/main_segment_greedy.cxx:33-86.  The reference re-scans every node for each pick (O(n^2)); here the same pick
 // sequence comes out of a heap ordered by (potential descending, node index ascending) with lazy invalidation.
+// The tree inference of segment_ccm (hmt/main_segment_ccm.cxx:39-53,76-92, hmt/tree_ccm.hxx:12-115) follows at the end: node energies and
+// energy tuples, the top-down resolution, and the per-node confidence of its -b image, with every sum in the reference's order.
 #include <algorithm>
+#include <cmath>
 #include <limits>
 #include <queue>
 #include <unordered_map>
@@ -99,6 +102,20 @@ int boundary_confidence_values(int n_trees, const int64_t* n_nodes, const uint32
 }
 
 }  // namespace glia
+
+// segment_ccm: the saturating sum and the node energy
+namespace {
+constexpr double kFmax = std::numeric_limits<double>::max();   // FMAX (glia_base.hxx:59)
+constexpr double kFeps = 2.22e-16;                             // FEPS (:57)
+// stats::plusEqual (util/stats.hxx:9-17): FMAX and -FMAX absorb what has their sign or is zero
+inline double& plus_equal(double& l, const double r) {
+  if ((l == kFmax && r >= 0.0) || (l >= 0.0 && r == kFmax)) l = kFmax;
+  else if ((l == -kFmax && r <= 0.0) || (l <= 0.0 && r == -kFmax)) l = -kFmax;
+  else l += r;
+  return l;
+}
+inline double energy_of(const double p) { return std::fabs(p - 0.0) < kFeps ? kFmax : -std::log(p); }   // isfeq(p, 0.0) ? FMAX : -log(p)
+}  // namespace
 
 extern "C" {
 
@@ -245,6 +262,90 @@ int64_t glia_hmt_label_transform(const uint32_t* node_label, const int32_t* chil
     ++key_to_assign;
   }
   return m;
+}
+
+// ---- segment_ccm ----
+
+int64_t glia_hmt_tree_energies(const uint32_t* h_order, int64_t n_merges, const double* h_merge_probs, uint32_t* node_label,
+                               int32_t* parent, int32_t* child0, int32_t* child1, double* em, double* es, double* Em, double* Es,
+                               int64_t capacity) {
+  if (!h_order || !node_label || !parent || !child0 || !child1 || !em || !es || !Em || !Es || n_merges < 0 || (n_merges > 0 && !h_merge_probs)) {
+    set_error("tree_energies: invalid argument");
+    return GLIA_HMT_ERR_ARG;
+  }
+  const int64_t n = glia_hmt_gen_tree(h_order, n_merges, node_label, parent, child0, child1, capacity);
+  if (n < 0) return n;
+  int64_t mi = 0;
+  for (int64_t i = 0; i < n; ++i) {                               // genTree's callbacks come in node order
+    if (child0[i] < 0) { em[i] = 0.0; es[i] = kFmax; }
+    else { const double p = h_merge_probs[mi++]; em[i] = energy_of(p); es[i] = energy_of(1.0 - p); }
+  }
+  const int rc = glia_hmt_tree_energy_tuples(child0, child1, em, es, n, Em, Es);
+  return rc ? rc : n;
+}
+
+int glia_hmt_tree_energy_tuples(const int32_t* child0, const int32_t* child1, const double* em, const double* es, int64_t n_nodes,
+                                double* Em, double* Es) {
+  if (!child0 || !child1 || !em || !es || !Em || !Es || n_nodes < 0) { set_error("tree_energy_tuples: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  for (int64_t i = 0; i < n_nodes; ++i) {                         // children have smaller indices than their parent
+    Em[i] = em[i]; Es[i] = es[i];
+    if (child0[i] < 0) continue;
+    for (int32_t c : {child0[i], child1[i]}) {
+      if (c < 0 || c >= i) { set_error("tree_energy_tuples: a child does not precede its parent"); return GLIA_HMT_ERR_ARG; }
+      plus_equal(Em[i], Em[c]); plus_equal(Es[i], std::min(Em[c], Es[c]));
+    }
+  }
+  return GLIA_HMT_OK;
+}
+
+int64_t glia_hmt_resolve_tree_ccm(const int32_t* child0, const int32_t* child1, const double* Em, const double* Es, int64_t n_nodes,
+                                  int32_t* h_picks, int64_t capacity) {
+  if (!child0 || !child1 || !Em || !Es || !h_picks || n_nodes < 0) { set_error("resolve_tree_ccm: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  if (n_nodes == 0) return 0;
+  std::vector<int32_t> queue(1, (int32_t)(n_nodes - 1));          // root() = the last node (type/tree.hxx:100)
+  int64_t np = 0;
+  for (size_t q = 0; q < queue.size(); ++q) {
+    const int32_t i = queue[q];
+    if (i < 0 || i >= n_nodes || (int64_t)queue.size() > n_nodes) { set_error("resolve_tree_ccm: malformed tree"); return GLIA_HMT_ERR_ARG; }
+    if (Em[i] < Es[i]) {
+      if (np >= capacity) { set_error("resolve_tree_ccm: output capacity too small"); return GLIA_HMT_ERR_CAPACITY; }
+      h_picks[np++] = i;
+    } else if (child0[i] >= 0) { queue.push_back(child0[i]); queue.push_back(child1[i]); }
+  }
+  return np;
+}
+
+int glia_hmt_tree_ccm_confidence(const int32_t* parent, const int32_t* child0, const int32_t* child1, const double* es, const double* Em,
+                                 const double* Es, int64_t n_nodes, double* pos, double* neg, double* confidence) {
+  if (!parent || !child0 || !child1 || !es || !Em || !Es || !confidence || n_nodes < 0) { set_error("tree_ccm_confidence: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  // what both energies add on the way up (tree_ccm.hxx:68-80 = :101-113): es of each ancestor, then min(Em, Es) of its other children
+  auto ancestors = [&](int64_t i, double& ret) {
+    int32_t prev = (int32_t)i;
+    for (int32_t a = parent[i]; a >= 0; a = parent[a]) {
+      plus_equal(ret, es[a]);
+      for (int32_t c : {child0[a], child1[a]}) if (c != prev) plus_equal(ret, std::min(Em[c], Es[c]));
+      prev = a;
+    }
+  };
+  std::vector<int32_t> queue;
+  for (int64_t i = 0; i < n_nodes; ++i) {
+    double p = Em[i];                                             // all descendants merge
+    ancestors(i, p);
+    double q = es[i];                                             // the first merging descendants, breadth-first
+    queue.clear();
+    if (child0[i] >= 0) { queue.push_back(child0[i]); queue.push_back(child1[i]); }
+    for (size_t k = 0; k < queue.size(); ++k) {
+      const int32_t j = queue[k];
+      if (Em[j] < Es[j]) plus_equal(q, Em[j]);
+      else if (child0[j] >= 0) { queue.push_back(child0[j]); queue.push_back(child1[j]); }
+    }
+    ancestors(i, q);
+    if (pos) pos[i] = p;
+    if (neg) neg[i] = q;
+    double sum = q;
+    confidence[i] = p / plus_equal(sum, p);
+  }
+  return GLIA_HMT_OK;
 }
 
 }  // extern "C"

@@ -13,6 +13,15 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("GLIA_HMT_LIB", os.path.join(_HERE, "libglia_hmt.so"))   # override: kernel experiments only
 
 MAX_IMAGES, MAX_BINS, MAX_THRESH = 8, 16, 4
+PREDICT_STAGE_MAX_DIM = 767      # GLIA_HMT_PREDICT_STAGE_MAX_DIM: longer rows are walked from global memory (pinned to the library by the GPU tests)
+
+
+def predict_tile_rows(n_rows, dim):
+    """glia_hmt_forest_predict_tile_rows: rows of the LDS tile RandomForest.predict uses for this input (64, 32, 16, 8), 0 = not staged"""
+    r = lib().glia_hmt_forest_predict_tile_rows(C.c_int64(n_rows), C.c_int(dim))
+    if r < 0:
+        raise HmtError(r, lib().glia_hmt_last_error().decode())
+    return r
 
 
 class HmtError(RuntimeError):
@@ -341,6 +350,53 @@ def label_transform(node_label, child0, child1, picks, key_to_assign=1):
     return _label_transform(lib(), "glia_hmt_", node_label, child0, child1, picks, key_to_assign, _np)
 
 
+def tree_energies(order, merge_probs):
+    """The tree of segment_ccm (hmt/main_segment_ccm.cxx:39-53, hmt/tree_ccm.hxx:12-27) -> (label, parent, child0, child1, em, es, Em, Es):
+    own energies and energy tuples per node."""
+    order = np.ascontiguousarray(order, dtype=np.uint32).reshape(-1, 3)
+    mp = np.ascontiguousarray(merge_probs, dtype=np.float64)
+    assert len(mp) >= len(order)
+    cap = 3 * len(order) + 1
+    lab = np.empty(cap, np.uint32); par = np.empty(cap, np.int32); c0 = np.empty(cap, np.int32); c1 = np.empty(cap, np.int32)
+    e = [np.empty(cap, np.float64) for _ in range(4)]
+    f = lib().glia_hmt_tree_energies; f.restype = C.c_int64
+    n = f(_np(order), C.c_int64(len(order)), _np(mp), _np(lab), _np(par), _np(c0), _np(c1), _np(e[0]), _np(e[1]), _np(e[2]), _np(e[3]), C.c_int64(cap))
+    if n < 0:
+        raise HmtError(int(n), lib().glia_hmt_last_error().decode())
+    return tuple(a[:n].copy() for a in [lab, par, c0, c1] + e)
+
+
+def tree_energy_tuples(child0, child1, em, es):
+    """computeEnergyTuples (hmt/tree_ccm.hxx:12-27) for given own energies -> (Em, Es)."""
+    c0 = np.ascontiguousarray(child0, np.int32); c1 = np.ascontiguousarray(child1, np.int32)
+    em = np.ascontiguousarray(em, np.float64); es = np.ascontiguousarray(es, np.float64)
+    Em = np.empty(max(len(c0), 1), np.float64); Es = np.empty(max(len(c0), 1), np.float64)
+    _check(lib().glia_hmt_tree_energy_tuples(_np(c0), _np(c1), _np(em), _np(es), C.c_int64(len(c0)), _np(Em), _np(Es)))
+    return Em[:len(c0)].copy(), Es[:len(c0)].copy()
+
+
+def resolve_tree_ccm(child0, child1, Em, Es):
+    """resolveFactorTree (hmt/tree_ccm.hxx:31-47): node indices in pick order."""
+    c0 = np.ascontiguousarray(child0, np.int32); c1 = np.ascontiguousarray(child1, np.int32)
+    Em = np.ascontiguousarray(Em, np.float64); Es = np.ascontiguousarray(Es, np.float64)
+    picks = np.empty(max(len(c0), 1), np.int32)
+    f = lib().glia_hmt_resolve_tree_ccm; f.restype = C.c_int64
+    n = f(_np(c0), _np(c1), _np(Em), _np(Es), C.c_int64(len(c0)), _np(picks), C.c_int64(len(picks)))
+    if n < 0:
+        raise HmtError(int(n), lib().glia_hmt_last_error().decode())
+    return picks[:n].copy()
+
+
+def tree_ccm_confidence(parent, child0, child1, es, Em, Es):
+    """The node value of segment_ccm -b (hmt/main_segment_ccm.cxx:76-86, hmt/tree_ccm.hxx:62-115) -> (pos, neg, confidence) per node."""
+    par = np.ascontiguousarray(parent, np.int32); c0 = np.ascontiguousarray(child0, np.int32); c1 = np.ascontiguousarray(child1, np.int32)
+    es = np.ascontiguousarray(es, np.float64); Em = np.ascontiguousarray(Em, np.float64); Es = np.ascontiguousarray(Es, np.float64)
+    out = [np.empty(max(len(par), 1), np.float64) for _ in range(3)]
+    _check(lib().glia_hmt_tree_ccm_confidence(_np(par), _np(c0), _np(c1), _np(es), _np(Em), _np(Es), C.c_int64(len(par)), _np(out[0]), _np(out[1]),
+                                              _np(out[2])))
+    return tuple(a[:len(par)].copy() for a in out)
+
+
 def _resolve_trees(L, prefix, trees, ptr):
     """trees: list of (label, parent, child0, child1, potential)"""
     nt = len(trees)
@@ -370,8 +426,30 @@ class RandomForest:
         arr = (C.c_char_p * len(model_files))(*[m.encode() for m in model_files])
         dist = (C.c_double * 3)(*distributor_args) if distributor_args is not None else None
         self.h = C.c_void_p()
+        self.ctx = ctx
         _check(lib().glia_hmt_forest_load(ctx.h, C.c_int(len(model_files)), arr, C.c_int(predict_label), dist,
                                           C.byref(self.h)))
+
+    def predict(self, rows):
+        """pred_rf (ml/rf/main_pred_rf.cxx:28-38): the classifier's value for every row of an [n, dim] float64 array -- what bc_feat and
+        merge_order_bc(want_feats=True) return.  A NumPy array goes through glia_hmt_forest_predict (rows streamed in chunks) and
+        comes back as NumPy; a CUDA tensor (rows contiguous, any row stride) goes through glia_hmt_forest_predict_device and comes
+        back as a tensor on the same device."""
+        if isinstance(rows, np.ndarray):
+            rows = np.ascontiguousarray(rows, dtype=np.float64)
+            assert rows.ndim == 2
+            out = np.empty(rows.shape[0], np.float64)
+            _check(lib().glia_hmt_forest_predict(self.ctx.h, self.h, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(out)))
+            return out
+        import torch
+        assert rows.is_cuda and rows.dtype == torch.float64 and rows.dim() == 2 and (rows.shape[1] == 0 or rows.stride(1) == 1)
+        assert rows.shape[0] <= 1 or rows.stride(0) >= rows.shape[1]
+        out = torch.empty(rows.shape[0], dtype=torch.float64, device=rows.device)
+        _fence(rows)
+        _check(lib().glia_hmt_forest_predict_device(self.ctx.h, self.h, C.c_void_p(rows.data_ptr()), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]),
+                                                    C.c_int64(rows.stride(0) if rows.shape[0] > 1 else rows.shape[1]), C.c_void_p(out.data_ptr())))
+        self.ctx.sync()
+        return out
 
     def close(self):
         if self.h:
@@ -390,6 +468,7 @@ class FeatureStubClassifier(RandomForest):
 
     def __init__(self, ctx, index):
         self.h = C.c_void_p()
+        self.ctx = ctx
         _check(lib().glia_hmt_forest_stub(ctx.h, C.c_int(index), C.byref(self.h)))
 
 

@@ -267,6 +267,26 @@ int glia_hmt_forest_file_parse(const char* path, int predict_label, int* ntree, 
 int glia_hmt_forest_stub(glia_hmt_ctx* ctx, int feature_index, glia_hmt_forest** out);
 void glia_hmt_forest_free(glia_hmt_forest* forest);
 
+/* Replaces the prediction loop of pred_rf (ml/rf/main_pred_rf.cxx:13-40; alg::RandomForest / EnsembleRandomForest::operator(),
+ * alg/rf.hxx; the model pick of opt::ThresholdModelDistributor, type/function.hxx:71-85) for a batch of feature rows -- what bc_feat -b
+ * and merge_order_bc -b write.  pred[i] = votes for predict_label / ntree of the model the distributor picks for row i (it tests
+ * x[dim1] < threshold first, then x[dim0] < threshold); for a stub classifier 1 - x[index].  The walk goes left iff x[var] <= split, so
+ * a NaN goes right; votes are integers, the results bit-exact.  dim = columns of a row: it must exceed every column the classifier
+ * reads (tree variables, distributor dimensions, stub index), else GLIA_HMT_ERR_ARG.  n_rows == 0 is GLIA_HMT_OK.  Any number of rows:
+ * beyond 2^23 tiles the work takes several launches.
+ * glia_hmt_forest_predict streams host rows through device buffers in bounded chunks and returns when h_pred is written.
+ * glia_hmt_forest_predict_device reads device rows (row i at d_rows + i * row_stride doubles, row_stride >= dim; the padding is never
+ * read) and is ordered on the context's stream like every other call.  Rows of up to GLIA_HMT_PREDICT_STAGE_MAX_DIM columns are staged
+ * in LDS, longer ones are walked from global memory (glia_amd/csrc/forest_predict.hip). */
+#define GLIA_HMT_PREDICT_STAGE_MAX_DIM 767
+int glia_hmt_forest_predict(glia_hmt_ctx* ctx, const glia_hmt_forest* forest, const double* h_rows, int64_t n_rows, int dim,
+                            double* h_pred);
+int glia_hmt_forest_predict_device(glia_hmt_ctx* ctx, const glia_hmt_forest* forest, const double* d_rows, int64_t n_rows, int dim,
+                                   int64_t row_stride /* doubles, >= dim */, double* d_pred);
+/* Host-only: the rows of the LDS tile the kernel takes for n_rows rows of dim columns -- 64, 32, 16 or 8 -- or 0 when rows of that
+ * length are not staged (dim > GLIA_HMT_PREDICT_STAGE_MAX_DIM).  For tests and tuning; no result depends on it. */
+int glia_hmt_forest_predict_tile_rows(int64_t n_rows, int dim);
+
 /* Length of one feature vector for the configuration the rag was built with (BoundaryClassificationFeats::dim,
  * hmt/bc_feat.hxx:225-230; or selectFeatures' length with --simpf). */
 int glia_hmt_feat_dim(const glia_hmt_rag* rag);
@@ -355,6 +375,29 @@ int64_t glia_hmt_resolve_trees_greedy(int n_trees, const int64_t* n_nodes, const
 int64_t glia_hmt_label_transform(const uint32_t* node_label, const int32_t* child0, const int32_t* child1, int64_t n_nodes,
                                  const int32_t* h_picks, int64_t n_picks, uint32_t key_to_assign, uint32_t* h_src,
                                  uint32_t* h_dst, int64_t capacity);
+
+/* ---- tree inference of segment_ccm (hmt/main_segment_ccm.cxx, hmt/tree_ccm.hxx), host-only ----
+ * glia_hmt_tree_energies = genTree with the node energies of main_segment_ccm.cxx:39-51 + computeEnergyTuples (tree_ccm.hxx:12-27).
+ * Node arrays as glia_hmt_tree_potentials lays them out; inner nodes consume h_merge_probs in merge order.  Per node: its own
+ * em / es (leaf: 0 / FMAX; inner node with merge probability p: em = isfeq(p, 0) ? FMAX : -log(p), es likewise from 1 - p) and the
+ * tuples Em = em + sum Em(child), Es = es + sum min(Em(child), Es(child)), children in the order child0, child1, every sum through
+ * the saturating stats::plusEqual (util/stats.hxx:9-17).  Returns the number of nodes. */
+int64_t glia_hmt_tree_energies(const uint32_t* h_order, int64_t n_merges, const double* h_merge_probs, uint32_t* node_label,
+                               int32_t* parent, int32_t* child0, int32_t* child1, double* em, double* es, double* Em, double* Es,
+                               int64_t capacity);
+/* computeEnergyTuples alone (tree_ccm.hxx:12-27), for given own energies: what glia_hmt_tree_energies runs after the energies. */
+int glia_hmt_tree_energy_tuples(const int32_t* child0, const int32_t* child1, const double* em, const double* es, int64_t n_nodes,
+                                double* Em, double* Es);
+/* resolveFactorTree (tree_ccm.hxx:31-47): breadth-first from the last node; a node with Em < Es is picked (a tie splits), else its
+ * children are queued, child0 first.  h_picks receives node indices in pick order; returns their number. */
+int64_t glia_hmt_resolve_tree_ccm(const int32_t* child0, const int32_t* child1, const double* Em, const double* Es, int64_t n_nodes,
+                                  int32_t* h_picks, int64_t capacity);
+/* The node value of segment_ccm -b (main_segment_ccm.cxx:76-86): pos / plusEqual(neg, pos) with pos = computeFactorNodeEnergyPositive
+ * and neg = computeFactorNodeEnergyNegative (tree_ccm.hxx:62-115), every sum in the reference's own order (O(nodes * depth), like
+ * the reference).  pos / neg / confidence: [n_nodes], pos and neg may be NULL.  The confidence array is the `potential` of
+ * glia_hmt_boundary_confidence. */
+int glia_hmt_tree_ccm_confidence(const int32_t* parent, const int32_t* child0, const int32_t* child1, const double* es, const double* Em,
+                                 const double* Es, int64_t n_nodes, double* pos, double* neg, double* confidence);
 
 /* genBoundaryConfidenceImage with all tree nodes (hmt/tree_segment.hxx:66-203; segment_greedy -b): every voxel on a
  * directed boundary of two supervoxels receives the largest (float) node potential among the tree nodes whose region
