@@ -28,7 +28,13 @@ def _gpu_rm(ctx, labels, pb, bins=8, thr=(0.2, 0.5, 0.8), **kw):
 
 
 def _feat_close(a, b):
+    """f32 images (variant=1): sums are taken in another order than the reference's"""
     return np.allclose(a, b, rtol=1e-5, atol=1e-12)
+
+
+def _feat_bits(a, b):
+    """Q8 / integer-valued images: every sum is exact in double, rows are bit-identical to the oracle's (README)"""
+    return a.shape == b.shape and (a.view(np.uint64) == b.view(np.uint64)).all()
 
 
 def test_p4_known_answer_stub_scorer(ctx):
@@ -62,11 +68,10 @@ def test_stub_scorer_matches_oracle(ctx, shape, S, G, variant, bins):
     cfg = O.make_cfg(pb, rb=[(pb, bins, 0.0, 1.0)])
     o_ref, s_ref, f_ref = O.Rag(labels).merge_order_bc(cfg, None, stub_index=stub, want_feats=True)
     assert order.shape == o_ref.shape and (order == o_ref).all()
-    assert _feat_close(feats, f_ref)
     if variant == 0:
-        assert (sal == s_ref).all()
+        assert (sal == s_ref).all() and _feat_bits(feats, f_ref)
     else:
-        assert np.allclose(sal, s_ref, rtol=0, atol=1e-12)
+        assert np.allclose(sal, s_ref, rtol=0, atol=1e-12) and _feat_close(feats, f_ref)
 
 
 @pytest.mark.parametrize("shape,S,G,ntree,depth", [((32, 32, 32), 8, 16, 31, 6), ((40, 36, 28), 6, 12, 255, 10),
@@ -90,7 +95,7 @@ def test_random_forest_matches_oracle(ctx, shape, S, G, ntree, depth):
     o_ref, s_ref, f_ref = O.Rag(labels).merge_order_bc(cfg, O.make_forest(forest, -1), want_feats=True)
     assert order.shape == o_ref.shape and (order == o_ref).all()
     assert (sal == s_ref).all()              # votes / ntree: exact
-    assert _feat_close(feats, f_ref)
+    assert _feat_bits(feats, f_ref)
     # the forest is walked by helper workgroups (63 by default); the result may not depend on how many there are:
     # 0 = the contraction workgroup walks the trees itself, 5 = every helper takes several records of a chunk.
     # GLIA_HMT_MINCAP: the smallest initial capacities, so that edge slots and list entries grow mid-run with helpers at work
@@ -133,7 +138,7 @@ def test_ensemble_random_forest_matches_oracle(ctx, shape, S, G, ntrees):
     assert set(used.tolist()) == {0, 1, 2}
     assert order.shape == o_ref.shape and (order == o_ref).all()
     assert (sal == s_ref).all()
-    assert _feat_close(feats, f_ref)
+    assert _feat_bits(feats, f_ref)
     for nh in ("0", "5"):
         with hmt.options(GLIA_HMT_HELPERS=nh):
             o2, s2 = rm.merge_order_bc(clf)[:2]
@@ -159,7 +164,7 @@ def test_fuzz_near_tie_case_of_round_1(ctx):
     o, s, f = rm.merge_order_bc(hmt.FeatureStubClassifier(ctx, int(g["stub"])), want_feats=True)
     assert o.shape == g["order"].shape and (o == g["order"]).all()
     assert (s == g["saliency"]).all()
-    assert _feat_close(f, g["feats"])
+    assert _feat_bits(f, g["feats"])
     # the same through a fresh oracle run (the fixture's expected values came from it)
     from oracle import pyoracle as O
     ocfg = O.make_cfg(pb, r=[(raw, bins, 0.0, 1.0)], b=[(pb, 8, 0.0, 1.0)], rl=[(raw, 4, 0.0, 1.0)],
@@ -182,7 +187,7 @@ def test_log_and_simple_features(ctx):
         order, sal, feats = rm.merge_order_bc(hmt.FeatureStubClassifier(ctx, stub), want_feats=True)
         o_ref, s_ref, f_ref = O.Rag(labels).merge_order_bc(cfg, None, stub_index=stub, want_feats=True)
         assert feats.shape == f_ref.shape
-        assert (order == o_ref).all() and _feat_close(feats, f_ref)
+        assert (order == o_ref).all() and _feat_bits(feats, f_ref)
 
 
 @pytest.mark.parametrize("shape,S,G,layout", [((32, 32, 32), 8, 16, 0), ((40, 36, 28), 6, 12, 1), ((64, 64), 4, 16, 2), ((32, 32, 32), 8, 16, 3)])
@@ -215,10 +220,10 @@ def test_histogram_as_features_layout(ctx, shape, S, G, layout):
     order, sal, feats = rm.merge_order_bc(hmt.FeatureStubClassifier(ctx, stub), want_feats=True)
     o_ref, s_ref, f_ref = O.Rag(labels).merge_order_bc(ocfg, None, stub_index=stub, want_feats=True)
     assert feats.shape == f_ref.shape and (order == o_ref).all() and (sal == s_ref).all()
-    assert _feat_close(feats, f_ref)
+    assert _feat_bits(feats, f_ref)
     # bc_feat for a given order
     po, _ = O.Rag(labels, only_contour=True).merge_order_pb(pb, type=2)
-    assert _feat_close(rm.bc_feat(po), O.Rag(labels).bc_feat(ocfg, po))
+    assert _feat_bits(rm.bc_feat(po), O.Rag(labels).bc_feat(ocfg, po))
     rm.close()
     # the median layout inside the greedy LOOP is refused, not silently ignored (bc_feat has it: test_median_as_features_for_a_given_order)
     rm_med = hmt.RegionMap(ctx, d_lab, pb=d_pb, cfg=hmt.make_config(d_pb, use_median_features=True, **dkw))
@@ -260,7 +265,7 @@ def test_full_vector_longer_than_the_kernel_buffers_is_refused(ctx):
     assert fd == O.feat_dim(3, ocfg)
     order, sal, feats = rm.merge_order_bc(hmt.FeatureStubClassifier(ctx, fd - 3), want_feats=True)
     o_ref, s_ref, f_ref = O.Rag(labels).merge_order_bc(ocfg, None, stub_index=fd - 3, want_feats=True)
-    assert (order == o_ref).all() and (sal == s_ref).all() and _feat_close(feats, f_ref)
+    assert (order == o_ref).all() and (sal == s_ref).all() and _feat_bits(feats, f_ref)
     rm.close()
 
 
@@ -273,13 +278,13 @@ def test_bc_feat_for_a_given_order(ctx, shape, S, G):
     rm = _gpu_rm(ctx, labels, pb)
     feats = rm.bc_feat(order)
     ref = O.Rag(labels).bc_feat(O.make_cfg(pb, rb=[(pb, 8, 0.0, 1.0)]), order)
-    assert feats.shape == ref.shape and _feat_close(feats, ref)
+    assert feats.shape == ref.shape and _feat_bits(feats, ref)
     # a merge order that joins non-neighbouring regions first (no shared record)
     labs = np.unique(labels)
     far = np.array([[labs[0], labs[-1], labs.max() + 1]], dtype=np.uint32)
     f2 = rm.bc_feat(far)
     r2 = O.Rag(labels).bc_feat(O.make_cfg(pb, rb=[(pb, 8, 0.0, 1.0)]), far)
-    assert _feat_close(f2, r2)
+    assert _feat_bits(f2, r2)
 
 
 def test_classifier_linkage_with_mask(ctx):
@@ -301,7 +306,7 @@ def test_classifier_linkage_with_mask(ctx):
     ocfg = O.make_cfg(pb, rb=[(pb, 8, 0.0, 1.0)])
     o_ref, s_ref, f_ref = O.Rag(labels, mask=mask).merge_order_bc(ocfg, None, stub_index=stub, want_feats=True)
     assert order.shape == o_ref.shape and (order == o_ref).all()
-    assert (sal == s_ref).all() and _feat_close(feats, f_ref)
+    assert (sal == s_ref).all() and _feat_bits(feats, f_ref)
 
 
 def _aux_images(shape, seed):
@@ -348,10 +353,10 @@ def test_feature_lists_with_several_image_volumes(ctx, layout, shape, S, G):
     order, sal, feats = rm.merge_order_bc(hmt.FeatureStubClassifier(ctx, stub), want_feats=True)
     o_ref, s_ref, f_ref = O.Rag(labels).merge_order_bc(ocfg, None, stub_index=stub, want_feats=True)
     assert order.shape == o_ref.shape and (order == o_ref).all()
-    assert (sal == s_ref).all() and _feat_close(feats, f_ref)
+    assert (sal == s_ref).all() and _feat_bits(feats, f_ref)
     # bc_feat for the given order goes through the forced-order mode of the same kernel
     f2 = rm.bc_feat(order)
-    assert _feat_close(f2, O.Rag(labels).bc_feat(ocfg, o_ref))
+    assert _feat_bits(f2, O.Rag(labels).bc_feat(ocfg, o_ref))
     rm.close()
 
 
@@ -378,7 +383,7 @@ def test_several_image_volumes_with_a_forest_and_simple_features(ctx):
         order, sal, feats = rm.merge_order_bc(clf, want_feats=True)
         o_ref, s_ref, f_ref = O.Rag(labels).merge_order_bc(ocfg, O.make_forest(forest, -1), want_feats=True)
         assert order.shape == o_ref.shape and (order == o_ref).all()
-        assert (sal == s_ref).all() and _feat_close(feats, f_ref)
+        assert (sal == s_ref).all() and _feat_bits(feats, f_ref)
         rm.close()
 
 
@@ -397,7 +402,7 @@ def test_bc_feat_with_saliency_features(ctx, use_log):
     rm = hmt.RegionMap(ctx, d_lab, pb=d_pb, cfg=cfg)
     got = rm.bc_feat(order, saliencies=sal, init_sal=0.75, sal_bias=1.5)
     ref = O.Rag(labels).bc_feat(ocfg, order, saliencies=sal, init_sal=0.75, sal_bias=1.5)
-    assert got.shape == ref.shape == (len(order), 104 + 5) and _feat_close(got, ref)
+    assert got.shape == ref.shape == (len(order), 104 + 5) and _feat_bits(got, ref)
     assert (got[:, 35] <= got[:, 36]).all()               # (min, max) of the two saliency differences
     rm.close()
 
