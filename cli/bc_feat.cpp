@@ -1,14 +1,15 @@
 // cli/bc_feat.cpp -- drop-in for hmt/main_bc_feat.cxx: boundary-classifier feature rows of a GIVEN merge order.
-//   bc_feat -s seg.mha -o order.txt --pb pb.mha [--rbi/--rbb/--rbl/--rbu ...] [--bt ...] [-n b] [-l b] [--simpf b] -b feats.txt
+//   bc_feat -s seg.mha -o order.txt --pb pb.mha [--rbi/--rbb/--rbl/--rbu ...] [--bt ...] [-n b] [-l b] [--simpf b] [--batch 0|1] -b feats.txt
+//   --batch 1: the rows by the batch route over the known merge tree (glia_hmt_bc_feat_batch) instead of the replay of the order
 #include "common.hpp"
 
 using namespace cli;
 
 int main(int argc, char* argv[]) {
   const std::string usage = "Usage: bc_feat -s <seg> -o <order> --pb <pb> [--rbi/--rbb/--rbl/--rbu ...] [--bt ...] [-n b] [-l b] [--simpf b] "
-                            "-b <feats>   (flags as hmt/main_bc_feat.cxx:125-185)\n";
+                            "[--batch 0|1] -b <feats>   (flags as hmt/main_bc_feat.cxx:125-185; --batch 1: batch route, default 0 = replay)\n";
   std::vector<std::string> known = {"segImage", "mergeOrder", "saliency", "rbi", "rbb", "rbl", "rbu", "rli", "rlb", "rll", "rlu", "ri", "rb", "rl",
-                                    "ru", "bi", "bb", "bl", "bu", "pb", "maskImage", "s0", "sb", "bt", "ns", "logs", "simpf", "histf", "medf", "bfeat"};
+                                    "ru", "bi", "bb", "bl", "bu", "pb", "maskImage", "s0", "sb", "bt", "ns", "logs", "simpf", "histf", "medf", "bfeat", "batch"};
   Args a = parse(argc, argv, {{"s", "segImage"}, {"o", "mergeOrder"}, {"y", "saliency"}, {"m", "maskImage"}, {"n", "ns"}, {"l", "logs"}, {"b", "bfeat"}},
                  known, usage);
   for (const char* req : {"segImage", "mergeOrder", "pb"})
@@ -33,8 +34,9 @@ int main(int argc, char* argv[]) {
   }
   const int d = glia_hmt_bc_feat_dim(rag, sal.empty() ? 0 : 1);
   std::vector<double> feats((size_t)(n ? n : 1) * d);
-  check(glia_hmt_bc_feat_saliency(ctx, rag, order.data(), n, sal.empty() ? nullptr : sal.data(), atof(a.str("s0", "1.0").c_str()),
-                                  atof(a.str("sb", "1.0").c_str()), feats.data()));
+  const bool batch = atoi(a.str("batch", "0").c_str()) != 0;
+  check((batch ? glia_hmt_bc_feat_batch : glia_hmt_bc_feat_saliency)(ctx, rag, order.data(), n, sal.empty() ? nullptr : sal.data(),
+                                                                     atof(a.str("s0", "1.0").c_str()), atof(a.str("sb", "1.0").c_str()), feats.data()));
   writeRows(a.str("bfeat"), feats.data(), n, d, /*FLT_PREC*/ 8);                  // :103-110
   glia_hmt_rag_free(rag); glia_hmt_ctx_destroy(ctx);
   (void)hipFree(f.dLab); (void)hipFree(f.dPb);

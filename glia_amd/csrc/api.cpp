@@ -27,7 +27,7 @@ void set_error(const std::string& msg) { g_err = msg; }
 // when the table is first used -- no entry point calls getenv() per call.
 static const char* const kOptionKeys[] = {"GLIA_HMT_PB_WINDOW", "GLIA_HMT_PB_BATCH", "GLIA_HMT_WINCAP", "GLIA_HMT_REBASE", "GLIA_HMT_HORIZON",
                                           "GLIA_HMT_FORCE_TREE", "GLIA_HMT_HELPERS", "GLIA_HMT_TRACE", "GLIA_HMT_LIBM", "GLIA_HMT_BC_NOCOMMON",
-                                          "GLIA_HMT_BC_GENERIC", "GLIA_HMT_DEBUG", "GLIA_HMT_MAXITERS", "GLIA_HMT_MINCAP", "GLIA_HMT_MEDIAN_BATCH"};
+                                          "GLIA_HMT_BC_GENERIC", "GLIA_HMT_DEBUG", "GLIA_HMT_MAXITERS", "GLIA_HMT_MINCAP", "GLIA_HMT_MEDIAN_BATCH", "GLIA_HMT_BCFEAT"};
 static std::mutex g_opt_mu;
 static std::unordered_map<std::string, std::string> g_opt;
 static bool g_opt_init = false;
@@ -1040,24 +1040,18 @@ int glia_hmt_bc_feat_dim(const glia_hmt_rag* rag, int with_saliency) {
   return cfg.fdim + median_extra_cols(rag, cfg) + ((with_saliency && !cfg.use_simple) ? 5 : 0);
 }
 
-int glia_hmt_bc_feat_saliency(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t* h_order, int64_t n_merges,
-                              const double* h_saliencies, double init_saliency, double saliency_bias, double* h_feats) {
-  if (!c || !rag || !h_order || !h_feats || n_merges < 0 || rag->ctx != c) { set_error("bc_feat: invalid argument"); return GLIA_HMT_ERR_ARG; }
-  BcCfg cfg;
-  int rc;
-  MedianFeatIn in;
-  if ((rc = bc_setup(c, rag, nullptr, "bc_feat", &cfg, &in))) return rc;
+// ---- bc_feat: what both routes to the statistic rows share ----
+// keys -> dense ids: leaves by label, the region created by merge i is R + i (RegionMap(seg, mask, order, false),
+// type/region_map.hxx:42-48,67-68); the order is validated on the way
+static int bc_feat_dense_order(const glia_hmt_rag* rag, const uint32_t* h_order, int64_t n_merges, std::vector<uint32_t>* forced_o) {
   const int64_t R = rag->arr.R;
-  if (n_merges == 0) return GLIA_HMT_OK;
-  if (n_merges >= R) { set_error("bc_feat: more merges than regions"); return GLIA_HMT_ERR_ARG; }
-  // keys -> dense ids: leaves by label, the region created by merge i is R + i (RegionMap(seg, mask, order, false),
-  // type/region_map.hxx:42-48,67-68)
   std::vector<uint32_t> lab((size_t)R);
   GLIA_HIP_TRY(hipMemcpy(lab.data(), rag->arr.d_rlabel, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
   std::unordered_map<uint32_t, uint32_t> id;
   id.reserve((size_t)R * 2);
   for (int64_t i = 0; i < R; ++i) id[lab[i]] = (uint32_t)i;
-  std::vector<uint32_t> forced((size_t)2 * n_merges);
+  std::vector<uint32_t>& forced = *forced_o;
+  forced.assign((size_t)2 * n_merges, 0);
   std::vector<uint8_t> used((size_t)R + n_merges, 0);
   for (int64_t i = 0; i < n_merges; ++i) {
     for (int s2 = 0; s2 < 2; ++s2) {
@@ -1069,49 +1063,43 @@ int glia_hmt_bc_feat_saliency(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t
     if (id.count(h_order[3 * i + 2])) { set_error("bc_feat: merge order reuses a region key"); return GLIA_HMT_ERR_ARG; }
     id[h_order[3 * i + 2]] = (uint32_t)(R + i);
   }
-  DeviceClassifier none;
-  memset(&none, 0, sizeof(none));
-  none.kind = 1;
-  BcRequest req;
-  req.forced = forced.data(); req.n_forced = n_merges; req.rows = true;
-  MergeResult res;
-  if ((rc = greedy_bc(rag->arr, cfg, none, c->stream, req, &res))) return rc;
-  keep_timing(rag, res);
-  if (res.n != n_merges) { set_error("bc_feat: merges not completed (internal error)"); count_internal_error(); return GLIA_HMT_ERR_INTERNAL; }
-  const int64_t n = res.n;
-  std::vector<double>& feats = res.rows;
-  int bfdim = cfg.bfdim, rfdim = cfg.rfdim, fdim = cfg.fdim;
-  if (rag->cfg.use_median_features) {
-    // GLIA_USE_MEDIAN_AS_FEATS: the kernel's rows (built from the statistics monoids) + the medians, means and standard deviations
-    // of the value multisets (median_feats.hip), spliced into the reference's layout (median_layout.hpp)
-    in.forced = forced.data(); in.n_merges = n_merges;
-    std::vector<double> reg, bnd;
-    std::vector<unsigned long long> marea;
-    if ((rc = median_feature_stats(in, c->stream, &reg, &bnd, &marea))) return rc;
-    const int nr = in.n_r, nb = in.n_b;
-    const int nd = cfg.fdim + median_extra_cols(rag, cfg);
-    std::vector<double> rows((size_t)n * nd);
-    for (int64_t i = 0; i < n; ++i) {
-      const bool swap = sdivide_host((double)marea[forced[2 * i]], cfg.norm_area) > sdivide_host((double)marea[forced[2 * i + 1]], cfg.norm_area);
-      // x1 = the smaller region (main_bc_feat.cxx:84-88): k of the statistics arrays for block b of the row
-      const int kreg[3] = {swap ? 1 : 0, swap ? 0 : 1, 2};
-      auto RS = [&](int blk, int img, int q) { return reg[(((size_t)i * 3 + kreg[blk]) * nr + img) * 3 + q]; };
-      auto BS = [&](int blk, int img, int q) { return bnd[(((size_t)i * 4 + (blk < 3 ? kreg[blk] : 3)) * nb + img) * 3 + q]; };
-      if (median_splice(cfg, &feats[(size_t)i * cfg.fdim], &rows[(size_t)i * nd], RS, BS) != nd) { set_error("bc_feat: internal error, median feature layout"); return GLIA_HMT_ERR_INTERNAL; }
-    }
-    feats.swap(rows);
-    fdim = nd;
-    if (!cfg.use_simple) { bfdim = cfg.bfdim + in.n_r + in.n_b; rfdim = cfg.rfdim + in.n_r + in.n_b; }
+  return GLIA_HMT_OK;
+}
+
+// GLIA_USE_MEDIAN_AS_FEATS: the statistic rows (built from the statistics monoids) + the medians, means and standard deviations
+// of the value multisets (median_feats.hip), spliced into the reference's layout (median_layout.hpp); *feats is replaced
+static int bc_feat_median_rows(glia_hmt_ctx* c, const glia_hmt_rag* rag, const BcCfg& cfg, MedianFeatIn& in, const std::vector<uint32_t>& forced, int64_t n,
+                               std::vector<double>* feats, int* bfdim, int* rfdim, int* fdim) {
+  in.forced = forced.data(); in.n_merges = n;
+  std::vector<double> reg, bnd;
+  std::vector<unsigned long long> marea;
+  if (int rc = median_feature_stats(in, c->stream, &reg, &bnd, &marea)) return rc;
+  const int nr = in.n_r, nb = in.n_b;
+  const int nd = cfg.fdim + median_extra_cols(rag, cfg);
+  std::vector<double> rows((size_t)n * nd);
+  for (int64_t i = 0; i < n; ++i) {
+    const bool swap = sdivide_host((double)marea[forced[2 * i]], cfg.norm_area) > sdivide_host((double)marea[forced[2 * i + 1]], cfg.norm_area);
+    // x1 = the smaller region (main_bc_feat.cxx:84-88): k of the statistics arrays for block b of the row
+    const int kreg[3] = {swap ? 1 : 0, swap ? 0 : 1, 2};
+    auto RS = [&](int blk, int img, int q) { return reg[(((size_t)i * 3 + kreg[blk]) * nr + img) * 3 + q]; };
+    auto BS = [&](int blk, int img, int q) { return bnd[(((size_t)i * 4 + (blk < 3 ? kreg[blk] : 3)) * nb + img) * 3 + q]; };
+    if (median_splice(cfg, &(*feats)[(size_t)i * cfg.fdim], &rows[(size_t)i * nd], RS, BS) != nd) { set_error("bc_feat: internal error, median feature layout"); return GLIA_HMT_ERR_INTERNAL; }
   }
-  if (!h_saliencies || cfg.use_simple) {       // selectFeatures carries no saliency (hmt/bc_feat.hxx:247-279)
-    memcpy(h_feats, feats.data(), sizeof(double) * (size_t)n * fdim);
-    return GLIA_HMT_OK;
-  }
-  // Saliency features (hmt/main_bc_feat.cxx:50-55): every region of the order carries a number -- initSal for the
-  // regions that are only merged, saliency + bias for the region a merge creates (genSaliencyMap, hmt/bc_feat.hxx:12-26).
-  // They do not depend on the image: each region block gets its number appended (bc_feat.hxx:76), the boundary block
-  // (min, max) of |s(x1) - s(x3)|, |s(x2) - s(x3)| (:163-166, :208-213).  Which region is x1 follows the area rule of
-  // main_bc_feat.cxx:88-91, for which the voxel counts of the tree nodes are summed up here.
+  feats->swap(rows);
+  *fdim = nd;
+  if (!cfg.use_simple) { *bfdim = cfg.bfdim + in.n_r + in.n_b; *rfdim = cfg.rfdim + in.n_r + in.n_b; }
+  return GLIA_HMT_OK;
+}
+
+// Saliency features (hmt/main_bc_feat.cxx:50-55): every region of the order carries a number -- initSal for the
+// regions that are only merged, saliency + bias for the region a merge creates (genSaliencyMap, hmt/bc_feat.hxx:12-26).
+// They do not depend on the image: each region block gets its number appended (bc_feat.hxx:76), the boundary block
+// (min, max) of |s(x1) - s(x3)|, |s(x2) - s(x3)| (:163-166, :208-213).  Which region is x1 follows the area rule of
+// main_bc_feat.cxx:88-91, for which the voxel counts of the tree nodes are summed up here.
+static int bc_feat_saliency_rows(const glia_hmt_rag* rag, const BcCfg& cfg, const uint32_t* h_order, const std::vector<uint32_t>& forced, int64_t n_merges,
+                                 const double* h_saliencies, double init_saliency, double saliency_bias, const std::vector<double>& feats, int bfdim,
+                                 int rfdim, int fdim, double* h_feats) {
+  const int64_t R = rag->arr.R;
   std::vector<uint32_t> rrec((size_t)R * kRegionWords);
   GLIA_HIP_TRY(hipMemcpy(rrec.data(), rag->arr.d_rrec, sizeof(uint32_t) * kRegionWords * R, hipMemcpyDeviceToHost));
   std::vector<unsigned long long> area((size_t)R + n_merges);
@@ -1142,6 +1130,77 @@ int glia_hmt_bc_feat_saliency(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t
     for (int q = 0; q < rfdim; ++q) out[k++] = in[bfdim + 2 * rfdim + q];
     out[k++] = s2;
   }
+  return GLIA_HMT_OK;
+}
+
+// route: the replay through the classifier loop (greedy_bc.hip, one contraction at a time) or the batch formulation over the known
+// tree (bc_feat_batch.hip); everything after the statistic rows is common
+static int bc_feat_rows(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t* h_order, int64_t n_merges, const double* h_saliencies, double init_saliency,
+                        double saliency_bias, double* h_feats, int route) {
+  if (!c || !rag || !h_order || !h_feats || n_merges < 0 || rag->ctx != c) { set_error("bc_feat: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  BcCfg cfg;
+  int rc;
+  MedianFeatIn in;
+  if ((rc = bc_setup(c, rag, nullptr, "bc_feat", &cfg, &in))) return rc;
+  const int64_t R = rag->arr.R;
+  if (n_merges == 0) return GLIA_HMT_OK;
+  if (n_merges >= R) { set_error("bc_feat: more merges than regions"); return GLIA_HMT_ERR_ARG; }
+  std::vector<uint32_t> forced;
+  if ((rc = bc_feat_dense_order(rag, h_order, n_merges, &forced))) return rc;
+  MergeResult res;
+  memset(&rag->bft, 0, sizeof(rag->bft));
+  if (route == GLIA_HMT_BCFEAT_BATCH) {
+    BcFeatBatchInfo info;
+    if ((rc = bc_feat_batch_rows(rag->arr, cfg, forced.data(), n_merges, c->stream, &res.rows, &info))) return rc;
+    res.n = n_merges;
+    rag->bft = glia_hmt_bc_feat_timing{info.ms_plan, info.ms_sets, info.ms_rows, info.height, info.launches, info.path_updates, GLIA_HMT_BCFEAT_BATCH};
+  } else {
+    DeviceClassifier none;
+    memset(&none, 0, sizeof(none));
+    none.kind = 1;
+    BcRequest req;
+    req.forced = forced.data(); req.n_forced = n_merges; req.rows = true;
+    if ((rc = greedy_bc(rag->arr, cfg, none, c->stream, req, &res))) return rc;
+    keep_timing(rag, res);
+    rag->bft = glia_hmt_bc_feat_timing{0.0, res.ms_table + res.ms_init, res.ms_loop, 0, 0, 0, GLIA_HMT_BCFEAT_REPLAY};
+    if (res.n != n_merges) { set_error("bc_feat: merges not completed (internal error)"); count_internal_error(); return GLIA_HMT_ERR_INTERNAL; }
+  }
+  const int64_t n = res.n;
+  std::vector<double>& feats = res.rows;
+  int bfdim = cfg.bfdim, rfdim = cfg.rfdim, fdim = cfg.fdim;
+  if (rag->cfg.use_median_features && (rc = bc_feat_median_rows(c, rag, cfg, in, forced, n, &feats, &bfdim, &rfdim, &fdim))) return rc;
+  if (!h_saliencies || cfg.use_simple) {       // selectFeatures carries no saliency (hmt/bc_feat.hxx:247-279)
+    memcpy(h_feats, feats.data(), sizeof(double) * (size_t)n * fdim);
+    return GLIA_HMT_OK;
+  }
+  return bc_feat_saliency_rows(rag, cfg, h_order, forced, n_merges, h_saliencies, init_saliency, saliency_bias, feats, bfdim, rfdim, fdim, h_feats);
+}
+
+// GLIA_HMT_BCFEAT = replay (default) | batch, read per call: which route the two older entry points take
+static int bc_feat_default_route(int* route) {
+  std::string v;
+  *route = GLIA_HMT_BCFEAT_REPLAY;
+  if (!option("GLIA_HMT_BCFEAT", &v) || v == "replay") return GLIA_HMT_OK;
+  if (v == "batch") { *route = GLIA_HMT_BCFEAT_BATCH; return GLIA_HMT_OK; }
+  set_error("bc_feat: GLIA_HMT_BCFEAT must be replay or batch, not '" + v + "'");
+  return GLIA_HMT_ERR_ARG;
+}
+
+int glia_hmt_bc_feat_saliency(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t* h_order, int64_t n_merges,
+                              const double* h_saliencies, double init_saliency, double saliency_bias, double* h_feats) {
+  int route;
+  if (int rc = bc_feat_default_route(&route)) return rc;
+  return bc_feat_rows(c, rag, h_order, n_merges, h_saliencies, init_saliency, saliency_bias, h_feats, route);
+}
+
+int glia_hmt_bc_feat_batch(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t* h_order, int64_t n_merges,
+                           const double* h_saliencies, double init_saliency, double saliency_bias, double* h_feats) {
+  return bc_feat_rows(c, rag, h_order, n_merges, h_saliencies, init_saliency, saliency_bias, h_feats, GLIA_HMT_BCFEAT_BATCH);
+}
+
+int glia_hmt_last_bc_feat_timing(const glia_hmt_rag* r, glia_hmt_bc_feat_timing* out) {
+  if (!r || !out) { set_error("last_bc_feat_timing: NULL argument"); return GLIA_HMT_ERR_ARG; }
+  *out = r->bft;
   return GLIA_HMT_OK;
 }
 

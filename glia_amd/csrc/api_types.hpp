@@ -32,6 +32,7 @@ struct glia_hmt_rag {
   double pass_ms = 0, alg_bytes = 0;
   double ms_table = 0, ms_init = 0, ms_loop = 0;
   glia_hmt_bc_label_timing bcl;   // the last glia_hmt_bc_label call
+  glia_hmt_bc_feat_timing bft = {0, 0, 0, 0, 0, 0, 0};   // the last bc_feat call, either route
   int64_t n_scored = 0;
   glia_hmt_feat_config cfg;
   bool has_cfg = false;

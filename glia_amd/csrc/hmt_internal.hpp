@@ -202,6 +202,14 @@ GLIA_DECLARE_GREEDY_BC(greedy_bc_sse2);
 GLIA_DECLARE_GREEDY_BC(greedy_bc_fma_common);      // + GLIA_BC_COMMON (bc_features.hpp): one image on the region and boundary lists, no --logs / --simpf / histogram columns
 GLIA_DECLARE_GREEDY_BC(greedy_bc_sse2_common);
 GLIA_DECLARE_GREEDY_BC(greedy_bc);
+// bc_feat for a given order as a batch computation over the known merge tree (bc_feat_batch.hip): rows [M][cfg.fdim] in the layout
+// greedy_bc writes them.  forced: dense region pairs of the merges, validated by the caller.
+struct BcFeatBatchInfo {
+  double ms_plan = 0, ms_sets = 0, ms_rows = 0;      // host plan (tree tables, uploads) | device: the sets | device: row assembly
+  int64_t height = 0, launches = 0, path_updates = 0;
+};
+int bc_feat_batch_rows(const RagArrays& rag, const BcCfg& cfg, const uint32_t* forced, int64_t M, hipStream_t stream, std::vector<double>* rows,
+                       BcFeatBatchInfo* info);
 int compact_tables(const AccParams& p, uint32_t rcap, uint32_t pcap, RagArrays* out, hipStream_t stream);
 int transform_keys(const uint32_t* order, int64_t n, std::vector<uint32_t>* src, std::vector<uint32_t>* dst);
 int transform_image(uint32_t* d_lab, int64_t n, const uint32_t* h_src, const uint32_t* h_dst, int64_t m, const uint32_t* d_mask,

@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "median_runs.hpp"
+#include "tree_paths.hpp"
 
 namespace glia {
 
@@ -147,25 +148,9 @@ int median_feature_stats(const MedianFeatIn& in, hipStream_t stream, std::vector
   auto leaf_of = [&](uint32_t label) { return (uint32_t)(std::lower_bound(lab.begin(), lab.end(), label) - lab.begin()); };
   // ---- the merge tree: leaves 0 .. R-1, the region of merge i = R + i; depth-first leaf positions, node = interval of positions ----
   const size_t nn = (size_t)R + (size_t)M;
-  std::vector<int64_t> parent(nn, -1);
-  for (int64_t i = 0; i < M; ++i) { parent[in.forced[2 * i]] = (int64_t)R + i; parent[in.forced[2 * i + 1]] = (int64_t)R + i; }
-  std::vector<uint32_t> pos(R), at(R), lo(nn), hi(nn);            // position of a leaf; leaf at a position; interval [lo, hi) of a node
-  {
-    uint32_t next = 0;
-    std::vector<std::pair<size_t, int>> stack;
-    for (size_t root = nn; root-- > 0;) {                        // (any order of the roots will do)
-      if (parent[root] >= 0) continue;
-      stack.push_back({root, 0});
-      while (!stack.empty()) {
-        auto& top = stack.back();
-        const size_t x = top.first;
-        if (x < R) { pos[x] = next; at[next] = (uint32_t)x; lo[x] = next; hi[x] = ++next; stack.pop_back(); continue; }
-        if (top.second == 0) { lo[x] = next; top.second = 1; stack.push_back({in.forced[2 * (x - R)], 0}); continue; }
-        if (top.second == 1) { top.second = 2; stack.push_back({in.forced[2 * (x - R) + 1], 0}); continue; }
-        hi[x] = next; stack.pop_back();
-      }
-    }
-  }
+  std::vector<int64_t> parent;
+  std::vector<uint32_t> pos, at, lo, hi;                          // position of a leaf; leaf at a position; interval [lo, hi) of a node
+  tp::tree_intervals(in.forced, R, M, &parent, &pos, &at, &lo, &hi);
   std::vector<unsigned long long> voff((size_t)R + 1, 0), leaf_off(R);      // voxel-value offsets by position / by leaf
   for (uint32_t q = 0; q < R; ++q) { voff[q + 1] = voff[q] + leaf_n[at[q]]; leaf_off[at[q]] = voff[q]; }
   area_out->assign(nn, 0);

@@ -551,6 +551,11 @@ class BcLabelOpts(C.Structure):
     _fields_ = [("metric", C.c_int), ("tweak", C.c_int), ("max_prec_drop", C.c_double), ("opt_split", C.c_int), ("global_opt", C.c_int)]
 
 
+class BcFeatTiming(C.Structure):
+    _fields_ = [("ms_plan", C.c_double), ("ms_sets", C.c_double), ("ms_rows", C.c_double), ("height", C.c_int64),
+                ("launches", C.c_int64), ("path_updates", C.c_int64), ("route", C.c_int)]
+
+
 class BcLabelTiming(C.Structure):
     _fields_ = [("ms_count", C.c_double), ("ms_nodes", C.c_double), ("ms_rules", C.c_double), ("entries", C.c_int64),
                 ("moves", C.c_int64), ("node_pairs", C.c_int64)]
@@ -737,6 +742,28 @@ class RegionMap:
         _check(lib().glia_hmt_bc_feat_saliency(self.ctx.h, self.h, _np(order), C.c_int64(len(order)), _np(sal),
                                                C.c_double(init_sal), C.c_double(sal_bias), _np(feats)))
         return feats
+
+    def bc_feat_batch(self, order, saliencies=None, init_sal=1.0, sal_bias=1.0):
+        """the rows of bc_feat by the batch route (hmt/main_bc_feat.cxx:59-95 is parallel over merges too): every set of the known
+        merge tree at once instead of a replay of the order; same arguments, row width and errors"""
+        order = np.ascontiguousarray(order, dtype=np.uint32)
+        d = lib().glia_hmt_bc_feat_dim(self.h, C.c_int(1 if saliencies is not None else 0))
+        feats = np.empty((len(order), d), np.float64)
+        sal = None if saliencies is None else np.ascontiguousarray(saliencies, dtype=np.float64)
+        _check(lib().glia_hmt_bc_feat_batch(self.ctx.h, self.h, _np(order), C.c_int64(len(order)), _np(sal),
+                                            C.c_double(init_sal), C.c_double(sal_bias), _np(feats)))
+        return feats
+
+    BC_FEAT_ROUTES = ("replay", "batch")
+
+    def last_bc_feat_timing(self):
+        """stages of the last bc_feat / bc_feat_batch call: ms_plan (host), ms_sets, ms_rows (device), height, launches,
+        path_updates, route ("replay" | "batch")"""
+        t = BcFeatTiming()
+        _check(lib().glia_hmt_last_bc_feat_timing(self.h, C.byref(t)))
+        out = {k: getattr(t, k) for k, _ in BcFeatTiming._fields_}
+        out["route"] = self.BC_FEAT_ROUTES[t.route]
+        return out
 
     BC_METRICS = {"f1": 0, "ri": 1, "vi": 2}
 

@@ -317,6 +317,28 @@ int glia_hmt_bc_feat(glia_hmt_ctx* ctx, glia_hmt_rag* rag, const uint32_t* h_ord
 int glia_hmt_bc_feat_saliency(glia_hmt_ctx* ctx, glia_hmt_rag* rag, const uint32_t* h_order, int64_t n_merges,
                               const double* h_saliencies, double init_saliency, double saliency_bias, double* h_feats);
 int glia_hmt_bc_feat_dim(const glia_hmt_rag* rag, int with_saliency);
+/* The same rows by a second route, parallel over merges as the reference's own loops are (hmt/main_bc_feat.cxx:59-95 under the
+ * parfor of util/mp.hxx:24-106): the order is given, so the merge tree is known before any statistic is combined, and every set a
+ * row looks at is computed for all tree nodes at once (glia_amd/csrc/bc_feat_batch.hip).  Arguments, row width
+ * (glia_hmt_bc_feat_dim) and errors are those of glia_hmt_bc_feat_saliency; h_saliencies may be NULL.  Rows are identical to the replay's wherever the sums are exact (quantised images) and
+ * within 1e-12 in the mean / standard deviation columns otherwise (another association of the f64 sums); two calls on one map
+ * return identical bytes.  Trees whose tables exceed the memory bound of DESIGN 7: GLIA_HMT_ERR_UNSUPPORTED.
+ * Option GLIA_HMT_BCFEAT = replay (default) | batch (glia_hmt_set_option or the environment) sends glia_hmt_bc_feat and
+ * glia_hmt_bc_feat_saliency down this route. */
+int glia_hmt_bc_feat_batch(glia_hmt_ctx* ctx, glia_hmt_rag* rag, const uint32_t* h_order, int64_t n_merges,
+                           const double* h_saliencies, double init_saliency, double saliency_bias, double* h_feats);
+/* the stages of the last bc_feat call on this map, whichever route it took */
+enum { GLIA_HMT_BCFEAT_REPLAY = 0, GLIA_HMT_BCFEAT_BATCH = 1 };
+typedef struct {
+  double ms_plan;          /* batch: host plan (tree tables, uploads); replay: 0 */
+  double ms_sets;          /* batch: device time of the sets of all tree nodes; replay: table + initial state of the loop */
+  double ms_rows;          /* batch: device time of the row kernel; replay: the loop */
+  int64_t height;          /* batch: height of the merge tree (levels of the bottom-up pass); replay: 0 */
+  int64_t launches;        /* batch: kernel launches of the call; replay: 0 */
+  int64_t path_updates;    /* batch: table updates of the min / max lifting (two per entry and channel); replay: 0 */
+  int route;               /* GLIA_HMT_BCFEAT_REPLAY | GLIA_HMT_BCFEAT_BATCH */
+} glia_hmt_bc_feat_timing;
+int glia_hmt_last_bc_feat_timing(const glia_hmt_rag* rag, glia_hmt_bc_feat_timing* out);
 
 /* Replaces hmt/main_bc_label_ri.cxx:27-153 and hmt/main_bc_label_vi.cxx:27-128 for a GIVEN merge order: the label of every merge,
  * GLIA_HMT_BC_MERGE (-1) or GLIA_HMT_BC_SPLIT (+1), decided against truth volumes (genBoundaryClassificationLabelF1 / RI / VI,
