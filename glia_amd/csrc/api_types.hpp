@@ -1,5 +1,7 @@
-// glia_amd/csrc/api_types.hpp -- the opaque handles of include/glia_hmt.h as the library sees them (api.cpp, slab_dist.cpp).
+// glia_amd/csrc/api_types.hpp -- the opaque handles of include/glia_hmt.h as the library sees them (api.cpp, api_rag.cpp, api_loops.cpp,
+// slab_dist.cpp), and the few host functions those files share.
 #pragma once
+#include "forest.hpp"
 #include "glibc_math.hpp"
 #include "greedy_common.hpp"
 #include "hmt_internal.hpp"
@@ -41,4 +43,19 @@ struct glia_hmt_rag {
   uint32_t* d_folded = nullptr;  // labels with the mask folded in (owned)
   int map_region[GLIA_HMT_MAX_IMAGES] = {0}, map_rlabel[GLIA_HMT_MAX_IMAGES] = {0}, map_boundary[GLIA_HMT_MAX_IMAGES] = {0};   // list entry -> channel
 };
+// a handle like this one, owning nothing yet: no arrays, no folded labels, no volume or planes to re-read
+inline glia_hmt_rag* rag_like(const glia_hmt_rag* like) {
+  glia_hmt_rag* rag = new glia_hmt_rag(*like);
+  rag->arr = RagArrays(); rag->d_folded = nullptr; rag->vol = VolumeRef(); rag->slab = VolumeRef();
+  return rag;
+}
 
+struct glia_hmt_forest {
+  int device = 0;
+  glia::DeviceClassifier dc;
+  OwnedArrays allocs;            // the packed trees of every model
+  int max_var = 0;
+};
+
+int free_tables(glia_hmt_ctx* c);           // api_rag.cpp: the accumulation tables of a context
+namespace glia { float ceil_f32(double d); uint32_t next_pow2(uint64_t v); HistSpec make_hist_spec(int bins, double lo, double hi); }   // api.cpp

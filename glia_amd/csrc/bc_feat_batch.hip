@@ -347,8 +347,8 @@ int bc_feat_batch_rows(const RagArrays& rag, const BcCfg& cfg, const uint32_t* f
   for (int c = 0; c < K; ++c) {
     if ((rc = buf.get(&s.P[c], nn, false, stream)) || (rc = buf.get(&s.B[c], nn, false, stream)) || (rc = buf.get(&s.A[c], (size_t)M, false, stream)) ||
         (rc = buf.get(&s.Sh[c], (size_t)M, false, stream))) return rc;
-    s.prec[c] = rag.c_prec[c] ? rag.c_prec[c] : rag.d_prec;
-    s.rrec[c] = rag.c_rrec[c] ? rag.c_rrec[c] : rag.d_rrec;
+    s.prec[c] = rag.c_prec[c];
+    s.rrec[c] = rag.c_rrec[c];
     s.bins[c] = cfg.cbins[c];
   }
   uint32_t *d_ea, *d_eb, *d_etop, *d_ejoin, *d_eplen, *d_keys, *d_vals, *d_ks, *d_vs, *d_le_start, *d_nm, *d_pmin, *d_pmax, *d_tmin, *d_tmax;

@@ -61,10 +61,3 @@ int launch_forest_predict(const DeviceClassifier& clf, const double* d_rows, lon
                           hipStream_t stream);
 
 }  // namespace glia
-
-struct glia_hmt_forest {
-  int device = 0;
-  glia::DeviceClassifier dc;
-  std::vector<void*> allocs;
-  int max_var = 0;
-};

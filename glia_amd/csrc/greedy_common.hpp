@@ -525,6 +525,24 @@ struct DeviceBuffers {
     return GLIA_HMT_OK;
   }
 };
+// Arrays that outlive the call that allocates them (they end up in a handle), and the few temporaries that bypass the block cache:
+// plain hipMalloc blocks, hipFree'd when the owner goes out of scope -- so a return from the middle of a function leaks nothing.  A
+// function that succeeds hands its arrays on with keep(); free_all() / free_one() free where the sequence of runtime calls matters.
+struct OwnedArrays {
+  std::vector<void*> all;
+  OwnedArrays() = default;
+  OwnedArrays(const OwnedArrays&) = delete;
+  ~OwnedArrays() { free_all(); }
+  template <typename T> int alloc(T** out, size_t n) {
+    GLIA_HIP_TRY(hipMalloc(out, sizeof(T) * (n ? n : 1)));
+    all.push_back(*out);
+    return GLIA_HMT_OK;
+  }
+  void keep() { all.clear(); }                       // success: whoever got the pointers owns them now
+  void adopt(void* p) { if (p) all.push_back(p); }   // ... and this is how an owner gets them
+  void free_all() { for (void* p : all) (void)hipFree(p); all.clear(); }
+  void free_one(void* p) { (void)hipFree(p); all.erase(std::find(all.begin(), all.end(), p)); }
+};
 
 // The arrays a loop kernel fills up to one capacity -- edge slots, list entries or values -- each registered once with the
 // elements it holds per unit of capacity; an ST_NEED_* handler grows them all with one call.

@@ -82,7 +82,9 @@ struct AccParams {
 constexpr int kMaxChannels = 4;     // distinct (image volume, histogram) pairs over all feature lists
 constexpr int kMaxListed = GLIA_HMT_MAX_IMAGES;   // images per feature list (region / label / boundary); the vector they give must still fit kMaxFeat columns
 
-// compact, sorted RAG as produced by the edge-table step
+// compact, sorted RAG as produced by the edge-table step.  INVARIANT, established by every producer and relied on by every consumer:
+// c_rrec[0] == d_rrec and c_prec[0] == d_prec -- a channel's records are read as c_rrec[ch] / c_prec[ch], never with a fallback.
+// It owns its blocks (released by free_rag_arrays only) unless it is a view (slab_dist.cpp, Block::view), which is never released.
 struct RagArrays {
   int64_t R = 0, P = 0;       // regions, directed pairs
   uint32_t* d_rlabel = nullptr;   // [R] ascending
@@ -91,7 +93,7 @@ struct RagArrays {
   uint32_t* d_pb = nullptr;       // [P]
   uint32_t* d_prec = nullptr;     // [P][kPairWords]
   // Feature lists with several image volumes: one accumulation pass per distinct (volume, histogram) CHANNEL.  Channel
-  // 0 is the boundary-probability volume (d_rrec / d_prec above = c_rrec[0] / c_prec[0]); the keys are common.
+  // 0 is the boundary-probability volume; the keys are common.
   int K = 1;
   uint32_t* c_rrec[kMaxChannels] = {nullptr, nullptr, nullptr, nullptr};
   uint32_t* c_prec[kMaxChannels] = {nullptr, nullptr, nullptr, nullptr};
@@ -104,6 +106,7 @@ struct RagArrays {
   unsigned long long nV = 0;
 };
 
+void free_rag_arrays(RagArrays* a);      // the one place that knows which pointers are owned: every block once, then *a = RagArrays()
 int launch_accumulate(const AccParams& p, hipStream_t stream);
 int launch_synth(int dim, const int64_t dims[3], int S, int G, uint64_t seed, int variant, uint32_t* d_labels,
                  uint32_t* d_truth_tmp, float* d_pb, hipStream_t stream);
@@ -193,7 +196,7 @@ struct BcRequest {
 // greedy_bc.hip is compiled five times: with the libm restatements of the feature code (glibc_math.hpp) selected at run time
 // (any combination, incl. "unpinned"), and with the two combinations real hosts have -- glibc's FMA build and its non-FMA
 // build -- fixed at compile time (a run-time choice between three logarithms at every call site costs the classifier loop
-// 5 %).  greedy_bc() picks the instance from cfg.libm_* (api.cpp).
+// 5 %).  greedy_bc() picks the instance from cfg.libm_* (api_loops.cpp).
 #define GLIA_DECLARE_GREEDY_BC(name) \
   int name(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier& clf, hipStream_t stream, const BcRequest& req, MergeResult* out)
 GLIA_DECLARE_GREEDY_BC(greedy_bc_generic);
@@ -212,6 +215,7 @@ int bc_feat_batch_rows(const RagArrays& rag, const BcCfg& cfg, const uint32_t* f
                        BcFeatBatchInfo* info);
 int compact_tables(const AccParams& p, uint32_t rcap, uint32_t pcap, RagArrays* out, hipStream_t stream);
 int transform_keys(const uint32_t* order, int64_t n, std::vector<uint32_t>* src, std::vector<uint32_t>* dst);
+int64_t gen_tree(const uint32_t* order, int64_t n, uint32_t* node_label, int32_t* parent, int32_t* child0, int32_t* child1, int64_t capacity);
 int transform_image(uint32_t* d_lab, int64_t n, const uint32_t* h_src, const uint32_t* h_dst, int64_t m, const uint32_t* d_mask,
                     int fill_missing, hipStream_t stream, double* ms);
 int relabel_image(uint32_t* d_lab, int64_t n, int64_t min_size, uint32_t* n_labels, hipStream_t stream);
@@ -226,9 +230,10 @@ int launch_libm_eval(int function, int variant, const double* d_in, double* d_ou
 int merge_rag_arrays(const RagArrays* parts, int n_parts, RagArrays* out, hipStream_t stream);
 // boundary-voxel values per directed pair of a map built from `vol` (its owned planes): fills rag->d_pv_off / d_pv / nV (owned)
 int collect_pair_values(RagArrays* rag, const VolumeRef& vol, hipStream_t stream);
-// value runs in a new pair order: out run j = source run order[j] (counts from the source offsets); allocates *out_off [n + 1], *out_vals
-int gather_value_runs(const unsigned long long* src_off, const float* src_vals, const uint32_t* order, uint32_t n, unsigned long long** out_off,
-                      float** out_vals, unsigned long long* nV, hipStream_t stream);
+// value runs in a new pair order: out run j = source run order[j] (counts from the source offsets); `own` allocates *out_off [n + 1], *out_vals
+struct OwnedArrays;
+int gather_value_runs(const unsigned long long* src_off, const float* src_vals, const uint32_t* order, uint32_t n, OwnedArrays& own,
+                      unsigned long long** out_off, float** out_vals, unsigned long long* nV, hipStream_t stream);
 int rag_cut_flags(const RagArrays& rag, const uint32_t* d_lab, int64_t nx, int64_t ny, int64_t nzl, int64_t zb, int64_t ze,
                   uint8_t* d_rflag, uint8_t* d_pflag, hipStream_t stream);
 

@@ -1,5 +1,5 @@
 // glia_amd/csrc/median_layout.hpp -- the column walk of GLIA_USE_MEDIAN_AS_FEATS (type/feat.hxx:677-722, 772-808; hmt/bc_feat.hxx:
-// 252-268), stated once for the host route (glia_hmt_bc_feat, api.cpp) and the device kernel (bc_init_score_median, greedy_bc.hip).
+// 252-268), stated once for the host route (glia_hmt_bc_feat, api_loops.cpp) and the device kernel (bc_init_score_median, greedy_bc.hip).
 // One more column per real-feature block: ImageRealFeats = [histogram] entropy | MEDIAN mean std | min max with mean and standard
 // deviation taken from the value vector, ImageDiffFeats = l1 x2 |d entropy| |d MEDIAN| |d mean| |d std| |d min| |d max|; the simple
 // selection carries the shared boundary's median beside its mean.

@@ -108,28 +108,30 @@ int compact_tables(const AccParams& p, uint32_t rcap, uint32_t pcap, RagArrays* 
   uint32_t* d_rk = nullptr; uint32_t* d_rs = nullptr;
   unsigned long long* d_pk = nullptr; uint32_t* d_ps = nullptr;
   DeviceBuffers buf;                               // (returns its blocks to the cache when this function ends: after the last sync)
-  int rc = sort_used<uint32_t>(buf, p.rkeys, rcap, &d_rk, &d_rs, &out->R, stream);
+  RagArrays a;
+  int rc = sort_used<uint32_t>(buf, p.rkeys, rcap, &d_rk, &d_rs, &a.R, stream);
   if (rc) return rc;
-  rc = sort_used<unsigned long long>(buf, p.pkeys, pcap, &d_pk, &d_ps, &out->P, stream);
+  rc = sort_used<unsigned long long>(buf, p.pkeys, pcap, &d_pk, &d_ps, &a.P, stream);
   if (rc) return rc;
-  const int64_t R = out->R, P = out->P;
-  GLIA_HIP_TRY(hipMalloc(&out->d_rlabel, sizeof(uint32_t) * (size_t)(R ? R : 1)));
-  GLIA_HIP_TRY(hipMalloc(&out->d_rrec, sizeof(uint32_t) * kRegionWords * (size_t)(R ? R : 1)));
-  GLIA_HIP_TRY(hipMalloc(&out->d_pa, sizeof(uint32_t) * (size_t)(P ? P : 1)));
-  GLIA_HIP_TRY(hipMalloc(&out->d_pb, sizeof(uint32_t) * (size_t)(P ? P : 1)));
-  GLIA_HIP_TRY(hipMalloc(&out->d_prec, sizeof(uint32_t) * kPairWords * (size_t)(P ? P : 1)));
+  const int64_t R = a.R, P = a.P;
+  OwnedArrays own;
+  if ((rc = own.alloc(&a.d_rlabel, (size_t)R)) || (rc = own.alloc(&a.d_rrec, kRegionWords * (size_t)(R ? R : 1))) || (rc = own.alloc(&a.d_pa, (size_t)P)) ||
+      (rc = own.alloc(&a.d_pb, (size_t)P)) || (rc = own.alloc(&a.d_prec, kPairWords * (size_t)(P ? P : 1)))) return rc;
+  a.c_rrec[0] = a.d_rrec; a.c_prec[0] = a.d_prec;
   if (R) {
-    hipLaunchKernelGGL(decode_region_keys, dim3((R + 255) / 256), dim3(256), 0, stream, d_rk, out->d_rlabel, R);
+    hipLaunchKernelGGL(decode_region_keys, dim3((R + 255) / 256), dim3(256), 0, stream, d_rk, a.d_rlabel, R);
     int64_t tot = R * kRegionWords;
-    hipLaunchKernelGGL(gather_records, dim3((tot + 255) / 256), dim3(256), 0, stream, p.rrec, d_rs, out->d_rrec, R, kRegionWords);
+    hipLaunchKernelGGL(gather_records, dim3((tot + 255) / 256), dim3(256), 0, stream, p.rrec, d_rs, a.d_rrec, R, kRegionWords);
   }
   if (P) {
-    hipLaunchKernelGGL(decode_pair_keys, dim3((P + 255) / 256), dim3(256), 0, stream, d_pk, out->d_pa, out->d_pb, P);
+    hipLaunchKernelGGL(decode_pair_keys, dim3((P + 255) / 256), dim3(256), 0, stream, d_pk, a.d_pa, a.d_pb, P);
     int64_t tot = P * kPairWords;
-    hipLaunchKernelGGL(gather_records, dim3((tot + 255) / 256), dim3(256), 0, stream, p.prec, d_ps, out->d_prec, P, kPairWords);
+    hipLaunchKernelGGL(gather_records, dim3((tot + 255) / 256), dim3(256), 0, stream, p.prec, d_ps, a.d_prec, P, kPairWords);
   }
   GLIA_HIP_TRY(hipGetLastError());
   GLIA_HIP_TRY(hipStreamSynchronize(stream));
+  own.keep();
+  *out = a;
   return GLIA_HMT_OK;
 }
 

@@ -88,14 +88,14 @@ __global__ void run_gather(const unsigned long long* src_off, const float* src_v
   out[v] = src_vals[src_off[order[lo]] + (v - new_off[lo])];
 }
 }  // namespace
-int gather_value_runs(const unsigned long long* src_off, const float* src_vals, const uint32_t* order, uint32_t n, unsigned long long** out_off,
-                      float** out_vals, unsigned long long* nV, hipStream_t stream) {
-  GLIA_HIP_TRY(hipMalloc(out_off, sizeof(unsigned long long) * ((size_t)n + 1)));
+int gather_value_runs(const unsigned long long* src_off, const float* src_vals, const uint32_t* order, uint32_t n, OwnedArrays& own,
+                      unsigned long long** out_off, float** out_vals, unsigned long long* nV, hipStream_t stream) {
+  int rc;
+  if ((rc = own.alloc(out_off, (size_t)n + 1))) return rc;
   *out_vals = nullptr; *nV = 0;
   unsigned long long total = 0;
   if (n) {
     DeviceBuffers buf;
-    int rc;
     unsigned long long* cnt;
     if ((rc = buf.get(&cnt, (size_t)n + 1, false, stream))) return rc;
     hipLaunchKernelGGL(run_counts, dim3((n + 256) / 256), dim3(256), 0, stream, src_off, order, n, cnt);
@@ -104,7 +104,7 @@ int gather_value_runs(const unsigned long long* src_off, const float* src_vals, 
     GLIA_HIP_TRY(hipMemcpyAsync(&total, *out_off + n, sizeof(total), hipMemcpyDeviceToHost, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
   } else GLIA_HIP_TRY(hipMemsetAsync(*out_off, 0, sizeof(unsigned long long), stream));
-  GLIA_HIP_TRY(hipMalloc(out_vals, sizeof(float) * (size_t)(total ? total : 1)));
+  if ((rc = own.alloc(out_vals, (size_t)total))) return rc;
   if (total) {
     hipLaunchKernelGGL(run_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src_off, src_vals, order, n, *out_off, total, *out_vals);
     GLIA_HIP_TRY(hipGetLastError());
@@ -155,22 +155,24 @@ int collect_pair_values(RagArrays* rag, const VolumeRef& vol, hipStream_t stream
   unsigned long long* cnt; uint32_t* cursor;
   if ((rc = buf.get(&cnt, (size_t)P + 1, false, stream))) return rc;
   if ((rc = buf.get(&cursor, (size_t)P + 1, true, stream))) return rc;
-  GLIA_HIP_TRY(hipMalloc(&rag->d_pv_off, sizeof(unsigned long long) * ((size_t)P + 1)));
+  OwnedArrays own;
+  unsigned long long* pv_off; float* pv;
+  if ((rc = own.alloc(&pv_off, (size_t)P + 1))) return rc;
   hipLaunchKernelGGL(pair_counts_u64, dim3((P + 256) / 256), dim3(256), 0, stream, rag->d_prec, P, cnt);
   if ((rc = rocprim_run(buf, stream, [&](void* t, size_t& b) {
-        return rocprim::exclusive_scan(t, b, cnt, rag->d_pv_off, 0ull, (size_t)P + 1, rocprim::plus<unsigned long long>(), stream); }))) return rc;
+        return rocprim::exclusive_scan(t, b, cnt, pv_off, 0ull, (size_t)P + 1, rocprim::plus<unsigned long long>(), stream); }))) return rc;
   unsigned long long total = 0;
-  GLIA_HIP_TRY(hipMemcpyAsync(&total, rag->d_pv_off + P, sizeof(total), hipMemcpyDeviceToHost, stream));
+  GLIA_HIP_TRY(hipMemcpyAsync(&total, pv_off + P, sizeof(total), hipMemcpyDeviceToHost, stream));
   GLIA_HIP_TRY(hipStreamSynchronize(stream));
-  GLIA_HIP_TRY(hipMalloc(&rag->d_pv, sizeof(float) * (size_t)(total ? total : 1)));
-  rag->nV = total;
+  if ((rc = own.alloc(&pv, (size_t)total))) return rc;
   const long long n_owned = (vol.ze - vol.zb) * vol.nx * vol.ny;
   if (total && n_owned > 0) {
-    hipLaunchKernelGGL(pair_values_scatter, dim3((unsigned)((n_owned + 255) / 256)), dim3(256), 0, stream, vol, rag->d_pa, rag->d_pb, (long long)P, rag->d_pv_off,
-                       cursor, rag->d_pv);
+    hipLaunchKernelGGL(pair_values_scatter, dim3((unsigned)((n_owned + 255) / 256)), dim3(256), 0, stream, vol, rag->d_pa, rag->d_pb, (long long)P, pv_off, cursor, pv);
     GLIA_HIP_TRY(hipGetLastError());
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
   }
+  own.keep();
+  rag->d_pv_off = pv_off; rag->d_pv = pv; rag->nV = total;
   return GLIA_HMT_OK;
 }
 namespace {
@@ -221,18 +223,19 @@ int merge_kind(const RagArrays* parts, int n_parts, RagArrays* out, hipStream_t 
     GLIA_HIP_TRY(hipMemcpyAsync(&nout, oidx + n, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
   }
+  OwnedArrays own;
+  RagArrays o = *out;                              // *out changes on success only: a caller that fails releases what it holds
   uint32_t *oa, *ob = nullptr;
-  GLIA_HIP_TRY(hipMalloc(&oa, sizeof(uint32_t) * (size_t)(nout ? nout : 1)));
-  if (!REGION) GLIA_HIP_TRY(hipMalloc(&ob, sizeof(uint32_t) * (size_t)(nout ? nout : 1)));
+  if ((rc = own.alloc(&oa, (size_t)nout)) || (!REGION && (rc = own.alloc(&ob, (size_t)nout)))) return rc;
   // the keys are shared by all image channels; every channel's records are reduced in the same sorted order
   for (int ch = 0; ch < K; ++ch) {
     uint32_t* dst;
-    GLIA_HIP_TRY(hipMalloc(&dst, sizeof(uint32_t) * W * (size_t)(nout ? nout : 1)));
+    if ((rc = own.alloc(&dst, W * (size_t)(nout ? nout : 1)))) return rc;
     uint32_t b2 = 0;
     for (int p = 0; p < n_parts; ++p) {
       const uint32_t m = (uint32_t)(REGION ? parts[p].R : parts[p].P);
       if (!m) continue;
-      const uint32_t* rec = REGION ? (ch == 0 ? parts[p].d_rrec : parts[p].c_rrec[ch]) : (ch == 0 ? parts[p].d_prec : parts[p].c_prec[ch]);
+      const uint32_t* rec = REGION ? parts[p].c_rrec[ch] : parts[p].c_prec[ch];
       GLIA_HIP_TRY(hipMemcpyAsync(src + (size_t)b2 * W, rec, sizeof(uint32_t) * (size_t)m * W, hipMemcpyDeviceToDevice, stream));
       b2 += m;
     }
@@ -243,11 +246,11 @@ int merge_kind(const RagArrays* parts, int n_parts, RagArrays* out, hipStream_t 
       GLIA_HIP_TRY(hipGetLastError());
       GLIA_HIP_TRY(hipStreamSynchronize(stream));
     }
-    if (REGION) { out->c_rrec[ch] = dst; if (ch == 0) out->d_rrec = dst; }
-    else { out->c_prec[ch] = dst; if (ch == 0) out->d_prec = dst; }
+    if (REGION) { o.c_rrec[ch] = dst; if (ch == 0) o.d_rrec = dst; }
+    else { o.c_prec[ch] = dst; if (ch == 0) o.d_prec = dst; }
   }
-  if (REGION) { out->R = nout; out->d_rlabel = oa; }
-  else { out->P = nout; out->d_pa = oa; out->d_pb = ob; }
+  if (REGION) { o.R = nout; o.d_rlabel = oa; }
+  else { o.P = nout; o.d_pa = oa; o.d_pb = ob; }
   if (!REGION) {
     // value runs: when every part with pairs carries them, the merged pair's run is the concatenation of its sources' runs, i.e.
     // the source runs laid out in the sorted order (a merged pair's offset = the offset of its first source)
@@ -270,18 +273,20 @@ int merge_kind(const RagArrays* parts, int n_parts, RagArrays* out, hipStream_t 
       GLIA_HIP_TRY(hipMemcpyAsync(cat_off + n, &vtot, sizeof(vtot), hipMemcpyHostToDevice, stream));
       GLIA_HIP_TRY(hipStreamSynchronize(stream));      // (vtot lives on this stack)
       unsigned long long* gscan; float* vals; unsigned long long nV = 0;
-      if ((rc = gather_value_runs(cat_off, cat_vals, i1, n, &gscan, &vals, &nV, stream))) return rc;
+      if ((rc = gather_value_runs(cat_off, cat_vals, i1, n, own, &gscan, &vals, &nV, stream))) return rc;
       unsigned long long* ooff;
-      GLIA_HIP_TRY(hipMalloc(&ooff, sizeof(unsigned long long) * ((size_t)nout + 1)));
+      if ((rc = own.alloc(&ooff, (size_t)nout + 1))) return rc;
       hipLaunchKernelGGL(merged_offsets, dim3((n + 255) / 256), dim3(256), 0, stream, flag, oidx, gscan, n, nout, nV, ooff);
       GLIA_HIP_TRY(hipGetLastError());
       GLIA_HIP_TRY(hipStreamSynchronize(stream));
-      (void)hipFree(gscan);
-      out->d_pv_off = ooff; out->d_pv = vals; out->nV = nV;
+      own.free_one(gscan);
+      o.d_pv_off = ooff; o.d_pv = vals; o.nV = nV;
     }
   }
-  out->K = K;
-  for (int ch = 0; ch < K; ++ch) out->c_bins[ch] = parts[0].c_bins[ch];
+  o.K = K;
+  for (int ch = 0; ch < K; ++ch) o.c_bins[ch] = parts[0].c_bins[ch];
+  own.keep();
+  *out = o;
   return GLIA_HMT_OK;
 }
 

@@ -109,14 +109,14 @@ __global__ void paint_pairs_kernel(VolumeRef vol, const uint32_t* pa, const uint
 
 int paint_pair_values(const VolumeRef& vol, const uint32_t* d_pa, const uint32_t* d_pb, int64_t P, const float* h_val, float* d_out,
                       hipStream_t stream) {
+  OwnedArrays own;
   float* d_val = nullptr;
-  GLIA_HIP_TRY(hipMalloc(&d_val, sizeof(float) * (size_t)(P ? P : 1)));
+  if (int rc = own.alloc(&d_val, (size_t)P)) return rc;
   GLIA_HIP_TRY(hipMemcpyAsync(d_val, h_val, sizeof(float) * (size_t)P, hipMemcpyHostToDevice, stream));
   const long long N = vol.nx * vol.ny * vol.nz;
   hipLaunchKernelGGL(paint_pairs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, vol, d_pa, d_pb, (long long)P, d_val, d_out);
   GLIA_HIP_TRY(hipGetLastError());
   GLIA_HIP_TRY(hipStreamSynchronize(stream));
-  (void)hipFree(d_val);
   return GLIA_HMT_OK;
 }
 
@@ -177,25 +177,26 @@ int transform_image(uint32_t* d_lab, int64_t n, const uint32_t* h_src, const uin
   }
   const uint32_t maxsrc = s.empty() ? 0u : s.back();
   const bool dense = maxsrc < kDenseLimit;
+  OwnedArrays own;
   uint32_t *da = nullptr, *db = nullptr;
   uint32_t mm = 0;
+  int rc;
   if (dense) {
     std::vector<uint32_t> lut((size_t)maxsrc + 1, kNoMap);
     for (size_t i = 0; i < s.size(); ++i) lut[s[i]] = d[i];
     mm = maxsrc + 1;
-    GLIA_HIP_TRY(hipMalloc(&da, sizeof(uint32_t) * lut.size()));
+    if ((rc = own.alloc(&da, lut.size()))) return rc;
     GLIA_HIP_TRY(hipMemcpyAsync(da, lut.data(), sizeof(uint32_t) * lut.size(), hipMemcpyHostToDevice, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
   } else {
     mm = (uint32_t)s.size();
-    GLIA_HIP_TRY(hipMalloc(&da, sizeof(uint32_t) * s.size()));
-    GLIA_HIP_TRY(hipMalloc(&db, sizeof(uint32_t) * s.size()));
+    if ((rc = own.alloc(&da, s.size())) || (rc = own.alloc(&db, s.size()))) return rc;
     GLIA_HIP_TRY(hipMemcpyAsync(da, s.data(), sizeof(uint32_t) * s.size(), hipMemcpyHostToDevice, stream));
     GLIA_HIP_TRY(hipMemcpyAsync(db, d.data(), sizeof(uint32_t) * s.size(), hipMemcpyHostToDevice, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
   }
   CallEvents<2> ev;
-  if (int rc = ev.create()) return rc;
+  if ((rc = ev.create())) return rc;
   // The first launch of a kernel of this translation unit loads its code object (this file's holds rocPRIM's sorts since the sparse
   // relabelling path of round 3: several milliseconds) -- on the host, between the two events.  Asking for the kernel's attributes loads it
   // here, so that the reported time is the kernel's (round 3's closing set reported 12.0 ms for a 4 ms kernel; tools/transform_bench.py).
@@ -212,22 +213,22 @@ int transform_image(uint32_t* d_lab, int64_t n, const uint32_t* h_src, const uin
   GLIA_HIP_TRY(hipEventRecord(ev.ev[1], stream));
   GLIA_HIP_TRY(hipEventSynchronize(ev.ev[1]));
   if (ms) *ms = ev.ms(0, 1);
-  (void)hipFree(da);
-  if (db) (void)hipFree(db);
+  own.free_all();                                // (before the events go, as ever)
   return GLIA_HMT_OK;
 }
 
 int relabel_image(uint32_t* d_lab, int64_t n, int64_t min_size, uint32_t* n_labels, hipStream_t stream) {
   *n_labels = 0;
   if (n == 0) return GLIA_HMT_OK;
+  OwnedArrays own;
   uint32_t* d_max;
-  GLIA_HIP_TRY(hipMalloc(&d_max, sizeof(uint32_t)));
+  if (int rc = own.alloc(&d_max, 1)) return rc;
   GLIA_HIP_TRY(hipMemsetAsync(d_max, 0, sizeof(uint32_t), stream));
   hipLaunchKernelGGL(max_label_kernel, dim3(2048), dim3(256), 0, stream, d_lab, (long long)n, d_max);
   uint32_t maxl = 0;
   GLIA_HIP_TRY(hipMemcpyAsync(&maxl, d_max, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
   GLIA_HIP_TRY(hipStreamSynchronize(stream));
-  (void)hipFree(d_max);
+  own.free_all();
   std::vector<uint32_t> labs;                   // labels present (not 0), and their voxel counts
   std::vector<unsigned long long> cntOf;
   if (maxl >= kDenseLimit) {
@@ -235,24 +236,24 @@ int relabel_image(uint32_t* d_lab, int64_t n, int64_t min_size, uint32_t* n_labe
     // run-length interface takes a 32-bit size and returns 32-bit counts: larger volumes are refused, not truncated
     if (n > 0xFFFFFFFFll) { set_error("relabel_image: labels >= 2^28 in a volume of more than 2^32 - 1 voxels are not supported"); return GLIA_HMT_ERR_UNSUPPORTED; }
     uint32_t *d_a = nullptr, *d_b = nullptr, *d_u = nullptr, *d_c = nullptr, *d_nr = nullptr;
-    void* d_tmp = nullptr;
-    auto freeAll = [&]() { for (void* q : {(void*)d_a, (void*)d_b, (void*)d_u, (void*)d_c, (void*)d_nr, d_tmp}) if (q) (void)hipFree(q); };
-    auto fail = [&](hipError_t e) { freeAll(); set_error(std::string("relabel_image: ") + hipGetErrorString(e)); return GLIA_HMT_ERR_HIP; };
+    char* d_tmp = nullptr;
+    auto fail = [&](hipError_t e) { set_error(std::string("relabel_image: ") + hipGetErrorString(e)); return GLIA_HMT_ERR_HIP; };
     hipError_t e;
-    if ((e = hipMalloc(&d_a, sizeof(uint32_t) * (size_t)n)) != hipSuccess || (e = hipMalloc(&d_b, sizeof(uint32_t) * (size_t)n)) != hipSuccess) return fail(e);
+    int rc;
+    if ((rc = own.alloc(&d_a, (size_t)n)) || (rc = own.alloc(&d_b, (size_t)n))) return rc;
     if ((e = hipMemcpyAsync(d_a, d_lab, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, stream)) != hipSuccess) return fail(e);
     size_t tmp_bytes = 0;
     if ((e = rocprim::radix_sort_keys(nullptr, tmp_bytes, d_a, d_b, (size_t)n, 0, 32, stream)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16)) != hipSuccess) return fail(e);
+    if ((rc = own.alloc(&d_tmp, tmp_bytes ? tmp_bytes : 16))) return rc;
     if ((e = rocprim::radix_sort_keys(d_tmp, tmp_bytes, d_a, d_b, (size_t)n, 0, 32, stream)) != hipSuccess) return fail(e);
-    (void)hipFree(d_tmp); d_tmp = nullptr;
+    own.free_one(d_tmp);
     // run lengths: unique labels into d_a (reused), counts into d_c; a run has at most n <= 2^32 - 1... counts are 32-bit in
     // rocPRIM's interface: volumes beyond 2^32 voxels of ONE label are out of reach of this path
-    if ((e = hipMalloc(&d_c, sizeof(uint32_t) * (size_t)n)) != hipSuccess || (e = hipMalloc(&d_nr, sizeof(uint32_t))) != hipSuccess) return fail(e);
-    d_u = d_a; d_a = nullptr;
+    if ((rc = own.alloc(&d_c, (size_t)n)) || (rc = own.alloc(&d_nr, 1))) return rc;
+    d_u = d_a;
     tmp_bytes = 0;
     if ((e = rocprim::run_length_encode(nullptr, tmp_bytes, d_b, (unsigned int)n, d_u, d_c, d_nr, stream)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16)) != hipSuccess) return fail(e);
+    if ((rc = own.alloc(&d_tmp, tmp_bytes ? tmp_bytes : 16))) return rc;
     if ((e = rocprim::run_length_encode(d_tmp, tmp_bytes, d_b, (unsigned int)n, d_u, d_c, d_nr, stream)) != hipSuccess) return fail(e);
     uint32_t nr = 0;
     if ((e = hipMemcpyAsync(&nr, d_nr, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) != hipSuccess || (e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e);
@@ -261,18 +262,18 @@ int relabel_image(uint32_t* d_lab, int64_t n, int64_t min_size, uint32_t* n_labe
       if ((e = hipMemcpy(u.data(), d_u, sizeof(uint32_t) * nr, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e);
       if ((e = hipMemcpy(c32.data(), d_c, sizeof(uint32_t) * nr, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e);
     }
-    freeAll();
+    own.free_all();
     for (uint32_t i = 0; i < nr; ++i) if (u[i] != 0u) { labs.push_back(u[i]); cntOf.push_back(c32[i]); }
   } else {
   unsigned long long* d_cnt;
-  GLIA_HIP_TRY(hipMalloc(&d_cnt, sizeof(unsigned long long) * ((size_t)maxl + 1)));
+  if (int rc = own.alloc(&d_cnt, (size_t)maxl + 1)) return rc;
   GLIA_HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * ((size_t)maxl + 1), stream));
   const long long threads = (n + 7) / 8;
   hipLaunchKernelGGL(count_labels_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, d_lab, (long long)n, d_cnt);
   std::vector<unsigned long long> cnt((size_t)maxl + 1);
   GLIA_HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost, stream));
   GLIA_HIP_TRY(hipStreamSynchronize(stream));
-  (void)hipFree(d_cnt);
+  own.free_all();
   for (uint32_t l = 1; l <= maxl; ++l) if (cnt[l]) { labs.push_back(l); cntOf.push_back(cnt[l]); }
   }
   // RelabelComponentImageFilter: objects (label != 0) sorted by size, largest first, ties by the smaller original

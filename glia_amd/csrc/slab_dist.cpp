@@ -99,14 +99,14 @@ int all_gather_u64(glia_hmt_comm* cm, const std::vector<std::vector<uint64_t>>& 
   for (size_t i = 0; i < cm->local.size(); ++i) std::copy(mine[i].begin(), mine[i].end(), all->begin() + (size_t)cm->local[i] * n);
   if (!cm->nccl || cm->world == 1) return GLIA_HMT_OK;
   hipStream_t s = cm->ctx->stream;
+  OwnedArrays own;
   uint64_t *d_in = nullptr, *d_out = nullptr;
-  GLIA_HIP_TRY(hipMalloc(&d_in, sizeof(uint64_t) * n));
-  GLIA_HIP_TRY(hipMalloc(&d_out, sizeof(uint64_t) * n * cm->world));
+  if (int rc = own.alloc(&d_in, (size_t)n)) return rc;
+  if (int rc = own.alloc(&d_out, (size_t)n * cm->world)) return rc;
   GLIA_HIP_TRY(hipMemcpyAsync(d_in, mine[0].data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
   GLIA_NCCL_TRY(g_rccl.AllGather(d_in, d_out, (size_t)n, ncclUint64, cm->nccl, s));
   GLIA_HIP_TRY(hipMemcpyAsync(all->data(), d_out, sizeof(uint64_t) * n * cm->world, hipMemcpyDeviceToHost, s));
   GLIA_HIP_TRY(hipStreamSynchronize(s));
-  (void)hipFree(d_in); (void)hipFree(d_out);
   return GLIA_HMT_OK;
 }
 
@@ -130,8 +130,7 @@ __global__ void permute_rows(const uint32_t* src, const uint32_t* idx, uint32_t 
 struct Sorted {                 // one rank's records in destination order (owned device arrays), counts per destination [world + 1]
   RagArrays arr;
   std::vector<uint64_t> rcount, pcount, vcount;      // vcount: boundary values per destination (0 without value runs)
-  std::vector<void*> owned;
-  void release() { for (void* p : owned) (void)hipFree(p); owned.clear(); }
+  OwnedArrays owned;
 };
 
 int sort_by_destination(const RagArrays& a, const uint8_t* d_rcut, const uint8_t* d_pcut, int world, hipStream_t s, Sorted* out) {
@@ -141,14 +140,13 @@ int sort_by_destination(const RagArrays& a, const uint8_t* d_rcut, const uint8_t
     const uint32_t n = (uint32_t)(kind ? a.P : a.R);
     std::vector<uint64_t>& cnt = kind ? out->pcount : out->rcount;
     cnt.assign((size_t)world + 1, 0);
-    auto alloc = [&](uint32_t** p, size_t words) -> int { GLIA_HIP_TRY(hipMalloc(p, sizeof(uint32_t) * (words ? words : 1))); out->owned.push_back(*p); return GLIA_HMT_OK; };
     uint32_t *lab = nullptr, *lab2 = nullptr;
     int rc;
-    if ((rc = alloc(&lab, n))) return rc;
-    if (kind && (rc = alloc(&lab2, n))) return rc;
+    if ((rc = out->owned.alloc(&lab, n))) return rc;
+    if (kind && (rc = out->owned.alloc(&lab2, n))) return rc;
     uint32_t* recs[kMaxChannels] = {nullptr, nullptr, nullptr, nullptr};
     const int W = kind ? kPairWords : kRegionWords;
-    for (int c = 0; c < a.K; ++c) if ((rc = alloc(&recs[c], (size_t)n * W))) return rc;
+    for (int c = 0; c < a.K; ++c) if ((rc = out->owned.alloc(&recs[c], (size_t)n * W))) return rc;
     if (n) {
       DeviceBuffers buf;
       uint32_t *k0, *k1, *i0, *i1, *d_cnt;
@@ -180,8 +178,7 @@ int sort_by_destination(const RagArrays& a, const uint8_t* d_rcut, const uint8_t
             (rc = buf2.get(&d_cnt, (size_t)world + 1, true, s))) return rc;
         hipLaunchKernelGGL(dest_keys, dim3((n + 255) / 256), dim3(256), 0, s, a.d_pa, d_pcut, n, (uint32_t)world, k0, i0, d_cnt);
         if ((rc = rocprim_run(buf2, s, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, k0, k1, i0, i1, (size_t)n, 0, 16, s); }))) return rc;
-        if ((rc = gather_value_runs(a.d_pv_off, a.d_pv, i1, n, &out->arr.d_pv_off, &out->arr.d_pv, &out->arr.nV, s))) return rc;
-        out->owned.push_back(out->arr.d_pv_off); out->owned.push_back(out->arr.d_pv);
+        if ((rc = gather_value_runs(a.d_pv_off, a.d_pv, i1, n, out->owned, &out->arr.d_pv_off, &out->arr.d_pv, &out->arr.nV, s))) return rc;
         std::vector<unsigned long long> off((size_t)n + 1);
         GLIA_HIP_TRY(hipMemcpy(off.data(), out->arr.d_pv_off, sizeof(unsigned long long) * off.size(), hipMemcpyDeviceToHost));
         uint64_t p0 = 0;
@@ -204,6 +201,7 @@ struct Block {
   uint32_t* pa() const { return base + R * (1 + (size_t)K * kRegionWords); }
   uint32_t* pb() const { return pa() + P; }
   uint32_t* prec(int c) const { return pb() + P + (size_t)c * P * kPairWords; }
+  // a NON-OWNING view (the only place that makes one): the block belongs to whoever allocated `base`; never free_rag_arrays() it
   RagArrays view(const RagArrays& like) const {
     RagArrays a; a.R = (int64_t)R; a.P = (int64_t)P; a.K = K;
     a.d_rlabel = rlabel(); a.d_pa = pa(); a.d_pb = pb();
@@ -219,14 +217,13 @@ __global__ void block_counts(const uint32_t* prec, uint32_t P, unsigned long lon
   if (i > P) return;
   cnt[i] = i < P ? (unsigned long long)prec[(size_t)i * kPairWords + P_CNT] : 0ull;
 }
-int block_value_offsets(Block* b, hipStream_t s, std::vector<void*>* scratch) {
+int block_value_offsets(Block* b, hipStream_t s, OwnedArrays& scratch) {
   const uint32_t P = (uint32_t)b->P;
   DeviceBuffers buf;
   int rc;
   unsigned long long* cnt;
   if ((rc = buf.get(&cnt, (size_t)P + 1, false, s))) return rc;
-  GLIA_HIP_TRY(hipMalloc(&b->pv_off, sizeof(unsigned long long) * ((size_t)P + 1)));
-  scratch->push_back(b->pv_off);
+  if ((rc = scratch.alloc(&b->pv_off, (size_t)P + 1))) return rc;
   hipLaunchKernelGGL(block_counts, dim3((P + 256) / 256), dim3(256), 0, s, b->prec(0), P, cnt);
   if ((rc = rocprim_run(buf, s, [&](void* t, size_t& bytes) {
         return rocprim::exclusive_scan(t, bytes, cnt, b->pv_off, 0ull, (size_t)P + 1, rocprim::plus<unsigned long long>(), s); }))) return rc;
@@ -247,13 +244,8 @@ void add_record_transfers(std::vector<Transfer>* ts, int src, int dst, const Rag
   if (nV) add(from ? reinterpret_cast<const uint32_t*>(from->d_pv) : nullptr, v0, 1, nV, to ? reinterpret_cast<uint32_t*>(to->pv()) : nullptr);
 }
 
-void free_arrays(RagArrays* a) {
-  (void)hipFree(a->d_rlabel); (void)hipFree(a->d_pa); (void)hipFree(a->d_pb);
-  if (a->d_pv_off) (void)hipFree(a->d_pv_off);
-  if (a->d_pv) (void)hipFree(a->d_pv);
-  for (int c = 0; c < a->K; ++c) { (void)hipFree(a->c_rrec[c]); (void)hipFree(a->c_prec[c]); }
-  *a = RagArrays();
-}
+// a release bound to the scope: runs however the function returns
+template <class F> struct AtExit { F f; explicit AtExit(F g) : f(g) {} AtExit(const AtExit&) = delete; ~AtExit() { f(); } };
 
 }  // namespace
 
@@ -329,32 +321,28 @@ int glia_hmt_rag_build_distributed(glia_hmt_ctx* c, glia_hmt_comm* cm, const gli
   memset(&st, 0, sizeof(st));
   int rc = GLIA_HMT_OK;
   // ---- 1. partial maps, cut flags, records in destination order ----
-  std::vector<glia_hmt_rag*> part((size_t)nl, nullptr);
-  std::vector<Sorted> sorted((size_t)nl);
-  std::vector<void*> scratch;
+  // (released in the reverse order: the partial maps, the sorted records, the scratch blocks, the reduced arrays)
   std::vector<RagArrays> reduced((size_t)nl);
+  AtExit free_reduced([&] { for (RagArrays& a : reduced) free_rag_arrays(&a); });
+  OwnedArrays scratch;
+  std::vector<Sorted> sorted((size_t)nl);
+  std::vector<glia_hmt_rag*> part((size_t)nl, nullptr);
+  AtExit free_parts([&] { for (glia_hmt_rag* p : part) glia_hmt_rag_free(p); });
   std::vector<std::vector<Block>> recvA((size_t)nl), recvB;
-  auto cleanup = [&]() {
-    for (glia_hmt_rag* p : part) if (p) glia_hmt_rag_free(p);
-    for (Sorted& x : sorted) x.release();
-    for (void* p : scratch) (void)hipFree(p);
-    for (RagArrays& a : reduced) if (a.d_rlabel) free_arrays(&a);
-  };
   for (int i = 0; i < nl && !rc; ++i) {
     const glia_hmt_slab& sl = slabs[i];
     rc = glia_hmt_rag_build_slab(c, sl.dims_local, sl.z_global_of_plane0, nz_global, sl.z_begin, sl.z_end, sl.d_labels, only_contour, sl.d_pb, sl.cfg, &part[i]);
     if (rc) break;
     const RagArrays& a = part[i]->arr;
     uint8_t *rcut = nullptr, *pcut = nullptr;
-    if (hipMalloc(&rcut, (size_t)(a.R ? a.R : 1)) != hipSuccess || hipMalloc(&pcut, (size_t)(a.P ? a.P : 1)) != hipSuccess) { set_error("rag_build_distributed: out of memory"); rc = GLIA_HMT_ERR_HIP; break; }
-    scratch.push_back(rcut); scratch.push_back(pcut);
+    if (scratch.alloc(&rcut, (size_t)a.R) || scratch.alloc(&pcut, (size_t)a.P)) { set_error("rag_build_distributed: out of memory"); rc = GLIA_HMT_ERR_HIP; break; }
     rc = rag_cut_flags(a, sl.d_labels, sl.dims_local[0], sl.dims_local[1], sl.dims_local[2], sl.z_begin, sl.z_end, rcut, pcut, s);
     // median linkage downstream: the image value of every boundary voxel goes along with its directed pair
     if (!rc && with_values) rc = collect_pair_values(&part[i]->arr, part[i]->slab, s);
     if (!rc) rc = sort_by_destination(part[i]->arr, rcut, pcut, world, s, &sorted[i]);
     st.records += (uint64_t)(a.R + a.P);
   }
-  if (rc) { cleanup(); return rc; }
+  if (rc) return rc;
   const int K = part[0]->arr.K;
   // counts of every (source, destination): [world][2 * (world + 1)]
   std::vector<std::vector<uint64_t>> mine((size_t)nl);
@@ -365,7 +353,7 @@ int glia_hmt_rag_build_distributed(glia_hmt_ctx* c, glia_hmt_comm* cm, const gli
     mine[i].insert(mine[i].end(), sorted[i].vcount.begin(), sorted[i].vcount.end());
   }
   std::vector<uint64_t> cnt;
-  if ((rc = all_gather_u64(cm, mine, ncol, &cnt))) { cleanup(); return rc; }
+  if ((rc = all_gather_u64(cm, mine, ncol, &cnt))) return rc;
   auto cR = [&](int src, int d) { return cnt[(size_t)src * ncol + d]; };
   auto cP = [&](int src, int d) { return cnt[(size_t)src * ncol + (world + 1) + d]; };
   auto cV = [&](int src, int d) { return cnt[(size_t)src * ncol + 2 * (world + 1) + d]; };
@@ -384,8 +372,7 @@ int glia_hmt_rag_build_distributed(glia_hmt_ctx* c, glia_hmt_comm* cm, const gli
         if (ld >= 0) {
           Block& b = recvA[ld][src];
           b.R = nR; b.P = nP; b.V = nV; b.K = K;
-          if (hipMalloc(&b.base, sizeof(uint32_t) * (Block::words(nR, nP, K, nV) + 1)) != hipSuccess) { set_error("rag_build_distributed: out of memory"); cleanup(); return GLIA_HMT_ERR_HIP; }
-          scratch.push_back(b.base);
+          if (scratch.alloc(&b.base, Block::words(nR, nP, K, nV) + 1)) { set_error("rag_build_distributed: out of memory"); return GLIA_HMT_ERR_HIP; }
           to = &b;
         }
         add_record_transfers(&ts, src, d, li >= 0 ? &sorted[li].arr : nullptr, r0, nR, p0, nP, to, K, v0, nV);
@@ -393,22 +380,22 @@ int glia_hmt_rag_build_distributed(glia_hmt_ctx* c, glia_hmt_comm* cm, const gli
       }
     }
     uint64_t sent = 0;
-    if ((rc = run_transfers(cm, ts, &sent))) { cleanup(); return rc; }
+    if ((rc = run_transfers(cm, ts, &sent))) return rc;
     st.bytes_cut_exchange = sent;
     if (with_values)
-      for (int i = 0; i < nl; ++i) for (int src = 0; src < world; ++src) if (recvA[i][src].P && (rc = block_value_offsets(&recvA[i][src], s, &scratch))) { cleanup(); return rc; }
+      for (int i = 0; i < nl; ++i) for (int src = 0; src < world; ++src) if (recvA[i][src].P && (rc = block_value_offsets(&recvA[i][src], s, scratch))) return rc;
   }
   for (int i = 0; i < nl; ++i) {
     std::vector<RagArrays> parts;
     for (int src = 0; src < world; ++src) if (recvA[i][src].R || recvA[i][src].P) parts.push_back(recvA[i][src].view(part[0]->arr));
     if (parts.empty()) { reduced[i] = RagArrays(); reduced[i].K = K; continue; }
-    if ((rc = merge_rag_arrays(parts.data(), (int)parts.size(), &reduced[i], s))) { cleanup(); return rc; }
+    if ((rc = merge_rag_arrays(parts.data(), (int)parts.size(), &reduced[i], s))) return rc;
   }
   // ---- 3. everything once to the loop owner, final reduction by key ----
   std::vector<std::vector<uint64_t>> mine2((size_t)nl);
   for (int i = 0; i < nl; ++i) mine2[i] = {(uint64_t)reduced[i].R, (uint64_t)reduced[i].P, (uint64_t)reduced[i].nV};
   std::vector<uint64_t> cnt2;
-  if ((rc = all_gather_u64(cm, mine2, 3, &cnt2))) { cleanup(); return rc; }
+  if ((rc = all_gather_u64(cm, mine2, 3, &cnt2))) return rc;
   const bool own = cm->is_local(loop_owner);
   std::vector<Block> fin;
   {
@@ -426,8 +413,7 @@ int glia_hmt_rag_build_distributed(glia_hmt_ctx* c, glia_hmt_comm* cm, const gli
         if (own) {
           Block& b = fin[(size_t)2 * src + piece];
           b.R = nR; b.P = nP; b.V = nV; b.K = K;
-          if (hipMalloc(&b.base, sizeof(uint32_t) * (Block::words(nR, nP, K, nV) + 1)) != hipSuccess) { set_error("rag_build_distributed: out of memory"); cleanup(); return GLIA_HMT_ERR_HIP; }
-          scratch.push_back(b.base);
+          if (scratch.alloc(&b.base, Block::words(nR, nP, K, nV) + 1)) { set_error("rag_build_distributed: out of memory"); return GLIA_HMT_ERR_HIP; }
           to = &b;
         }
         const RagArrays* from = li < 0 ? nullptr : (piece ? &reduced[li] : &sorted[li].arr);
@@ -435,27 +421,25 @@ int glia_hmt_rag_build_distributed(glia_hmt_ctx* c, glia_hmt_comm* cm, const gli
       }
     }
     uint64_t sent = 0;
-    if ((rc = run_transfers(cm, ts, &sent))) { cleanup(); return rc; }
+    if ((rc = run_transfers(cm, ts, &sent))) return rc;
     st.bytes_to_loop_owner = sent;
     if (own && with_values)
-      for (Block& b : fin) if (b.P && (rc = block_value_offsets(&b, s, &scratch))) { cleanup(); return rc; }
+      for (Block& b : fin) if (b.P && (rc = block_value_offsets(&b, s, scratch))) return rc;
   }
   if (own) {
     std::vector<RagArrays> parts;
     for (const Block& b : fin) if (b.R || b.P) parts.push_back(b.view(part[0]->arr));
-    glia_hmt_rag* rag = new glia_hmt_rag(*part[0]);
-    rag->arr = RagArrays(); rag->arr.K = K;
-    rag->d_folded = nullptr; rag->vol = VolumeRef(); rag->slab = VolumeRef();
+    glia_hmt_rag* rag = rag_like(part[0]);
+    rag->arr.K = K;
     rag->dims[2] = nz_global;
     rag->pass_ms = 0; rag->alg_bytes = 0;
     for (glia_hmt_rag* p : part) { rag->pass_ms += p->pass_ms; rag->alg_bytes += p->alg_bytes; }
     if (!parts.empty()) rc = merge_rag_arrays(parts.data(), (int)parts.size(), &rag->arr, s);
-    if (rc) { delete rag; cleanup(); return rc; }
+    if (rc) { glia_hmt_rag_free(rag); return rc; }
     for (int ch = 0; ch < kMaxChannels; ++ch) rag->arr.c_bins[ch] = part[0]->arr.c_bins[ch];
     *out = rag;
   }
   GLIA_HIP_TRY(hipStreamSynchronize(s));
-  cleanup();
   if (stats) *stats = st;
   return GLIA_HMT_OK;
 }

@@ -101,6 +101,29 @@ int boundary_confidence_values(int n_trees, const int64_t* n_nodes, const uint32
   return GLIA_HMT_OK;
 }
 
+// hmt::genTree (hmt/tree_build.hxx:12-38): order -> array tree, children before parents; the node count, or an error code
+int64_t gen_tree(const uint32_t* h_order, int64_t n_merges, uint32_t* node_label, int32_t* parent, int32_t* child0, int32_t* child1, int64_t capacity) {
+  std::unordered_map<uint32_t, int> nmap;
+  int64_t ni = 0;
+  auto add = [&](uint32_t label, int c0, int c1) -> int64_t {
+    if (ni >= capacity) return -1;
+    node_label[ni] = label; parent[ni] = -1; child0[ni] = c0; child1[ni] = c1;
+    nmap.emplace(label, (int)ni);
+    return ni++;
+  };
+  for (int64_t i = 0; i < n_merges; ++i) {
+    const uint32_t x0 = h_order[3 * i], x1 = h_order[3 * i + 1], x2 = h_order[3 * i + 2];
+    auto n0 = nmap.find(x0);
+    int64_t i0 = n0 == nmap.end() ? add(x0, -1, -1) : n0->second;
+    auto n1 = nmap.find(x1);
+    int64_t i1 = n1 == nmap.end() ? add(x1, -1, -1) : n1->second;
+    if (i0 < 0 || i1 < 0 || ni >= capacity) { set_error("gen_tree: output capacity too small"); return GLIA_HMT_ERR_CAPACITY; }
+    parent[i0] = (int32_t)ni; parent[i1] = (int32_t)ni;
+    add(x2, (int)i0, (int)i1);
+  }
+  return ni;
+}
+
 }  // namespace glia
 
 // segment_ccm: the saturating sum and the node energy

@@ -383,6 +383,66 @@ def test_slab_partials_with_two_image_channels(ctx):
     o1, s1 = whole.merge_order_bc(clf)
     o2, s2 = merged.merge_order_bc(clf)
     assert (o1 == o2).all() and (s1 == s2).all()
+    # the channel invariant as callers see it: channel 0 of every producer's map IS the record arrays copy_arrays hands out
+    for what, rm in (("built", whole), ("merged", merged), ("from_tensors", rebuilt[0])):
+        t = rm.to_tensors()
+        r0, p0 = torch.full_like(t["rrec"], -1), torch.full_like(t["prec"], -1)
+        torch.cuda.synchronize()                                                    # (the library copies on its own stream)
+        assert hmt.lib().glia_hmt_rag_copy_channel(rm.h, 0, hmt.C.c_void_p(r0.data_ptr()), hmt.C.c_void_p(p0.data_ptr())) == 0, what
+        assert r0.cpu().numpy().tobytes() == t["rrec"].cpu().numpy().tobytes() and p0.cpu().numpy().tobytes() == t["prec"].cpu().numpy().tobytes(), what
+    # ... and both bc_feat routes read every channel of the merged map alike
+    assert merged.bc_feat_batch(o2).tobytes() == merged.bc_feat(o2).tobytes()
+
+
+def test_a_failed_call_leaves_the_context_and_communicator_usable(ctx):
+    """A call that fails half-way -- glia_hmt_rag_build_distributed after slab 0's partial map, cut flags and sorted records exist,
+    glia_hmt_rag_merge on parts that do not belong together -- returns its status and message, and the same context (and
+    communicator) then runs the correct call to the bit-identical whole map, both channels.  (16, 20, 24) with S = 6 and two slabs:
+    the smallest volume that gives every slab owned planes plus a halo plane and several regions that cross the cut."""
+    torch = _torch()
+    from glia_amd import hmt
+    from oracle import pyoracle as O
+    shape, world = (16, 20, 24), 2
+    labels, pb = O.synth(shape, 6, 12)
+    raw = (np.round(np.random.default_rng(11).random(shape) * 255) / 256.0).astype(np.float32)
+    d_lab = torch.from_numpy(labels.view(np.int32)).cuda()
+    d_pb, d_raw = torch.from_numpy(pb).cuda(), torch.from_numpy(raw).cuda()
+    mk = lambda p_, r_, bins=8: hmt.make_config(p_, rb=[(r_, bins, 0.0, 1.0), (p_, bins, 0.0, 1.0)])
+    want = hmt.RegionMap(ctx, d_lab, pb=d_pb, cfg=mk(d_pb, d_raw)).to_tensors()
+    assert "rrec1" in want and "prec1" in want
+
+    def same_as_whole(rm):
+        got = rm.to_tensors()
+        assert got.keys() == want.keys()
+        for k in want:
+            assert torch.equal(got[k], want[k]), k
+
+    comm = hmt.Comm(ctx, world)
+    slabs, planes = [], []
+    for r in range(world):
+        first, n, zb, ze = hmt.slab_range(shape[0], world, r)
+        assert 0 < ze - zb < n                                                      # owned planes and a halo plane
+        sl, sp, sr = d_lab[first:first + n].contiguous(), d_pb[first:first + n].contiguous(), d_raw[first:first + n].contiguous()
+        slabs.append((sl, sp, first, zb, ze, mk(sp, sr)))
+        planes.append((sl, sp, sr, first, zb, ze))
+    broken = mk(planes[1][1], planes[1][2])
+    broken.boundary[0].d_image = None                                               # slab 1: a null image in the boundary list
+    with pytest.raises(hmt.HmtError) as e:
+        hmt.build_distributed(ctx, comm, [slabs[0], slabs[1][:5] + (broken,)], shape[0])
+    assert e.value.code == hmt.ERR_ARG and "rag_build: null image in a feature list" in str(e.value)
+    merged, st = hmt.build_distributed(ctx, comm, slabs, shape[0])
+    assert st.cut_records > 0
+    same_as_whole(merged)
+    comm.close()
+    # RegionMap.merge: parts with different bins are refused, the parts that belong together then merge to the whole
+    parts = [hmt.RegionMap(ctx, sl, pb=sp, cfg=mk(sp, sr), slab=(first, shape[0], zb, ze)) for sl, sp, sr, first, zb, ze in planes]
+    sl, sp, sr, first, zb, ze = planes[1]
+    other = hmt.RegionMap(ctx, sl, pb=sp, cfg=mk(sp, sr, bins=4), slab=(first, shape[0], zb, ze))
+    with pytest.raises(hmt.HmtError) as e:
+        hmt.RegionMap.merge(ctx, [parts[0], other])
+    assert e.value.code == hmt.ERR_ARG and "rag_merge: parts do not belong together" in str(e.value)
+    same_as_whole(hmt.RegionMap.merge(ctx, parts))
+    assert hmt.Context.internal_errors() == 0
 
 
 def _mask_for(shape, seed=3):
