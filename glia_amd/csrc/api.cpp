@@ -24,7 +24,7 @@ void set_error(const std::string& msg) { g_err = msg; }
 // when the table is first used -- no entry point calls getenv() per call.
 static const char* const kOptionKeys[] = {"GLIA_HMT_PB_WINDOW", "GLIA_HMT_PB_BATCH", "GLIA_HMT_WINCAP", "GLIA_HMT_REBASE", "GLIA_HMT_HORIZON",
                                           "GLIA_HMT_FORCE_TREE", "GLIA_HMT_HELPERS", "GLIA_HMT_TRACE", "GLIA_HMT_LIBM", "GLIA_HMT_BC_NOCOMMON",
-                                          "GLIA_HMT_BC_GENERIC", "GLIA_HMT_DEBUG", "GLIA_HMT_MAXITERS", "GLIA_HMT_MINCAP", "GLIA_HMT_MEDIAN_BATCH", "GLIA_HMT_BCFEAT"};
+                                          "GLIA_HMT_BC_GENERIC", "GLIA_HMT_DEBUG", "GLIA_HMT_MAXITERS", "GLIA_HMT_MINCAP", "GLIA_HMT_MEDIAN_BATCH", "GLIA_HMT_BCFEAT", "GLIA_HMT_CC"};
 static std::mutex g_opt_mu;
 static std::unordered_map<std::string, std::string> g_opt;
 static bool g_opt_init = false;
@@ -283,6 +283,32 @@ int glia_hmt_watershed(glia_hmt_ctx* c, int dim, const int64_t dims[3], const fl
   if (!c || !dims || !d_image || !d_labels || (dim != 2 && dim != 3) || !(level >= 0.0)) { set_error("watershed: invalid argument"); return GLIA_HMT_ERR_ARG; }
   GLIA_HIP_TRY(hipSetDevice(c->device));
   return watershed_labels(dim, dims, d_image, level, d_labels, n_labels, sweeps, c->stream);
+}
+
+// labelIdentityConnectedComponents / labelConnectedComponents (util/image.hxx:331-373, :302-313); every test below comes before the
+// first HIP call
+int glia_hmt_label_components(glia_hmt_ctx* c, int dim, const int64_t dims[3], const uint32_t* d_labels_in, const uint32_t* d_mask, int mode,
+                              uint32_t* d_labels_out, uint32_t* n_components) {
+  auto bad = [](const char* what) { set_error(std::string("label_components: ") + what); return GLIA_HMT_ERR_ARG; };
+  if (!c || !dims || !d_labels_in || !d_labels_out || !n_components) return bad("ctx, dims, the two volumes and n_components must not be NULL");
+  if (dim != 2 && dim != 3) return bad("dim must be 2 or 3");
+  const uint64_t most = 0xFFFFFFFEull;                 // 2^32 - 2: 32-bit voxel indices and one free value
+  uint64_t n = 1;
+  for (int i = 0; i < dim; ++i) {
+    if (dims[i] <= 0) return bad("extents must be positive");
+    if ((uint64_t)dims[i] > most / n) return bad("between 1 and 2^32 - 2 voxels");
+    n *= (uint64_t)dims[i];
+  }
+  if (mode < GLIA_HMT_CC_IDENTITY || mode > GLIA_HMT_CC_BINARY_INVERTED) return bad("mode must be 0 (identity), 1 (binary) or 2 (binary, inverted)");
+  if (d_labels_out == d_labels_in) return bad("the volume cannot be labelled in place");
+  int route = GLIA_HMT_CC_ROUTE_TILED;
+  std::string v;
+  if (option("GLIA_HMT_CC", &v) && v != "tiled") {
+    if (v != "global") return bad(("GLIA_HMT_CC must be tiled or global, not '" + v + "'").c_str());
+    route = GLIA_HMT_CC_ROUTE_GLOBAL;
+  }
+  GLIA_HIP_TRY(hipSetDevice(c->device));
+  return label_components(dim, dims, d_labels_in, d_mask, mode, route, d_labels_out, n_components, c->stream);
 }
 
 // hmt::genTree (hmt/tree_build.hxx:12-38): order -> array tree, children before parents

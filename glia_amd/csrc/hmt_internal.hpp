@@ -226,6 +226,10 @@ int boundary_confidence_values(int n_trees, const int64_t* n_nodes, const uint32
                                int64_t P, std::vector<float>* out);
 int watershed_labels(int dim, const int64_t dims[3], const float* d_img, double level, uint32_t* d_out, uint32_t* n_labels, int* sweeps,
                      hipStream_t stream);
+// face-connected components of a label volume (components.hip); arguments validated by the caller (api.cpp), route = GLIA_HMT_CC
+enum { GLIA_HMT_CC_ROUTE_TILED = 0, GLIA_HMT_CC_ROUTE_GLOBAL = 1 };
+int label_components(int dim, const int64_t dims[3], const uint32_t* d_in, const uint32_t* d_mask, int mode, int route, uint32_t* d_out,
+                     uint32_t* n_components, hipStream_t stream);
 int launch_libm_eval(int function, int variant, const double* d_in, double* d_out, int64_t n, hipStream_t stream);
 int merge_rag_arrays(const RagArrays* parts, int n_parts, RagArrays* out, hipStream_t stream);
 // boundary-voxel values per directed pair of a map built from `vol` (its owned planes): fills rag->d_pv_off / d_pv / nV (owned)

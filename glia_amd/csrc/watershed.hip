@@ -26,6 +26,7 @@
 #include "greedy_common.hpp"
 #include "hmt_internal.hpp"
 #include "skew.hpp"
+#include "union_find.hpp"
 
 namespace glia {
 namespace {
@@ -152,24 +153,9 @@ __global__ __launch_bounds__(kWsThreads) void ws_hmin_tile(WsGrid G, const float
 
 // plateau components by union-find: comp(p) -> the smallest linear index of p's face-connected set of equal g.  One pass unites
 // every voxel with its +x / +y / +z neighbour of equal value (the larger root is linked under the smaller with atomicMin), one
-// pass flattens.
-__device__ __forceinline__ uint32_t ws_root(const uint32_t* comp, uint32_t x) {
-  for (;;) {
-    const uint32_t p = __hip_atomic_load(&comp[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (p == x) return x;
-    x = p;
-  }
-}
-__device__ __forceinline__ void ws_unite(uint32_t* comp, uint32_t a, uint32_t b) {
-  for (;;) {
-    a = ws_root(comp, a); b = ws_root(comp, b);
-    if (a == b) return;
-    if (a > b) { const uint32_t t = a; a = b; b = t; }
-    const uint32_t old = atomicMin(&comp[b], a);       // b was a root: now it points at the smaller root a
-    if (old == b) return;
-    b = old;                                           // somebody linked b meanwhile: go on from there
-  }
-}
+// pass flattens (union_find.hpp).
+__device__ __forceinline__ uint32_t ws_root(const uint32_t* comp, uint32_t x) { return uf_root<__HIP_MEMORY_SCOPE_AGENT>(comp, x); }
+__device__ __forceinline__ void ws_unite(uint32_t* comp, uint32_t a, uint32_t b) { uf_unite<__HIP_MEMORY_SCOPE_AGENT>(comp, a, b); }
 __global__ void ws_comp_unite(WsGrid G, const float* g, uint32_t* comp) {
   const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= G.n) return;

@@ -207,6 +207,25 @@ class Context:
                                         C.byref(n), C.byref(sw)))
         return out, n.value, sw.value
 
+    CC_MODES = {"identity": 0, "binary": 1, "binary_inverted": 2}
+
+    def label_components(self, labels, mask=None, mode="identity"):
+        """Face-connected components of a CUDA label tensor (uint32 payload) -> (out int32 tensor holding uint32 0..n, n), numbered
+        in raster order of their first voxel.  mode "identity" = labelIdentityConnectedComponents (util/image.hxx:331-373, equal
+        labels join), "binary" = labelConnectedComponents (util/image.hxx:302-313, non-zero voxels join), "binary_inverted" =
+        labelcc_image --invert (zero voxels join).  mask: 0 masks a voxel out.  The input is left unchanged."""
+        import torch
+        assert labels.is_cuda and labels.is_contiguous() and labels.element_size() == 4 and labels.dim() in (2, 3)
+        assert mask is None or (mask.is_cuda and mask.is_contiguous() and mask.element_size() == 4 and mask.shape == labels.shape)
+        dim, d = _dims(tuple(labels.shape))
+        out = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
+        n = C.c_uint32(0)
+        _fence(labels)
+        _check(lib().glia_hmt_label_components(self.h, C.c_int(dim), d, C.c_void_p(labels.data_ptr()),
+                                               C.c_void_p(mask.data_ptr()) if mask is not None else None, C.c_int(self.CC_MODES[mode]),
+                                               C.c_void_p(out.data_ptr()), C.byref(n)))
+        return out, n.value
+
     def set_table_hint(self, regions, pairs):
         _check(lib().glia_hmt_ctx_set_table_hint(self.h, C.c_int64(regions), C.c_int64(pairs)))
 

@@ -480,6 +480,31 @@ int glia_hmt_last_merge_timing(const glia_hmt_rag* rag, double* ms_table, double
 int glia_hmt_watershed(glia_hmt_ctx* ctx, int dim, const int64_t dims[3], const float* d_image, double level, uint32_t* d_labels,
                        uint32_t* n_labels, int* sweeps);
 
+/* ---- face-connected components of a label volume (gadget/main_labelicc_image.cxx, gadget/main_labelcc_image.cxx) ----------
+ * A component is a maximal face-connected set of voxels that take part (4 neighbours in 2D, 6 in 3D, in the reference order
+ * -x, +x, -y, +y, -z, +z of type/neighbor.hxx:72-89; the order does not influence the result).  Components are numbered
+ * 1..*n_components in raster order of their first voxel (x fastest); every other voxel gets BG_VAL (0).
+ *   GLIA_HMT_CC_IDENTITY         labelIdentityConnectedComponents (util/image.hxx:331-373, "Used to relabel 3D label sub-volume
+ *                                cut from bigger volume"): a voxel takes part if its label != 0 and it is not masked out; two
+ *                                neighbours are joined if both take part and their labels are equal.  Pinned exactly.
+ *   GLIA_HMT_CC_BINARY           labelConnectedComponents (util/image.hxx:302-313) = itk::ConnectedComponentImageFilter with
+ *                                SetFullyConnected(false): takes part if label != 0 and not masked out; neighbours are joined if
+ *                                both take part.  The partition is the filter's; ITK's label ORDER is unpinned.
+ *   GLIA_HMT_CC_BINARY_INVERTED  labelcc_image --invert (gadget/main_labelcc_image.cxx:10-18): takes part if label == 0 and not
+ *                                masked out; otherwise as GLIA_HMT_CC_BINARY.
+ * d_mask: u32 volume or NULL; MASK_OUT_VAL (0) masks a voxel out: it is never a start and never a neighbour (image.hxx:349,
+ * type/neighbor.hxx:80-86) and its output is 0.  The reference gives only the identity mode a mask; accepting one in the binary
+ * modes is an extension.  dims as for glia_hmt_watershed (dims[2] ignored when dim == 2); between 1 and 2^32 - 2 voxels.
+ * d_labels_out must not be d_labels_in: the volume cannot be labelled in place (tile borders are merged from the input labels
+ * while other workgroups already write).  GLIA_HMT_ERR_ARG, message "label_components: ...", before any HIP call for: a NULL ctx,
+ * dims, input, output or n_components; dim other than 2 or 3; a non-positive extent or a size outside the range; a mode outside
+ * 0..2; d_labels_out == d_labels_in; an unknown value of the option GLIA_HMT_CC.
+ * Option GLIA_HMT_CC = tiled (default) | global: two routes to the same bytes -- tile-local union-find in LDS, tile faces united in
+ * global memory; or every voxel pair united in global memory (the cross-check). */
+enum { GLIA_HMT_CC_IDENTITY = 0, GLIA_HMT_CC_BINARY = 1, GLIA_HMT_CC_BINARY_INVERTED = 2 };
+int glia_hmt_label_components(glia_hmt_ctx* ctx, int dim, const int64_t dims[3], const uint32_t* d_labels_in,
+                              const uint32_t* d_mask, int mode, uint32_t* d_labels_out, uint32_t* n_components);
+
 /* ---- synthetic inputs for tests / bench, generated on the device -------------- */
 int glia_hmt_synth(glia_hmt_ctx* ctx, int dim, const int64_t dims[3], int S, int G, uint64_t seed,
                    int variant, uint32_t* d_labels, float* d_pb);
