@@ -333,4 +333,30 @@ inline void loadFeatInputs(const Args& a, FeatInputs& f, int64_t zFirst = 0, int
   f.cfg.use_median_features = a.has("medf") ? flagOf(a, "medf") : 0;
 }
 
+// the image pairs of eval_ri / eval_vi (-p, -r, -m) on the device; mask[i] = NULL where image i has none
+struct EvalInputs {
+  std::vector<const uint32_t*> res, ref, mask;
+  std::vector<int64_t> voxels;
+};
+inline EvalInputs loadEvalInputs(const Args& a) {
+  const std::vector<std::string> resFiles = a.all("resImage"), refFiles = a.all("refImage"), maskFiles = a.all("mask");
+  if (resFiles.empty() || resFiles.size() != refFiles.size()) perr("Error: the numbers of proposed and reference images do not match...");
+  EvalInputs in;
+  for (size_t i = 0; i < resFiles.size(); ++i) {
+    Volume res = readMetaImage(resFiles[i], false), ref = readMetaImage(refFiles[i], false);
+    if (res.dim != ref.dim || res.size() != ref.size()) perr("Error: image sizes do not match...");
+    in.res.push_back(upload(res.u32));
+    in.ref.push_back(upload(ref.u32));
+    in.voxels.push_back((int64_t)res.size());
+    uint32_t* m = nullptr;
+    if (i < maskFiles.size()) {
+      Volume mask = readMetaImage(maskFiles[i], false);
+      if (mask.size() != res.size()) perr("Error: image sizes do not match...");
+      m = upload(mask.u32);
+    }
+    in.mask.push_back(m);
+  }
+  return in;
+}
+
 }  // namespace cli

@@ -311,6 +311,65 @@ int glia_hmt_label_components(glia_hmt_ctx* c, int dim, const int64_t dims[3], c
   return label_components(dim, dims, d_labels_in, d_mask, mode, route, d_labels_out, n_components, c->stream);
 }
 
+// the shared table of stats::pairStats / centropy / getOverlap on images (util/image_stats.hxx:122-158,248-273,308-335); every test
+// comes before the first HIP call
+static int overlap_args(const char* who, const glia_hmt_ctx* c, const uint32_t* d_a, const uint32_t* d_b, int64_t n_voxels) {
+  auto bad = [&](const char* what) { set_error(std::string(who) + ": " + what); return GLIA_HMT_ERR_ARG; };
+  if (!c) return bad("ctx must not be NULL");
+  if (!d_a || !d_b) return bad("the two label volumes must not be NULL");
+  if (n_voxels < 1 || (uint64_t)n_voxels > 0xFFFFFFFEull) return bad("between 1 and 2^32 - 2 voxels");
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_label_overlap(glia_hmt_ctx* c, const uint32_t* d_a, const uint32_t* d_b, const uint32_t* d_mask, int64_t n_voxels, int flags,
+                           glia_hmt_overlap_entry* h_entries, int64_t capacity, int64_t* n_entries) {
+  auto bad = [](const char* what) { set_error(std::string("label_overlap: ") + what); return GLIA_HMT_ERR_ARG; };
+  if (int rc = overlap_args("label_overlap", c, d_a, d_b, n_voxels)) return rc;
+  if (!n_entries) return bad("n_entries must not be NULL");
+  if (capacity < 0 || (capacity > 0 && !h_entries)) return bad("h_entries must hold `capacity` >= 0 entries");
+  if (flags & ~(GLIA_HMT_OVERLAP_DROP_ZERO_A | GLIA_HMT_OVERLAP_DROP_ZERO_B)) return bad("unknown flag bits");
+  GLIA_HIP_TRY(hipSetDevice(c->device));
+  std::vector<glia_hmt_overlap_entry> table;
+  OverlapPass pass;
+  if (int rc = label_overlap(d_a, d_b, d_mask, (unsigned long long)n_voxels, flags, c->stream, &table, &pass)) return rc;
+  c->evt = glia_hmt_eval_timing{pass.ms, (int64_t)table.size(), pass.repeats};
+  *n_entries = (int64_t)table.size();
+  if ((int64_t)table.size() > capacity) { set_error("label_overlap: " + std::to_string(table.size()) + " entries, capacity " + std::to_string(capacity)); return GLIA_HMT_ERR_CAPACITY; }
+  std::copy(table.begin(), table.end(), h_entries);
+  return GLIA_HMT_OK;
+}
+
+// operation() of gadget/main_eval_ri.cxx:9-61 and gadget/main_eval_vi.cxx:7-29: excluded0 = {}, excluded1 = {BG_VAL}
+int glia_hmt_eval(glia_hmt_ctx* c, int n_images, const uint32_t* const* d_res, const uint32_t* const* d_ref, const uint32_t* const* d_mask,
+                  const int64_t* n_voxels, int vi_mode, glia_hmt_eval_result* out) {
+  auto bad = [](const char* what) { set_error(std::string("eval: ") + what); return GLIA_HMT_ERR_ARG; };
+  if (!c) return bad("ctx must not be NULL");
+  if (n_images < 1) return bad("at least one image pair");
+  if (!d_res || !d_ref || !n_voxels || !out) return bad("d_res, d_ref, n_voxels and out must not be NULL");
+  if (vi_mode != GLIA_HMT_VI_REFERENCE && vi_mode != GLIA_HMT_VI_EXACT) return bad("vi_mode must be GLIA_HMT_VI_REFERENCE or GLIA_HMT_VI_EXACT");
+  for (int i = 0; i < n_images; ++i) if (int rc = overlap_args("eval", c, d_res[i], d_ref[i], n_voxels[i])) return rc;
+  GLIA_HIP_TRY(hipSetDevice(c->device));
+  std::vector<std::vector<glia_hmt_overlap_entry>> tables((size_t)n_images);
+  std::vector<const glia_hmt_overlap_entry*> ptr((size_t)n_images);
+  std::vector<int64_t> len((size_t)n_images);
+  glia_hmt_eval_timing t = {0, 0, 0};
+  for (int i = 0; i < n_images; ++i) {
+    OverlapPass pass;
+    if (int rc = label_overlap(d_res[i], d_ref[i], d_mask ? d_mask[i] : nullptr, (unsigned long long)n_voxels[i], GLIA_HMT_OVERLAP_DROP_ZERO_B, c->stream,
+                               &tables[i], &pass)) return rc;
+    t.ms_count += pass.ms; t.entries += (int64_t)tables[i].size(); t.repeats += pass.repeats;
+    ptr[i] = tables[i].data(); len[i] = (int64_t)tables[i].size();
+  }
+  c->evt = t;
+  return overlap_scores(ptr.data(), len.data(), n_images, vi_mode, out);
+}
+
+int glia_hmt_last_eval_timing(const glia_hmt_ctx* c, glia_hmt_eval_timing* out) {
+  if (!c || !out) { set_error("last_eval_timing: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  *out = c->evt;
+  return GLIA_HMT_OK;
+}
+
 // hmt::genTree (hmt/tree_build.hxx:12-38): order -> array tree, children before parents
 int64_t glia_hmt_transform_keys(const uint32_t* h_order, int64_t n_merges, uint32_t* h_src, uint32_t* h_dst, int64_t capacity) {
   if (!h_order || !h_src || !h_dst || n_merges < 0) { set_error("transform_keys: invalid argument"); return GLIA_HMT_ERR_ARG; }

@@ -20,6 +20,7 @@ struct glia_hmt_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   uint32_t hint_rcap = 0, hint_pcap = 0;
   double transform_ms = 0;
+  glia_hmt_eval_timing evt = {0, 0, 0};   // the last glia_hmt_label_overlap / glia_hmt_eval call
   int tz = kTZ;                  // tile depth of the accumulation pass; halved when the LDS tables of a pass overflowed a lot
   LibmSel libm = {kLibmDevice, kLibmDevice, kLibmDevice};   // restatement of the host's log2 / log the kernels use (glibc_math.hpp)
 };

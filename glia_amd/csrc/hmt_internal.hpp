@@ -230,6 +230,13 @@ int watershed_labels(int dim, const int64_t dims[3], const float* d_img, double 
 enum { GLIA_HMT_CC_ROUTE_TILED = 0, GLIA_HMT_CC_ROUTE_GLOBAL = 1 };
 int label_components(int dim, const int64_t dims[3], const uint32_t* d_in, const uint32_t* d_mask, int mode, int route, uint32_t* d_out,
                      uint32_t* n_components, hipStream_t stream);
+// the contingency table of two label streams under a mask (label_overlap.hip): entries with count > 0 ascending by (a, b); arguments
+// validated by the caller (api.cpp).  info: device time of the counting passes (all of them, a repeated pass included) and how many were repeated
+struct OverlapPass { double ms = 0; int repeats = 0; };
+int label_overlap(const uint32_t* d_a, const uint32_t* d_b, const uint32_t* d_mask, unsigned long long n_voxels, int flags,
+                  hipStream_t stream, std::vector<glia_hmt_overlap_entry>* out, OverlapPass* info);
+// the scores of eval_ri / eval_vi from such tables (eval.cpp, host-only); arguments validated by the caller
+int overlap_scores(const glia_hmt_overlap_entry* const* tables, const int64_t* n_entries, int n_tables, int vi_mode, glia_hmt_eval_result* out);
 int launch_libm_eval(int function, int variant, const double* d_in, double* d_out, int64_t n, hipStream_t stream);
 int merge_rag_arrays(const RagArrays* parts, int n_parts, RagArrays* out, hipStream_t stream);
 // boundary-voxel values per directed pair of a map built from `vol` (its owned planes): fills rag->d_pv_off / d_pv / nV (owned)

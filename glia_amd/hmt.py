@@ -76,7 +76,44 @@ def _check(rc):
         raise HmtError(rc, lib().glia_hmt_last_error().decode())
 
 
-ERR_ARG, ERR_INTERNAL = -1, -7
+ERR_ARG, ERR_CAPACITY, ERR_INTERNAL = -1, -4, -7
+
+OVERLAP_ENTRY = np.dtype([("a", np.uint32), ("b", np.uint32), ("count", np.uint64)])      # glia_hmt_overlap_entry
+VI_MODES = {"reference": 0, "exact": 1}                                                   # GLIA_HMT_VI_REFERENCE | GLIA_HMT_VI_EXACT
+
+
+class EvalResult(C.Structure):
+    """glia_hmt_eval_result"""
+    _fields_ = [(k + s, C.c_uint64) for k in ("tp", "tn", "fp", "fn") for s in ("_lo", "_hi")] + \
+               [(k, C.c_double) for k in ("precision", "recall", "f1", "rand_index", "false_split", "false_merge")]
+
+    def as_dict(self):
+        out = {k.upper(): (getattr(self, k + "_hi") << 64) | getattr(self, k + "_lo") for k in ("tp", "tn", "fp", "fn")}
+        out.update({k: getattr(self, k) for k in ("precision", "recall", "f1", "rand_index", "false_split", "false_merge")})
+        return out
+
+
+class EvalTiming(C.Structure):
+    """glia_hmt_eval_timing"""
+    _fields_ = [("ms_count", C.c_double), ("entries", C.c_int64), ("repeats", C.c_int64)]
+
+
+def overlap_scores(tables, vi_mode="reference"):
+    """glia_hmt_overlap_scores (host-only, needs no GPU): the numbers of eval_ri / eval_vi from the contingency tables of one or
+    more image pairs -- structured arrays as Context.label_overlap returns them (or anything np.asarray turns into one), taken
+    as given.  -> dict: TP, TN, FP, FN (Python ints, summed over the tables before any ratio), precision, recall, f1 (NaN at
+    0 / 0, as the reference), rand_index, false_split = H(a | b), false_merge = H(b | a) (means over the tables).
+    vi_mode "reference": log2 of the INTEGER quotient floor(marginal / count), what the reference tool prints
+    (util/image_stats.hxx:153 divides two uints); "exact": the real quotient."""
+    if isinstance(tables, np.ndarray) and tables.dtype == OVERLAP_ENTRY:
+        tables = [tables]
+    keep = [np.ascontiguousarray(t, dtype=OVERLAP_ENTRY).reshape(-1) for t in tables]
+    n = len(keep)
+    ptrs = (C.c_void_p * max(n, 1))(*[t.ctypes.data if len(t) else None for t in keep])
+    lens = (C.c_int64 * max(n, 1))(*[len(t) for t in keep])
+    out = EvalResult()
+    _check(lib().glia_hmt_overlap_scores(ptrs, lens, C.c_int(n), C.c_int(VI_MODES[vi_mode]), C.byref(out)))
+    return out.as_dict()
 
 
 def set_option(key, value):
@@ -137,6 +174,7 @@ class Context:
         self.h = C.c_void_p()
         _check(lib().glia_hmt_ctx_create(C.c_int(device), C.c_void_p(stream) if stream else None, C.byref(self.h)))
         self.device = device
+        self._overlap_room = 0           # entries of the last label_overlap table: the size of the next call's host buffer
         if lib().glia_hmt_ctx_libm_status(self.h) == 0:
             import warnings
             warnings.warn(lib().glia_hmt_last_error().decode())
@@ -225,6 +263,56 @@ class Context:
                                                C.c_void_p(mask.data_ptr()) if mask is not None else None, C.c_int(self.CC_MODES[mode]),
                                                C.c_void_p(out.data_ptr()), C.byref(n)))
         return out, n.value
+
+    def label_overlap(self, a, b, mask=None, drop_zero_a=False, drop_zero_b=False):
+        """glia_hmt_label_overlap: the contingency table of two CUDA label tensors (uint32 payload, same number of voxels, any
+        shape) -> structured array (a, b, count) of the pairs with count > 0, ascending by (a, b).  mask: 0 drops the voxel;
+        drop_zero_a / drop_zero_b drop the voxels whose label in a / b is 0.  Tensors that are not 16-byte aligned (a view one
+        element into a buffer) take the scalar path to the same result."""
+        for t in (a, b) + (() if mask is None else (mask,)):
+            assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == a.numel()
+            _fence(t)
+        flags = (1 if drop_zero_a else 0) | (2 if drop_zero_b else 0)
+        out = np.empty(max(self._overlap_room, 1 << 12), OVERLAP_ENTRY)
+        n = C.c_int64(0)
+        while True:
+            rc = lib().glia_hmt_label_overlap(self.h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
+                                              C.c_void_p(mask.data_ptr()) if mask is not None else None, C.c_int64(a.numel()), C.c_int(flags),
+                                              _np(out), C.c_int64(len(out)), C.byref(n))
+            if rc != ERR_CAPACITY or n.value <= len(out):
+                break
+            out = np.empty(n.value, OVERLAP_ENTRY)          # the table is larger than the guess: once more with room for it
+        _check(rc)
+        self._overlap_room = n.value                        # the next call on this context starts with room for a table of this size
+        return out[:n.value].copy()
+
+    def evaluate(self, res, ref, masks=None, vi_mode="reference"):
+        """eval_ri and eval_vi (gadget/main_eval_ri.cxx, main_eval_vi.cxx) of proposed volumes against reference volumes on the
+        device: CUDA label tensors (uint32 payload) or lists of them, pair i with masks[i] (None, one tensor, or a list that
+        may hold None).  Masked-out voxels and voxels with reference label 0 are dropped.  -> dict: TP, TN, FP, FN (Python
+        ints, summed over the pairs), precision, recall, f1, rand_index, false_split, false_merge (means over the pairs;
+        vi_mode as overlap_scores)."""
+        if not isinstance(res, (list, tuple)):
+            res, ref = [res], [ref]
+            masks = None if masks is None else [masks]
+        assert len(res) == len(ref) and len(res) >= 1 and (masks is None or len(masks) == len(res))
+        for i, (p, r) in enumerate(zip(res, ref)):
+            for t in (p, r) + (() if masks is None or masks[i] is None else (masks[i],)):
+                assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == p.numel()
+                _fence(t)
+        n = len(res)
+        ptrs = lambda ts: (C.c_void_p * n)(*[None if t is None else t.data_ptr() for t in ts])
+        nv = (C.c_int64 * n)(*[p.numel() for p in res])
+        out = EvalResult()
+        _check(lib().glia_hmt_eval(self.h, C.c_int(n), ptrs(res), ptrs(ref), ptrs(masks) if masks is not None else None, nv,
+                                   C.c_int(VI_MODES[vi_mode]), C.byref(out)))
+        return out.as_dict()
+
+    def last_eval_timing(self):
+        """the counting passes of the last label_overlap / evaluate call: ms_count (device), entries, repeats"""
+        t = EvalTiming()
+        _check(lib().glia_hmt_last_eval_timing(self.h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in EvalTiming._fields_}
 
     def set_table_hint(self, regions, pairs):
         _check(lib().glia_hmt_ctx_set_table_hint(self.h, C.c_int64(regions), C.c_int64(pairs)))

@@ -505,6 +505,69 @@ enum { GLIA_HMT_CC_IDENTITY = 0, GLIA_HMT_CC_BINARY = 1, GLIA_HMT_CC_BINARY_INVE
 int glia_hmt_label_components(glia_hmt_ctx* ctx, int dim, const int64_t dims[3], const uint32_t* d_labels_in,
                               const uint32_t* d_mask, int mode, uint32_t* d_labels_out, uint32_t* n_components);
 
+/* ---- scoring a label volume against truth (gadget/main_eval_ri.cxx, gadget/main_eval_vi.cxx) ----------
+ * glia_hmt_label_overlap is the table the reference's evaluation family shares: the loops of stats::pairStats and stats::centropy on
+ * images (util/image_stats.hxx:248-273, :122-158) and stats::getOverlap (:308-335) each walk two label images and a mask and count
+ * the voxels of every label pair in an unordered_map.  d_a (proposed) and d_b (reference) are u32 streams of n_voxels -- 2D and 3D
+ * are the same call --, 1 <= n_voxels <= 2^32 - 2; d_mask (optional, u32): MASK_OUT_VAL = 0 drops the voxel; flags drop the voxels
+ * with a == 0 / b == 0 (the `excluded` sets {BG_VAL} of the callers).  Labels are arbitrary 32-bit values on both sides.
+ * h_entries receives the pairs with count > 0, ascending by (a, b); two calls on the same input return identical bytes.
+ * *n_entries = their number; more than `capacity`: GLIA_HMT_ERR_CAPACITY, *n_entries still set, h_entries untouched (h_entries may be
+ * NULL when capacity is 0).  Vector loads need d_a, d_b and d_mask 16-byte aligned; other pointers take a scalar path to the same
+ * result.  GLIA_HMT_ERR_ARG, message "label_overlap: ...", before any HIP call for: a NULL ctx, volume or n_entries, NULL h_entries
+ * with capacity > 0, capacity < 0, n_voxels outside the range, unknown flag bits. */
+#define GLIA_HMT_OVERLAP_DROP_ZERO_A 1
+#define GLIA_HMT_OVERLAP_DROP_ZERO_B 2
+typedef struct {
+  uint32_t a, b;
+  uint64_t count;
+} glia_hmt_overlap_entry;
+int glia_hmt_label_overlap(glia_hmt_ctx* ctx, const uint32_t* d_a, const uint32_t* d_b, const uint32_t* d_mask, int64_t n_voxels,
+                           int flags, glia_hmt_overlap_entry* h_entries, int64_t capacity, int64_t* n_entries);
+
+/* Host-only (no ctx, no HIP call): the numbers eval_ri and eval_vi print, from the tables of one or more image pairs.  The entries
+ * are taken as given -- whatever filtering the caller applied has already happened --; a (a, b) pair occurs once per table and
+ * counts are > 0 (a zero count is GLIA_HMT_ERR_ARG).
+ * Pair counts (stats::pairStats, util/stats.hxx:189-229): per table n = sum of counts, TP = sum c (c - 1) / 2, pairs of equal a /
+ * equal b from the marginals, TN / FP / FN as :225-228; the four are SUMMED over the tables before any ratio is taken
+ * (main_eval_ri.cxx:41-47) and returned as 128-bit integers in lo / hi words.  precision, recall, rand_index (util/stats.hxx:232-256)
+ * keep the guard den = isfeq(den, 0) ? den + FEPS : den, FEPS = 2.22e-16; f1 = 2 p r / (p + r) (:259-261) is NaN at 0 / 0, as in the
+ * reference.  Integer -> double conversions are exact up to 2^53 and round to nearest above (the reference converts Boost's
+ * int512_t, whose rounding is not pinned).
+ * Entropies (stats::centropy, util/image_stats.hxx:122-158): per table false_split = H(a | b) = sum c_ab log2(q) / n with q = n_b / c_ab,
+ * false_merge = H(b | a) likewise with n_a; the result is stats::mean over the tables (main_eval_vi.cxx:26).  The reference computes
+ * std::log2(up.second / bp.second) on two `uint`s (:153): q is the INTEGER quotient floor(marginal / c_ab).  GLIA_HMT_VI_REFERENCE
+ * reproduces that (what the reference tool prints; the tools' default); GLIA_HMT_VI_EXACT takes the real quotient as a double --
+ * the conditional entropy of the textbook.  The two agree when every quotient is an integer.  log2 is the host libm's.  Terms are
+ * added in entry order, in double; the reference adds them in unordered_map order, so its own last bits are not pinned: every
+ * term is >= 0 (q >= 1), a sum over E entries is within about E * 2^-53 relative of the correctly rounded one.
+ * No voxel selected (all tables empty): 0 / 0 = NaN for the entropies and f1, 0 for precision and recall, 0 / FEPS = 0 for
+ * rand_index -- what the C++ returns; not an error.  GLIA_HMT_ERR_ARG, message "eval: ...": n_tables < 1, a NULL argument, a
+ * negative length, an unknown mode. */
+enum { GLIA_HMT_VI_REFERENCE = 0, GLIA_HMT_VI_EXACT = 1 };
+typedef struct {
+  uint64_t tp_lo, tp_hi, tn_lo, tn_hi, fp_lo, fp_hi, fn_lo, fn_hi;   /* pairs: value = hi * 2^64 + lo */
+  double precision, recall, f1, rand_index;
+  double false_split, false_merge;
+} glia_hmt_eval_result;
+int glia_hmt_overlap_scores(const glia_hmt_overlap_entry* const* h_tables, const int64_t* n_entries, int n_tables, int vi_mode,
+                            glia_hmt_eval_result* out);
+
+/* Replaces the operation() of gadget/main_eval_ri.cxx:9-61 and gadget/main_eval_vi.cxx:7-29 for volumes on the device: one counting
+ * pass per image pair with GLIA_HMT_OVERLAP_DROP_ZERO_B (excluded1 = {BG_VAL}: masked-out voxels and voxels with reference label 0
+ * are dropped, the proposed label 0 counts as a label), then glia_hmt_overlap_scores.  d_res / d_ref: n_images device pointers,
+ * n_voxels[i] voxels each; d_mask: NULL, or n_images pointers of which any may be NULL (main_eval_ri.cxx:34).  Errors as the two
+ * calls above, message "eval: ...". */
+int glia_hmt_eval(glia_hmt_ctx* ctx, int n_images, const uint32_t* const* d_res, const uint32_t* const* d_ref,
+                  const uint32_t* const* d_mask, const int64_t* n_voxels, int vi_mode, glia_hmt_eval_result* out);
+/* the counting passes of the last glia_hmt_label_overlap or glia_hmt_eval call on this context */
+typedef struct {
+  double ms_count;         /* device time of the counting kernel, every pass of every image pair (label_overlap.hip) */
+  int64_t entries;         /* entries of the tables */
+  int64_t repeats;         /* passes repeated because the global table filled up */
+} glia_hmt_eval_timing;
+int glia_hmt_last_eval_timing(const glia_hmt_ctx* ctx, glia_hmt_eval_timing* out);
+
 /* ---- synthetic inputs for tests / bench, generated on the device -------------- */
 int glia_hmt_synth(glia_hmt_ctx* ctx, int dim, const int64_t dims[3], int S, int G, uint64_t seed,
                    int variant, uint32_t* d_labels, float* d_pb);
