@@ -6,6 +6,12 @@
 // an operand no region has, an operand that is already merged, a created key an earlier merge created, a created key that is a leaf's
 // label, and n == R.  Checked: the dense pairs on success; on failure the kind and the index of the first offending merge -- both
 // against the model and against what the corruption was made to provoke.
+//
+// Second line: leaf_truth_counts of the same header, which turns the (label, truth) table of glia_hmt_label_overlap into the (leaf,
+// truth) table of bc_label, against a std::map<label, leaf> lookup per entry.  Tables over labels drawn as above, ascending by (a, b),
+// whose `a` is a region label, a value below the first, between two or above the last label, or the masked label 0xFFFFFFFF; truth
+// labels include 0 and 0xFFFFFFFF, so the pair (0xFFFFFFFF, 0xFFFFFFFF) that label_overlap appends last occurs too.  Checked: the
+// entries kept, with their leaves; strictly ascending (leaf, truth); the sum of the counts.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -15,6 +21,7 @@
 #include <vector>
 
 #include "../glia_amd/csrc/dense_order.hpp"
+#include "../include/glia_hmt.h"      // glia_hmt_overlap_entry
 
 using glia::DenseOrderError;
 using glia::DenseOrderResult;
@@ -47,6 +54,68 @@ static DenseOrderResult model(const std::vector<uint32_t>& labels, const std::ve
 
 struct Counts { long orders = 0, merges = 0, by_kind[5] = {0, 0, 0, 0, 0}; };
 
+// sparse ascending labels, with runs of neighbours
+static std::vector<uint32_t> draw_labels() {
+  const uint32_t R = 1 + (uint32_t)(rnd() % 64);
+  std::vector<uint32_t> labels(R);
+  uint32_t next = (uint32_t)(rnd() % 5);
+  for (uint32_t i = 0; i < R; ++i) { labels[i] = next; next += (rnd() % 3) ? 1 + (uint32_t)(rnd() % 1000) : 1; }
+  return labels;
+}
+
+// ---- leaf_truth_counts ----
+constexpr uint32_t kMasked = 0xFFFFFFFFu;                               // kMaskedLabel (hmt_internal.hpp)
+struct LeafCount { uint32_t leaf, truth; unsigned long long count; };   // TruthCount (hmt_internal.hpp)
+struct TableCounts { long tables = 0, entries = 0, kept = 0, kept_truth0 = 0, kept_truth_max = 0, below = 0, between = 0, above = 0, masked = 0, reserved = 0; };
+
+static bool check_table(const std::vector<uint32_t>& labels, TableCounts* tc) {
+  const size_t R = labels.size();
+  auto truth = [&]() { const uint64_t k = rnd() % 8; return k == 0 ? 0u : k == 1 ? kMasked : k == 2 ? (uint32_t)rnd() : 1 + (uint32_t)(rnd() % 6); };
+  std::map<std::pair<uint32_t, uint32_t>, uint64_t> table;              // ascending by (a, b), as label_overlap returns it
+  auto put = [&](uint32_t a) { for (int k = 1 + (int)(rnd() % 3); k > 0; --k) table[{a, truth()}] = 1 + rnd() % (1ull << 40); };
+  for (size_t i = 0; i < R; ++i) {
+    if (rnd() % 3) put(labels[i]);
+    if (i == 0 && labels[0] > 0 && (rnd() & 1)) put((uint32_t)(rnd() % labels[0]));                                             // below the first label
+    if (i + 1 < R && labels[i + 1] - labels[i] > 1 && rnd() % 4 == 0) put(labels[i] + 1 + (uint32_t)(rnd() % (labels[i + 1] - labels[i] - 1)));   // between two
+  }
+  if (rnd() & 1) put(labels[R - 1] + 1 + (uint32_t)(rnd() % 100000));    // above the last label
+  if (rnd() & 1) put(kMasked);                                           // masked-out voxels; with truth 0xFFFFFFFF: the reserved pair, last
+  std::vector<glia_hmt_overlap_entry> entries;
+  for (const auto& e : table) entries.push_back(glia_hmt_overlap_entry{e.first.first, e.first.second, e.second});
+  std::map<uint32_t, uint32_t> leaf_of;
+  for (size_t i = 0; i < R; ++i) leaf_of[labels[i]] = (uint32_t)i;
+  std::vector<LeafCount> want, got;
+  unsigned long long want_sum = 0, got_sum = 0;
+  for (const auto& e : entries) {
+    auto it = leaf_of.find(e.a);
+    if (e.a == kMasked && e.b == kMasked) ++tc->reserved;
+    else if (e.a == kMasked) ++tc->masked;
+    else if (it == leaf_of.end()) ++(e.a < labels[0] ? tc->below : e.a > labels[R - 1] ? tc->above : tc->between);
+    else {
+      want.push_back(LeafCount{it->second, e.b, e.count});
+      want_sum += e.count;
+      ++tc->kept; tc->kept_truth0 += e.b == 0; tc->kept_truth_max += e.b == kMasked;
+    }
+  }
+  ++tc->tables; tc->entries += (long)entries.size();
+  glia::leaf_truth_counts(entries.data(), entries.size(), labels.data(), (int64_t)R, kMasked, &got);
+  if (got.size() != want.size()) { fprintf(stderr, "dense_order_check: leaf_truth_counts keeps %zu entries, the map lookup %zu\n", got.size(), want.size()); return false; }
+  for (size_t i = 0; i < got.size(); ++i) {
+    if (got[i].leaf != want[i].leaf || got[i].truth != want[i].truth || got[i].count != want[i].count) {
+      fprintf(stderr, "dense_order_check: leaf_truth_counts entry %zu is (%u, %u, %llu), the map lookup gives (%u, %u, %llu)\n", i, got[i].leaf, got[i].truth,
+              got[i].count, want[i].leaf, want[i].truth, want[i].count);
+      return false;
+    }
+    if (i && !(got[i - 1].leaf < got[i].leaf || (got[i - 1].leaf == got[i].leaf && got[i - 1].truth < got[i].truth))) {
+      fprintf(stderr, "dense_order_check: leaf_truth_counts entry %zu is not above entry %zu in (leaf, truth)\n", i, i - 1);
+      return false;
+    }
+    got_sum += got[i].count;
+  }
+  if (got_sum != want_sum) { fprintf(stderr, "dense_order_check: leaf_truth_counts sums to %llu voxels, the kept entries to %llu\n", got_sum, want_sum); return false; }
+  return true;
+}
+
 // want_error < 0: whatever the model says
 static bool check(const char* what, const std::vector<uint32_t>& labels, const std::vector<uint32_t>& order, int64_t n, int want_error, int64_t want_merge) {
   std::vector<uint32_t> got_dense, want_dense;
@@ -71,10 +140,8 @@ int main(int argc, char** argv) {
   s_state = argc > 2 ? strtoull(argv[2], nullptr, 0) : 0x9E3779B97F4A7C15ull;
   Counts cnt;
   for (long t = 0; t < n_random; ++t) {
-    const uint32_t R = 1 + (uint32_t)(rnd() % 64);
-    std::vector<uint32_t> labels(R);
-    uint32_t next = (uint32_t)(rnd() % 5);
-    for (uint32_t i = 0; i < R; ++i) { labels[i] = next; next += (rnd() % 3) ? 1 + (uint32_t)(rnd() % 1000) : 1; }      // sparse, with runs of neighbours
+    const std::vector<uint32_t> labels = draw_labels();
+    const uint32_t R = (uint32_t)labels.size();
     const uint32_t top = labels[R - 1];
     const int64_t n = (rnd() % 3) ? (int64_t)R - 1 : (int64_t)(rnd() % R);
     std::vector<uint32_t> order, live(labels);
@@ -128,5 +195,13 @@ int main(int argc, char** argv) {
   for (int k = 0; k < 5; ++k) if (n_random >= 100 && !cnt.by_kind[k]) { fprintf(stderr, "dense_order_check: corruption %d was never exercised\n", k); return 1; }
   printf("dense_order_check: %ld orders, %ld merges agree with the live-key model; corrupted: %ld unknown, %ld merged, %ld reused, %ld leaf key, %ld too many\n", cnt.orders,
          cnt.merges, cnt.by_kind[0], cnt.by_kind[1], cnt.by_kind[2], cnt.by_kind[3], cnt.by_kind[4]);
+  TableCounts tc;
+  for (long t = 0; t < n_random; ++t) if (!check_table(draw_labels(), &tc)) return 1;
+  std::vector<LeafCount> none{LeafCount{1, 2, 3}};
+  glia::leaf_truth_counts((const glia_hmt_overlap_entry*)nullptr, 0, (const uint32_t*)nullptr, 0, kMasked, &none);      // no entries, no regions
+  if (!none.empty()) { fprintf(stderr, "dense_order_check: leaf_truth_counts of an empty table is not empty\n"); return 1; }
+  printf("leaf_truth_counts: %ld tables, %ld entries agree with the map lookup; kept: %ld (%ld with truth 0, %ld with truth 0xFFFFFFFF); dropped: %ld below, "
+         "%ld between, %ld above the labels, %ld masked, %ld reserved pair\n", tc.tables, tc.entries, tc.kept, tc.kept_truth0, tc.kept_truth_max, tc.below, tc.between,
+         tc.above, tc.masked, tc.reserved);
   return 0;
 }

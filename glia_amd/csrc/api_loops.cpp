@@ -323,12 +323,14 @@ int glia_hmt_bc_feat_dim(const glia_hmt_rag* rag, int with_saliency) {
 
 // ---- a given merge order: what bc_feat and bc_label share ----
 // keys -> dense ids: leaves by label, the region created by merge i is R + i (RegionMap(seg, mask, order, false),
-// type/region_map.hxx:42-48,67-68); the order is validated on the way (dense_order.hpp), `who` prefixes the messages
-static int dense_order_of(const glia_hmt_rag* rag, const char* who, const uint32_t* h_order, int64_t n_merges, std::vector<uint32_t>* forced) {
+// type/region_map.hxx:42-48,67-68); the order is validated on the way (dense_order.hpp), `who` prefixes the messages; *lab = the
+// region labels, [R] ascending
+static int dense_order_of(const glia_hmt_rag* rag, const char* who, const uint32_t* h_order, int64_t n_merges, std::vector<uint32_t>* lab,
+                          std::vector<uint32_t>* forced) {
   const int64_t R = rag->arr.R;
-  std::vector<uint32_t> lab((size_t)R);
-  if (R) GLIA_HIP_TRY(hipMemcpy(lab.data(), rag->arr.d_rlabel, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
-  const DenseOrderResult r = dense_order(lab.data(), R, h_order, n_merges, forced);
+  lab->resize((size_t)R);
+  if (R) GLIA_HIP_TRY(hipMemcpy(lab->data(), rag->arr.d_rlabel, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
+  const DenseOrderResult r = dense_order(lab->data(), R, h_order, n_merges, forced);
   if (r.error == kDenseOrderOk) return GLIA_HMT_OK;
   set_error(std::string(who) + (r.error == kDenseOrderTooMany ? ": more merges than regions" : r.error == kDenseOrderReusedKey ? ": merge order reuses a region key"
                                                                                              : ": merge order refers to an unknown or already merged region"));
@@ -412,8 +414,8 @@ static int bc_feat_rows(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t* h_or
   MedianFeatIn in;
   if ((rc = bc_setup(c, rag, nullptr, "bc_feat", &cfg, &in))) return rc;
   if (n_merges == 0) return GLIA_HMT_OK;
-  std::vector<uint32_t> forced;
-  if ((rc = dense_order_of(rag, "bc_feat", h_order, n_merges, &forced))) return rc;
+  std::vector<uint32_t> rlabel, forced;
+  if ((rc = dense_order_of(rag, "bc_feat", h_order, n_merges, &rlabel, &forced))) return rc;
   MergeResult res;
   memset(&rag->bft, 0, sizeof(rag->bft));
   if (route == GLIA_HMT_BCFEAT_BATCH) {
@@ -527,7 +529,8 @@ int glia_hmt_score_initial_edges_shard(glia_hmt_ctx* c, glia_hmt_rag* rag, const
 }
 
 // hmt/main_bc_label_ri.cxx:27-153 (F1 / RI, --optSplit, --opt) and hmt/main_bc_label_vi.cxx:27-128 (VI, majority over truths, --opt):
-// one counting pass per truth volume on the device (truth_overlap.hip), per-node values and the label rules on the host (bc_label.cpp)
+// the contingency table of labels and each truth volume on the device (label_overlap.hip), its labels -> leaves (dense_order.hpp),
+// per-node values and the label rules (bc_label.cpp) on the host
 int glia_hmt_bc_label(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t* const* d_truth, int n_truth, const uint32_t* h_order,
                       int64_t n_merges, const glia_hmt_bc_label_opts* opts, int32_t* h_labels) {
   glia_hmt_bc_label_opts o = {GLIA_HMT_BC_LABEL_F1, 0, 1.0, 0, 0};         // the tools' defaults (main_bc_label_ri.cxx:19-23)
@@ -547,20 +550,24 @@ int glia_hmt_bc_label(glia_hmt_ctx* c, glia_hmt_rag* rag, const uint32_t* const*
   if (rag->only_contour) { set_error("bc_label: the region map must hold region points (only_contour = 0)"); return GLIA_HMT_ERR_ARG; }
   if (!rag->vol.lab) { set_error("bc_label: needs the volumes the region map was built from (whole-volume build)"); return GLIA_HMT_ERR_UNSUPPORTED; }
   const int64_t R = rag->arr.R;
-  std::vector<uint32_t> forced;
-  if (int rc = dense_order_of(rag, "bc_label", h_order, n_merges, &forced)) return rc;
+  std::vector<uint32_t> rlabel, forced;
+  if (int rc = dense_order_of(rag, "bc_label", h_order, n_merges, &rlabel, &forced)) return rc;
   rag->bcl = glia_hmt_bc_label_timing{0, 0, 0, 0, 0, 0};
   if (n_merges == 0) return GLIA_HMT_OK;
   GLIA_HIP_TRY(hipSetDevice(c->device));
+  const unsigned long long N = (unsigned long long)(rag->vol.nx * rag->vol.ny * rag->vol.nz);
   std::vector<NodeTruthStats> st((size_t)n_truth);
   for (int t = 0; t < n_truth; ++t) {
+    // with a mask vol.lab is the folded copy (masked-out voxels hold kMaskedLabel): no mask argument, 8 B per voxel
+    std::vector<glia_hmt_overlap_entry> table;
+    OverlapPass pass;
+    if (int rc = label_overlap(rag->vol.lab, d_truth[t], nullptr, N, 0, c->stream, &table, &pass)) return rc;
     std::vector<TruthCount> cnt;
-    float ms = 0;
-    if (int rc = truth_overlap(rag->vol, rag->arr.d_rlabel, (uint32_t)R, d_truth[t], c->stream, &cnt, &ms)) return rc;
+    leaf_truth_counts(table.data(), table.size(), rlabel.data(), R, kMaskedLabel, &cnt);
     const auto t0 = std::chrono::steady_clock::now();
     int64_t moves = 0, pairs = 0;
     node_truth_stats(cnt, (uint32_t)R, forced.data(), n_merges, &st[t], &moves, &pairs);
-    rag->bcl.ms_count += ms;
+    rag->bcl.ms_count += pass.ms;
     rag->bcl.ms_nodes += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     rag->bcl.entries += (int64_t)cnt.size(); rag->bcl.moves += moves; rag->bcl.node_pairs += pairs;
   }

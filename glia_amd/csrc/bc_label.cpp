@@ -1,6 +1,7 @@
 // glia_amd/csrc/bc_label.cpp -- truth-based merge labels for a GIVEN merge order (hmt/main_bc_label_ri.cxx, main_bc_label_vi.cxx).
 //
-// The device builds the leaf x truth contingency table (truth_overlap.hip).  Here, per tree node x and truth t != 0 (BG_VAL is
+// The device counts the (label, truth) pairs (label_overlap.hip) and one walk over that table maps its labels to leaves
+// (leaf_truth_counts, dense_order.hpp): the leaf x truth contingency table.  Here, per tree node x and truth t != 0 (BG_VAL is
 // excluded) with c_xt voxels of x:  n(x) = sum_t c_xt,  size(x) = all voxels of x,  Q(x) = sum_t c_xt^2,  E(x) = sum_t c_xt log2 c_xt.
 // A list L of regions that partitions x (r0 + r1, the merged region, a best-split list) then has (stats::pairStats,
 // util/stats.hxx:189-229, and stats::vi, util/image_stats.hxx:69-110)

@@ -1,7 +1,9 @@
 // glia_amd/csrc/dense_order.hpp -- a merge order in region keys -> dense ids, validated on the way.  Host only, no HIP (the pattern
 // of tree_paths.hpp): cli/dense_order_check.cpp runs it against a set of live keys updated merge by merge.  Dense ids: leaf i = the
 // i-th label ascending, the region merge k creates = R + k (RegionMap(seg, mask, order, false), type/region_map.hxx:42-48,67-68).
+// leaf_truth_counts, below, applies the same leaf numbering to a contingency table (bc_label); the same program checks it.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include <unordered_map>
@@ -32,6 +34,23 @@ inline DenseOrderResult dense_order(const uint32_t* labels, int64_t R, const uin
     id[order[3 * i + 2]] = (uint32_t)(R + i);
   }
   return {kDenseOrderOk, -1};
+}
+
+// The contingency table of (label volume, truth volume) -> the table of bc_label.  entries [n]: (a, b, count) ascending by (a, b), as
+// label_overlap returns them; labels [R] ascending; *out = (leaf, truth, count) with leaf = the index of a in labels, ascending by
+// (leaf, truth) -- the order of the entries, so one cursor walks the labels and nothing is sorted or searched.  Dropped: a == masked
+// (a masked-out voxel is in no region, util/struct.hxx:86-91; with masked = 0xFFFFFFFF this is also the pair (0xFFFFFFFF, 0xFFFFFFFF)
+// that label_overlap appends last), and an `a` that is no region's label.  Truth 0 stays: it makes the region's size.
+template <class Entry, class Count>
+inline void leaf_truth_counts(const Entry* entries, size_t n, const uint32_t* labels, int64_t R, uint32_t masked, std::vector<Count>* out) {
+  out->clear();
+  int64_t leaf = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t a = entries[i].a;
+    if (a == masked) continue;
+    while (leaf < R && labels[leaf] < a) ++leaf;
+    if (leaf < R && labels[leaf] == a) out->push_back(Count{(uint32_t)leaf, entries[i].b, entries[i].count});
+  }
 }
 
 }  // namespace glia

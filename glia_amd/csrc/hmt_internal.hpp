@@ -149,11 +149,9 @@ struct MedianInitRecords {
 struct MedianInitTiming { double ms_sort = 0, ms_select = 0; unsigned long long bytes = 0; };   // sort stage (grouping + sort + run sums) | selection kernels | device memory taken
 int median_init_stats(const MedianFeatIn& in, const MedianInitRecords& rec, uint32_t e0, uint32_t e1, hipStream_t stream, double* d_reg, double* d_bnd,
                       MedianInitTiming* timing);
-// bc_label (truth_overlap.hip, bc_label.cpp): the voxels of dense leaf `leaf` with truth label `truth` (0 included), sorted by
-// (leaf, truth); *ms = device time of the counting pass
+// bc_label (bc_label.cpp): the voxels of dense leaf `leaf` with truth label `truth` (0 included), sorted by (leaf, truth) -- the
+// table of label_overlap, below, with its labels mapped to leaves (leaf_truth_counts, dense_order.hpp)
 struct TruthCount { uint32_t leaf, truth; unsigned long long count; };
-int truth_overlap(const VolumeRef& vol, const uint32_t* d_rlabel, uint32_t R, const uint32_t* d_truth, hipStream_t stream,
-                  std::vector<TruthCount>* out, float* ms);
 // per tree node (leaves 0 .. R-1, merge k = R + k) and one truth volume: n = voxels with truth != 0, size = all voxels,
 // Q = sum_t c_t^2, E = sum_t c_t log2 c_t (t != 0); *moves = map entries moved by the small-to-large merging, *node_pairs = the
 // (node, truth) pairs of the tree (what a walk that visits each of them once would do)

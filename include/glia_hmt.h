@@ -365,7 +365,7 @@ int glia_hmt_bc_label(glia_hmt_ctx* ctx, glia_hmt_rag* rag, const uint32_t* cons
                       int64_t n_merges, const glia_hmt_bc_label_opts* opts, int32_t* h_labels);
 /* the stages of the last glia_hmt_bc_label call on this map */
 typedef struct {
-  double ms_count;         /* device time of the counting pass(es), all truth volumes (truth_overlap.hip) */
+  double ms_count;         /* device time of the counting pass(es), all truth volumes (label_overlap.hip) */
   double ms_nodes;         /* host: per-node values (small-to-large merging) */
   double ms_rules;         /* host: the label rules */
   int64_t entries;         /* (leaf, truth) entries of the contingency tables, truth 0 included */

@@ -1,7 +1,8 @@
 """Host check of the merge-order validator bc_feat and bc_label share (glia_amd/csrc/dense_order.hpp): cli/dense_order_check compares it
 with a model that keeps the set of live keys merge by merge -- the dense pairs of random valid orders over 1 to 64 sparse ascending
 labels, and for each order corrupted in five ways (unknown region, already merged, reused created key, created key equal to a leaf,
-n == R) the kind of the failure and the index of the first offending merge.  No GPU."""
+n == R) the kind of the failure and the index of the first offending merge.  Its second line: leaf_truth_counts of the same header, the
+labels of a contingency table -> leaves, against a map lookup per entry, with every kind of entry it drops.  No GPU."""
 import os
 import re
 import subprocess
@@ -22,3 +23,10 @@ def test_dense_order_agrees_with_the_live_key_model():
         # every order gets the n == R corruption; the others need one merge (unknown, leaf key) or two (merged, reused) to corrupt
         assert n_orders == orders and too_many == orders and merges > 10 * orders
         assert unknown == leaf and merged == reused and orders // 2 < merged <= unknown <= orders
+        # second line: leaf_truth_counts (the table of label_overlap -> the (leaf, truth) table of bc_label) against a map lookup per entry
+        m = re.match(r"leaf_truth_counts: (\d+) tables, (\d+) entries agree with the map lookup; kept: (\d+) \((\d+) with truth 0, (\d+) with truth 0xFFFFFFFF\); "
+                     r"dropped: (\d+) below, (\d+) between, (\d+) above the labels, (\d+) masked, (\d+) reserved pair$", r.stdout.splitlines()[1])
+        assert m, r.stdout
+        tables, entries, kept, truth0, truth_max, below, between, above, masked, reserved = (int(g) for g in m.groups())
+        assert tables == orders and entries == kept + below + between + above + masked + reserved
+        assert min(truth0, truth_max, below, between, above, masked, reserved) > 0 and kept > 10 * orders

@@ -473,3 +473,66 @@ def test_large_256(ctx):
         assert rm.bc_label(dt, order, **kw).tolist() == ref.labels([truth], gaps=gaps, **kw), kw
         if gaps is not None:
             _no_near_ties(gaps)
+
+
+# ---- the contingency table behind the labels: glia_hmt_label_overlap on (labels, truth), its labels mapped to leaves on the host ----
+def _table_entries(labels, truths, m):
+    """distinct (label, truth) pairs over the kept voxels, truth 0 included, summed over the truths"""
+    keep = np.ones(labels.size, bool) if m is None else m.reshape(-1) != 0
+    lab = labels.reshape(-1)[keep].astype(np.uint64) << np.uint64(32)
+    return sum(len(np.unique(lab | t.reshape(-1)[keep].astype(np.uint64))) for t in truths)
+
+
+# voxel counts: 19575 = 4 * 4893 + 3 (the scalar tail of the stream; two workgroups of 16 Ki voxels), 961 (less than one workgroup
+# step of 1024), 40320 (three workgroups).  The truth cells are small, so that the table has more than 768 entries everywhere: in
+# the 2D case every voxel has a truth label of its own and none is erased.
+TABLE_VOLS = [((29, 27, 25), 3, 4, True, dict(metric="f1")), ((31, 31), 2, 1, False, dict(metric="ri")),
+              ((40, 36, 28), 4, 6, True, dict(metric="vi", opt=1))]
+
+
+@pytest.mark.parametrize("mask", [False, True])
+@pytest.mark.parametrize("shape,S,G,erase,kw", TABLE_VOLS)
+def test_table_entries(ctx, shape, S, G, erase, kw, mask):
+    """last_bc_label_timing()["entries"] is the number of distinct (label, truth) pairs NumPy finds, also when the counting pass is
+    repeated: under GLIA_HMT_MINCAP the table starts at 1024 slots, of which a pass may fill 768"""
+    from glia_amd import hmt
+    rm, labels, pb, truth, m = _case(ctx, shape, S, G, erase=erase, mask=mask)
+    assert labels.size == int(np.prod(shape)) and (m is None) == (not mask)
+    truths = [truth]
+    if kw["metric"] == "vi":                                                   # several truths: the entries of all their tables
+        truths.append(truth_cells(shape, 5, seed=4321).astype(np.uint32) + 1)
+    want_entries = _table_entries(labels, truths, m)
+    assert min(_table_entries(labels, [t], m) for t in truths) > 768           # every MINCAP pass below is certain to be repeated
+    order, _ = rm.merge_order_pb(type=1)
+    assert len(order) > 20
+    want = Ref(labels, order, m).labels(truths, **kw)
+    dts = [_dt(t) for t in truths]
+    assert rm.bc_label(dts, order, **kw).tolist() == want
+    assert rm.last_bc_label_timing()["entries"] == want_entries
+    with hmt.options(GLIA_HMT_MINCAP="1"):
+        assert rm.bc_label(dts, order, **kw).tolist() == want
+    assert rm.last_bc_label_timing()["entries"] == want_entries
+    assert hmt.Context.internal_errors() == 0
+
+
+def test_reserved_pair(ctx):
+    """truth 0xFFFFFFFF on masked-out voxels is the pair (0xFFFFFFFF, 0xFFFFFFFF) of the folded labels, which label_overlap keeps out
+    of its hash table and appends last; it belongs to no region, while 0xFFFFFFFF on kept voxels is a truth label like any other"""
+    shape = (26, 24, 22)
+    rm, labels, pb, truth, m = _case(ctx, shape, 4, 9, mask=True)
+    truth = truth.copy()
+    a = tuple(slice(v // 2 - 4, v // 2 + 5) for v in shape)                    # around the masked-out block in the middle
+    b = tuple(slice(0, v // 3) for v in shape)
+    truth[a] = 0xFFFFFFFF
+    truth[b] = 0xFFFFFFFE
+    assert (m[a] == 0).any() and (m[a] != 0).any() and (m[b] == 0).any() and (m[b] != 0).any()
+    assert len(np.unique(labels[a][m[a] != 0])) > 1 and len(np.unique(labels[b][m[b] != 0])) > 1
+    order, _ = rm.merge_order_pb(type=1)
+    ref = Ref(labels, order, m)
+    dt = _dt(truth)
+    for metric in ("f1", "ri", "vi"):
+        gaps = [] if metric == "vi" else None
+        assert rm.bc_label(dt, order, metric=metric).tolist() == ref.labels([truth], metric=metric, gaps=gaps), metric
+        assert rm.last_bc_label_timing()["entries"] == _table_entries(labels, [truth], m)
+        if gaps is not None:
+            _no_near_ties(gaps)

@@ -1,12 +1,12 @@
-"""Times the counting pass of glia_hmt_label_overlap (label_overlap.hip) beside its nearest existing kernel, `to_count` of
-glia_hmt_bc_label (truth_overlap.hip), on the same two volumes in the same process, the calls alternating.
+"""Times the counting pass of glia_hmt_label_overlap (label_overlap.hip), with and without a mask, on the same two volumes
+in the same process, the calls alternating.  (profiles/eval_bench.txt is a run of an earlier version, which also timed the counting
+kernel glia_hmt_bc_label had then; bc_label counts with label_overlap now.)
 usage: eval_bench.py [--sizes 512 1024] [--reps 7] [--warmup 2] [--out FILE]
 
 Inputs (device synth, S = 16 labels; truth cells of side 40, tools/bclabel_bench.truth_of): label_overlap without a mask (8 B/voxel)
-and with an all-ones mask (12 B/voxel); bc_label with a one-merge order, so that its host stages cost nothing.  Both times are device
-milliseconds of the counting kernel alone -- glia_hmt_last_eval_timing().ms_count and glia_hmt_last_bc_label_timing().ms_count.
-Reported per size: median and minimum of the repetitions, GB/s of the algorithmic bytes, their share of the 8 TB/s HBM peak, the
-entries of the table, the passes repeated because the global table was too small, and who won each alternating pair."""
+and with an all-ones mask (12 B/voxel).  The times are device milliseconds of the counting kernel alone,
+glia_hmt_last_eval_timing().ms_count.  Reported per size: median and minimum of the repetitions, GB/s of the algorithmic bytes, their
+share of the 8 TB/s HBM peak, the entries of the table and the passes repeated because the global table was too small."""
 import argparse
 import os
 import statistics
@@ -14,7 +14,6 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import numpy as np
 import torch
 from bclabel_bench import truth_of
 from glia_amd import hmt
@@ -36,26 +35,20 @@ def main():
         lines.append(s)
 
     ctx = hmt.Context(0)
-    say("label_overlap vs to_count of bc_label on %s; synth S = 16 labels against truth cells of side 40" % torch.cuda.get_device_name(0))
+    say("label_overlap on %s; synth S = 16 labels against truth cells of side 40" % torch.cuda.get_device_name(0))
     for size in args.sizes:
         n_vox = size ** 3
-        lab, pb = ctx.synth((size,) * 3, 16, 128)
+        lab, _ = ctx.synth((size,) * 3, 16, 128)
         truth = truth_of(lab, 40)
         ones = torch.ones_like(lab)
         torch.cuda.synchronize()
-        rm = hmt.RegionMap(ctx, lab, pb=pb)
-        keys = rm.regions()["label"]
-        order = np.array([[keys[0], keys[1], int(keys.max()) + 1]], np.uint32)       # one merge: the counting pass is the whole call
 
         def run(which):
-            if which == "to_count":
-                rm.bc_label(truth, order)
-                return rm.last_bc_label_timing()["ms_count"], rm.last_bc_label_timing()["entries"], 0
             ctx.label_overlap(lab, truth, mask=ones if which == "label_overlap+mask" else None)
             t = ctx.last_eval_timing()
             return t["ms_count"], t["entries"], t["repeats"]
 
-        names = ("to_count", "label_overlap", "label_overlap+mask")
+        names = ("label_overlap", "label_overlap+mask")
         for _ in range(args.warmup):
             for w in names:
                 run(w)
@@ -66,18 +59,14 @@ def main():
                 t, entries, repeats = run(w)
                 ms[w].append(t)
                 info[w] = (entries, repeats)
-        say("%d^3 (%d voxels, %d regions):" % (size, n_vox, rm.num_regions))
+        say("%d^3 (%d voxels):" % (size, n_vox))
         for w in names:
             nbytes = (12.0 if w.endswith("mask") else 8.0) * n_vox
             med = statistics.median(ms[w])
             say("  %-18s median %.3f ms, min %.3f ms, %.0f GB/s of %d B/voxel = %.1f %% of 8 TB/s; %d entries, %d repeated passes   [%s]"
                 % (w, med, min(ms[w]), nbytes / (med * 1e6), nbytes / n_vox, 100.0 * nbytes / HBM_PEAK / (med * 1e-3), info[w][0], info[w][1],
                    " ".join("%.3f" % v for v in ms[w])))
-        wins = sum(a < b for a, b in zip(ms["label_overlap"], ms["to_count"]))
-        say("  label_overlap (8 B/voxel) faster than to_count in %d of %d alternating pairs; ratio of medians %.2f"
-            % (wins, args.reps, statistics.median(ms["to_count"]) / statistics.median(ms["label_overlap"])))
-        rm.close()
-        del lab, pb, truth, ones
+        del lab, truth, ones
         hmt.Context.release_cached_memory()
         torch.cuda.empty_cache()
     if args.out:
