@@ -7,31 +7,6 @@
 
 using namespace cli;
 
-// rows of a feature file; *dim = their common length (0 for an empty file)
-static std::vector<double> readRows(const std::string& file, int64_t* rows, int* dim) {
-  std::ifstream is(file);
-  if (!is) perr("Error: cannot open file " + file);
-  std::vector<double> v;
-  std::string line;
-  *rows = 0; *dim = 0;
-  while (std::getline(is, line)) {
-    const char* p = line.c_str();
-    int n = 0;
-    for (;;) {
-      char* end = nullptr;
-      const double x = strtod(p, &end);       // also reads "nan" / "inf", which operator>> refuses
-      if (end == p) break;
-      v.push_back(x); ++n; p = end;
-    }
-    while (*p == ' ' || *p == '\t' || *p == '\r') ++p;
-    if (*p) perr("Error: invalid value in data file " + file);
-    if (n == 0) continue;                     // blank line
-    if (*rows > 0 && n != *dim) perr("Error: invalid data file dimension in " + file);
-    *dim = n; ++*rows;
-  }
-  return v;
-}
-
 int main(int argc, char* argv[]) {
   const std::string usage = "Usage: pred_rf --m <model>... [--md <dim0> <dim1> <threshold>] --f <feats>... --l <label> --p <preds>...   "
                             "(flags as ml/rf/main_pred_rf.cxx:43-60)\n";

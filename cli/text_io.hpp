@@ -36,4 +36,30 @@ inline void writeRows(const std::string& file, const double* d, int64_t rows, in
   for (int64_t i = 0; i < rows; ++i) { for (int k = 0; k < cols; ++k) os << d[i * cols + k] << " "; os << "\n"; }
 }
 
+// readData of a matrix (util/text_io.hxx; pred_rf's and train_rf's feature and label files): one row per line, values separated by blanks
+// rows of a feature file; *dim = their common length (0 for an empty file)
+inline std::vector<double> readRows(const std::string& file, int64_t* rows, int* dim) {
+  std::ifstream is(file);
+  if (!is) perr("Error: cannot open file " + file);
+  std::vector<double> v;
+  std::string line;
+  *rows = 0; *dim = 0;
+  while (std::getline(is, line)) {
+    const char* p = line.c_str();
+    int n = 0;
+    for (;;) {
+      char* end = nullptr;
+      const double x = strtod(p, &end);       // also reads "nan" / "inf", which operator>> refuses
+      if (end == p) break;
+      v.push_back(x); ++n; p = end;
+    }
+    while (*p == ' ' || *p == '\t' || *p == '\r') ++p;
+    if (*p) perr("Error: invalid value in data file " + file);
+    if (n == 0) continue;                     // blank line
+    if (*rows > 0 && n != *dim) perr("Error: invalid data file dimension in " + file);
+    *dim = n; ++*rows;
+  }
+  return v;
+}
+
 }  // namespace cli

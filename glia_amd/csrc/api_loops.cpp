@@ -9,6 +9,7 @@
 #include "bc_features.hpp"
 #include "dense_order.hpp"
 #include "api_types.hpp"
+#include "forest_train.hpp"
 #include "median_layout.hpp"
 
 namespace glia {
@@ -170,6 +171,103 @@ void glia_hmt_forest_free(glia_hmt_forest* f) {
   if (!f) return;
   (void)hipSetDevice(f->device);
   delete f;                               // (its arrays go with it)
+}
+
+// ---- training (forest_train.hip) ----
+void glia_hmt_train_opts_default(glia_hmt_train_opts* o) {
+  if (!o) return;
+  const TrainOptions d;
+  o->ntree = d.ntree; o->mtry = d.mtry; o->sample_ratio = d.sample_ratio; o->nodesize = d.nodesize; o->balance = d.balance;
+  o->max_depth = d.max_depth; o->seed = d.seed;
+}
+
+int glia_hmt_forest_train(glia_hmt_ctx* c, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_train_opts* opts,
+                          glia_hmt_forest_model** out) {
+  if (!c || !out) { set_error("forest_train: NULL context or output"); return GLIA_HMT_ERR_ARG; }
+  if ((n_rows > 0 && dim > 0 && !h_rows) || (n_rows > 0 && !h_labels)) { set_error("forest_train: NULL rows or labels"); return GLIA_HMT_ERR_ARG; }
+  TrainOptions o;
+  if (opts) {
+    o.ntree = opts->ntree; o.mtry = opts->mtry; o.sample_ratio = opts->sample_ratio; o.nodesize = opts->nodesize; o.balance = opts->balance;
+    o.max_depth = opts->max_depth; o.seed = opts->seed;
+  }
+  TrainPlan plan;
+  const std::string bad = train_plan(h_rows, n_rows, dim, h_labels, o, &plan);
+  if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_ARG; }
+  GLIA_HIP_TRY(hipSetDevice(c->device));
+  glia_hmt_forest_model* m = new glia_hmt_forest_model;
+  const int rc = forest_train_device(h_rows, n_rows, dim, plan, o, c->stream, &m->m, &c->trt);
+  if (rc) { delete m; return rc; }
+  *out = m;
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_forest_model_from_arrays(int ntree, int nrnodes, int nclass, int mtry, const double* xbestsplit, const int* treemap,
+                                      const int* nodestatus, const int* nodeclass, const int* bestvar, const int* ndbigtree, const double* classwt,
+                                      const double* cutoff, const int* orig_labels, const int* new_labels, glia_hmt_forest_model** out) {
+  if (ntree < 1 || nrnodes < 1 || nclass < 1 || !xbestsplit || !treemap || !nodestatus || !nodeclass || !bestvar || !ndbigtree || !classwt ||
+      !cutoff || !orig_labels || !new_labels || !out) {
+    set_error("forest_model_from_arrays: invalid argument");
+    return GLIA_HMT_ERR_ARG;
+  }
+  const size_t nn = (size_t)ntree * (size_t)nrnodes;
+  glia_hmt_forest_model* m = new glia_hmt_forest_model;
+  ForestModel& f = m->m;
+  f.ntree = ntree; f.nrnodes = nrnodes; f.nclass = nclass; f.mtry = mtry;
+  f.xbestsplit.assign(xbestsplit, xbestsplit + nn); f.treemap.assign(treemap, treemap + 2 * nn);
+  f.nodestatus.assign(nodestatus, nodestatus + nn); f.nodeclass.assign(nodeclass, nodeclass + nn); f.bestvar.assign(bestvar, bestvar + nn);
+  f.ndbigtree.assign(ndbigtree, ndbigtree + ntree); f.classwt.assign(classwt, classwt + nclass); f.cutoff.assign(cutoff, cutoff + nclass);
+  f.orig_labels.assign(orig_labels, orig_labels + nclass); f.new_labels.assign(new_labels, new_labels + nclass);
+  *out = m;
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_forest_model_sizes(const glia_hmt_forest_model* m, int* ntree, int* nrnodes, int* nclass, int* mtry) {
+  if (!m) { set_error("forest_model_sizes: NULL model"); return GLIA_HMT_ERR_ARG; }
+  if (ntree) *ntree = m->m.ntree;
+  if (nrnodes) *nrnodes = m->m.nrnodes;
+  if (nclass) *nclass = m->m.nclass;
+  if (mtry) *mtry = m->m.mtry;
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_forest_model_arrays(const glia_hmt_forest_model* m, double* xbestsplit, int* treemap, int* nodestatus, int* nodeclass, int* bestvar,
+                                 int* ndbigtree, double* classwt, double* cutoff, int* orig_labels, int* new_labels) {
+  if (!m) { set_error("forest_model_arrays: NULL model"); return GLIA_HMT_ERR_ARG; }
+  const ForestModel& f = m->m;
+  auto put = [](auto* dst, const auto& v) { if (dst && !v.empty()) memcpy(dst, v.data(), sizeof(v[0]) * v.size()); };
+  put(xbestsplit, f.xbestsplit); put(treemap, f.treemap); put(nodestatus, f.nodestatus); put(nodeclass, f.nodeclass); put(bestvar, f.bestvar);
+  put(ndbigtree, f.ndbigtree); put(classwt, f.classwt); put(cutoff, f.cutoff); put(orig_labels, f.orig_labels); put(new_labels, f.new_labels);
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_forest_model_write(const glia_hmt_forest_model* m, const char* path) {
+  if (!m || !path) { set_error("forest_model_write: NULL argument"); return GLIA_HMT_ERR_ARG; }
+  const std::string bad = write_forest_model(m->m, path);
+  if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_IO; }
+  return GLIA_HMT_OK;
+}
+
+void glia_hmt_forest_model_free(glia_hmt_forest_model* m) { delete m; }
+
+int glia_hmt_forest_from_model(glia_hmt_ctx* c, const glia_hmt_forest_model* m, int predict_label, glia_hmt_forest** out) {
+  if (!c || !m || !out) { set_error("forest_from_model: NULL argument"); return GLIA_HMT_ERR_ARG; }
+  HostForest hf;
+  int rc = model_to_host_forest(m->m, predict_label, &hf);
+  if (rc) return rc;
+  GLIA_HIP_TRY(hipSetDevice(c->device));
+  glia_hmt_forest* f = new glia_hmt_forest;
+  f->device = c->device;
+  memset(&f->dc, 0, sizeof(f->dc));
+  f->dc.kind = 0; f->dc.n_models = 1;
+  if ((rc = upload_forest(hf, f, 0, c->stream))) { glia_hmt_forest_free(f); return rc; }
+  *out = f;
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_last_forest_train_timing(const glia_hmt_ctx* c, glia_hmt_forest_train_timing* out) {
+  if (!c || !out) { set_error("last_forest_train_timing: NULL argument"); return GLIA_HMT_ERR_ARG; }
+  *out = c->trt;
+  return GLIA_HMT_OK;
 }
 
 // ---- batch prediction (forest_predict.hip) ----

@@ -2,6 +2,7 @@
 // slab_dist.cpp), and the few host functions those files share.
 #pragma once
 #include "forest.hpp"
+#include "forest_model.hpp"
 #include "glibc_math.hpp"
 #include "greedy_common.hpp"
 #include "hmt_internal.hpp"
@@ -21,6 +22,7 @@ struct glia_hmt_ctx {
   uint32_t hint_rcap = 0, hint_pcap = 0;
   double transform_ms = 0;
   glia_hmt_eval_timing evt = {0, 0, 0};   // the last glia_hmt_label_overlap / glia_hmt_eval call
+  glia_hmt_forest_train_timing trt = {};  // the last glia_hmt_forest_train call
   int tz = kTZ;                  // tile depth of the accumulation pass; halved when the LDS tables of a pass overflowed a lot
   LibmSel libm = {kLibmDevice, kLibmDevice, kLibmDevice};   // restatement of the host's log2 / log the kernels use (glibc_math.hpp)
 };
@@ -58,5 +60,9 @@ struct glia_hmt_forest {
   int max_var = 0;
 };
 
-int free_tables(glia_hmt_ctx* c);           // api_rag.cpp: the accumulation tables of a context
+struct glia_hmt_forest_model {
+  glia::ForestModel m;
+};
+
+int free_tables(glia_hmt_ctx* c);          // api_rag.cpp: the accumulation tables of a context
 namespace glia { float ceil_f32(double d); uint32_t next_pow2(uint64_t v); HistSpec make_hist_spec(int bins, double lo, double hi); }   // api.cpp

@@ -121,35 +121,42 @@ int load_forest_file(const char* path, int predict_label, HostForest* out) {
   nodeclass = transposed(nodeclass, n_nc[0], n_nc[1]);
   bestvar = transposed(bestvar, n_bv[0], n_bv[1]);
 
-  out->ntree = ntree; out->nrnodes = nrnodes; out->nclass = nclass;
-  out->split.assign((size_t)ntree * nrnodes, 0.0);
-  out->meta.assign((size_t)ntree * nrnodes * 4, 0);
+  // the node arrays the device walks: one conversion for a model read from a file and one held in memory
+  ForestModel m;
+  m.ntree = ntree; m.nrnodes = nrnodes; m.nclass = nclass; m.mtry = mtry;
+  m.xbestsplit.swap(xbest); m.treemap.swap(treemap); m.nodestatus.swap(nodestatus); m.nodeclass.swap(nodeclass); m.bestvar.swap(bestvar);
+  ndbigtree.resize((size_t)ntree, 0); classwt.resize((size_t)nclass, 1.0); cutoff.resize((size_t)nclass, 0.0);
+  orig.resize((size_t)nclass); newl.resize((size_t)nclass, 0);
+  m.ndbigtree.swap(ndbigtree); m.classwt.swap(classwt); m.cutoff.swap(cutoff); m.orig_labels.swap(orig); m.new_labels.swap(newl);
+  return model_to_host_forest(m, predict_label, out);
+}
+
+int model_to_host_forest(const ForestModel& m, int predict_label, HostForest* out) {
+  const std::string bad = model_check(m);
+  if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_ARG; }
   int target = -1;
-  for (int i = 0; i < nclass; ++i) if (orig[i] == predict_label) { target = i; break; }   // ml/rf/rf.hxx:366-369
+  for (int i = 0; i < m.nclass; ++i) if (m.orig_labels[i] == predict_label) { target = i; break; }   // ml/rf/rf.hxx:366-369
   if (target < 0) { set_error("Error: invalid label for random forest predictor"); return GLIA_HMT_ERR_ARG; }
+  out->ntree = m.ntree; out->nrnodes = m.nrnodes; out->nclass = m.nclass;
+  out->split.assign((size_t)m.ntree * m.nrnodes, 0.0);
+  out->meta.assign((size_t)m.ntree * m.nrnodes * 4, 0);
   int maxvar = 0;
-  for (int j = 0; j < ntree; ++j) {
-    for (int k = 0; k < nrnodes; ++k) {
-      const size_t i = (size_t)j * nrnodes + k;
-      const bool terminal = nodestatus[i] == -1;
-      int* m = &out->meta[i * 4];
-      out->split[i] = xbest[i];
-      m[0] = bestvar[i] - 1;
-      m[1] = treemap[(size_t)2 * j * nrnodes + 2 * k] - 1;
-      m[2] = treemap[(size_t)2 * j * nrnodes + 2 * k + 1] - 1;
-      m[3] = terminal ? ((nodeclass[i] - 1 == target) ? 1 : 0) : -1;
-      if (!terminal) {
-        if (m[0] < 0 || m[1] < 0 || m[2] < 0 || m[1] >= nrnodes || m[2] >= nrnodes) {
-          // nodes beyond ndbigtree[j] are unused and all-zero: make them harmless terminals
-          m[0] = 0; m[1] = m[2] = 0; m[3] = 0;
-        } else if (m[0] > maxvar) maxvar = m[0];
-      }
+  for (size_t i = 0; i < (size_t)m.ntree * m.nrnodes; ++i) {
+    const bool terminal = m.nodestatus[i] == -1;
+    int* q = &out->meta[i * 4];
+    out->split[i] = m.xbestsplit[i];
+    q[0] = m.bestvar[i] - 1; q[1] = m.treemap[2 * i] - 1; q[2] = m.treemap[2 * i + 1] - 1;
+    q[3] = terminal ? ((m.nodeclass[i] - 1 == target) ? 1 : 0) : -1;
+    if (!terminal) {
+      if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[1] >= m.nrnodes || q[2] >= m.nrnodes) {
+        // nodes beyond ndbigtree[j] are unused and all-zero: make them harmless terminals
+        q[0] = 0; q[1] = q[2] = 0; q[3] = 0;
+      } else if (q[0] > maxvar) maxvar = q[0];
     }
   }
   out->max_var = maxvar;
   return GLIA_HMT_OK;
 }
-
 
 int pack_forest(const HostForest& hf, std::vector<PackedNode>* nodes, std::vector<int>* roots) {
   nodes->clear();

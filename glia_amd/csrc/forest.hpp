@@ -1,5 +1,6 @@
 // glia_amd/csrc/forest.hpp -- boundary classifier objects (alg/rf.hxx:10-122).
 #pragma once
+#include "forest_model.hpp"
 #include "hmt_internal.hpp"
 
 namespace glia {
@@ -54,6 +55,7 @@ struct DeviceClassifier {
 };
 
 int load_forest_file(const char* path, int predict_label, HostForest* out);
+int model_to_host_forest(const ForestModel& model, int predict_label, HostForest* out);
 // forest_predict.hip: pred[i] = the classifier's value for row i (device arrays; row i starts at d_rows + i * row_stride)
 // rows of the LDS tile the kernel takes for this input (64, 32, 16 or 8); 0: rows of `dim` columns are walked from global memory
 int forest_predict_tile_rows(long long n_rows, int dim);

@@ -579,6 +579,105 @@ class FeatureStubClassifier(RandomForest):
         _check(lib().glia_hmt_forest_stub(ctx.h, C.c_int(index), C.byref(self.h)))
 
 
+class TrainOpts(C.Structure):
+    """glia_hmt_train_opts: train_rf's options (ml/rf/main_train_rf.cxx:11-15) + max_depth + seed"""
+    _fields_ = [("ntree", C.c_int), ("mtry", C.c_int), ("sample_ratio", C.c_double), ("nodesize", C.c_int), ("balance", C.c_int),
+                ("max_depth", C.c_int), ("seed", C.c_uint64)]
+
+
+class ForestTrainTiming(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("ms_total", "ms_upload", "ms_bootstrap", "ms_prepare", "ms_gather", "ms_sort", "ms_scan", "ms_split",
+                                          "ms_partition", "ms_download")] + \
+               [(k, C.c_int64) for k in ("levels", "launches", "batches", "trees_in_flight", "nodes")] + [("device_bytes", C.c_uint64)]
+
+
+class ForestModel:
+    """A trained forest on the host (glia_hmt_forest_model): every array of the GLIA model file."""
+    _TREE = (("xbestsplit", np.float64, 1), ("treemap", np.int32, 2), ("nodestatus", np.int32, 1), ("nodeclass", np.int32, 1),
+             ("bestvar", np.int32, 1))
+    _CLASS = (("classwt", np.float64), ("cutoff", np.float64), ("orig_labels", np.int32), ("new_labels", np.int32))
+
+    def __init__(self, ctx, handle):
+        self.ctx = ctx
+        self.h = handle
+
+    @classmethod
+    def from_arrays(cls, arrays, ctx=None):
+        """a model from a dict like synth_forest.synthetic_forest returns (+ optional mtry, classwt, cutoff, new_labels); host-only"""
+        ntree, nrnodes = arrays["xbestsplit"].shape
+        nclass = len(arrays["orig_labels"])
+        a = dict(arrays)
+        a.setdefault("classwt", np.ones(nclass)); a.setdefault("cutoff", np.full(nclass, 1.0 / nclass))
+        a.setdefault("new_labels", np.arange(1, nclass + 1))
+        keep = [np.ascontiguousarray(a[k], dtype=t) for k, t, _ in cls._TREE] + [np.ascontiguousarray(a["ndbigtree"], dtype=np.int32)] + \
+               [np.ascontiguousarray(a[k], dtype=t) for k, t in cls._CLASS]
+        h = C.c_void_p()
+        _check(lib().glia_hmt_forest_model_from_arrays(C.c_int(ntree), C.c_int(nrnodes), C.c_int(nclass), C.c_int(int(a.get("mtry", 3))),
+                                                       *[_np(x) for x in keep], C.byref(h)))
+        return cls(ctx, h)
+
+    def sizes(self):
+        v = [C.c_int() for _ in range(4)]
+        _check(lib().glia_hmt_forest_model_sizes(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("ntree", "nrnodes", "nclass", "mtry"), (x.value for x in v)))
+
+    def arrays(self):
+        """dict of the model's arrays in synth_forest's layout: tree arrays [ntree, nrnodes], treemap [ntree, nrnodes, 2]"""
+        s = self.sizes()
+        out = {k: np.zeros((s["ntree"], s["nrnodes"]) + ((2,) if w == 2 else ()), t) for k, t, w in self._TREE}
+        out["ndbigtree"] = np.zeros(s["ntree"], np.int32)
+        out.update({k: np.zeros(s["nclass"], t) for k, t in self._CLASS})
+        order = [k for k, _, _ in self._TREE] + ["ndbigtree"] + [k for k, _ in self._CLASS]
+        _check(lib().glia_hmt_forest_model_arrays(self.h, *[_np(out[k]) for k in order]))
+        out["mtry"] = s["mtry"]
+        return out
+
+    def write(self, path):
+        _check(lib().glia_hmt_forest_model_write(self.h, str(path).encode()))
+
+    def forest(self, predict_label=-1, ctx=None):
+        """the classifier RandomForest.predict / merge_order_bc take, without a trip through a file"""
+        f = RandomForest.__new__(RandomForest)
+        f.h = C.c_void_p()
+        f.ctx = ctx or self.ctx
+        _check(lib().glia_hmt_forest_from_model(f.ctx.h, self.h, C.c_int(predict_label), C.byref(f.h)))
+        return f
+
+    def close(self):
+        if self.h:
+            lib().glia_hmt_forest_model_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def train_forest(ctx, rows, labels, **opts):
+    """train_rf (ml/rf/main_train_rf.cxx): grows the forest on the device by the rule of DESIGN 3.12.  rows [n, dim] float64, labels [n]
+    integers; options ntree, mtry, sample_ratio, nodesize, balance, max_depth, seed (defaults: glia_hmt_train_opts_default)."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+    assert rows.ndim == 2 and labels.shape[0] == rows.shape[0]
+    o = TrainOpts()
+    lib().glia_hmt_train_opts_default(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(TrainOpts._fields_):
+            raise TypeError("train_forest: unknown option " + k)
+        setattr(o, k, v)
+    h = C.c_void_p()
+    _check(lib().glia_hmt_forest_train(ctx.h, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(labels), C.byref(o), C.byref(h)))
+    return ForestModel(ctx, h)
+
+
+def last_forest_train_timing(ctx):
+    t = ForestTrainTiming()
+    _check(lib().glia_hmt_last_forest_train_timing(ctx.h, C.byref(t)))
+    return {k: getattr(t, k) for k, _ in ForestTrainTiming._fields_}
+
+
 class Slab(C.Structure):
     """glia_hmt_slab (include/glia_hmt.h)"""
     _fields_ = [("dims_local", C.c_int64 * 3), ("z_global_of_plane0", C.c_int64), ("z_begin", C.c_int64), ("z_end", C.c_int64),

@@ -75,9 +75,14 @@ def _arr(f, a, dtype):
     f.write(a.tobytes())
 
 
-def write_model(path, forest):
+def write_model(path, forest, mtry=3, classwt=None, cutoff=None):
+    """mtry, classwt (default: ones) and cutoff (default: 1 / nclass) are the fields a trained model sets (ml/rf/ml_rf.h:97-156); the walk
+    reads none of them, and the defaults are what this writer has always written."""
     ntree, nrnodes = forest["xbestsplit"].shape
     nclass = len(forest["orig_labels"])
+    classwt = np.ones(nclass) if classwt is None else np.asarray(classwt, np.float64)
+    cutoff = np.full(nclass, 1.0 / nclass) if cutoff is None else np.asarray(cutoff, np.float64)
+    assert classwt.shape == (nclass,) and cutoff.shape == (nclass,)
     hdr = bytearray(_HDR)
 
     def n2(name, a, b):
@@ -88,7 +93,7 @@ def write_model(path, forest):
     n2("n_bestvar", nrnodes, ntree); n2("n_ndbigtree", ntree, 1); n2("n_orig_labels", nclass, 1)
     n2("n_new_labels", nclass, 1)
     struct.pack_into("<i", hdr, _OFF["nrnodes"], nrnodes); struct.pack_into("<i", hdr, _OFF["ntree"], ntree)
-    struct.pack_into("<i", hdr, _OFF["mtry"], 3); struct.pack_into("<i", hdr, _OFF["nclass"], nclass)
+    struct.pack_into("<i", hdr, _OFF["mtry"], int(mtry)); struct.pack_into("<i", hdr, _OFF["nclass"], nclass)
 
     def filemat(mem, n0, n1):   # memory (node fastest) -> file (row-major n0 x n1); undone by the reader's transpose
         return np.ascontiguousarray(np.asarray(mem).reshape(n1, n0).T)
@@ -97,14 +102,14 @@ def write_model(path, forest):
         f.write(bytes(hdr))
         f.write(struct.pack("<ii", nrnodes, ntree))
         _arr(f, filemat(forest["xbestsplit"], nrnodes, ntree), np.float64)
-        _arr(f, np.ones(nclass), np.float64)
-        _arr(f, np.full(nclass, 1.0 / nclass), np.float64)
+        _arr(f, classwt, np.float64)
+        _arr(f, cutoff, np.float64)
         _arr(f, filemat(forest["treemap"], nrnodes, 2 * ntree), np.int32)
         _arr(f, filemat(forest["nodestatus"], nrnodes, ntree), np.int32)
         _arr(f, filemat(forest["nodeclass"], nrnodes, ntree), np.int32)
         _arr(f, filemat(forest["bestvar"], nrnodes, ntree), np.int32)
         _arr(f, forest["ndbigtree"], np.int32)
-        f.write(struct.pack("<i", 3))
+        f.write(struct.pack("<i", int(mtry)))
         _arr(f, forest["orig_labels"], np.int32)
         _arr(f, np.arange(1, nclass + 1), np.int32)
         f.write(struct.pack("<i", nclass))

@@ -287,6 +287,59 @@ int glia_hmt_forest_predict_device(glia_hmt_ctx* ctx, const glia_hmt_forest* for
  * length are not staged (dim > GLIA_HMT_PREDICT_STAGE_MAX_DIM).  For tests and tuning; no result depends on it. */
 int glia_hmt_forest_predict_tile_rows(int64_t n_rows, int dim);
 
+/* ---- training the boundary classifier ---------------------------------------------------------------
+ * Replaces train_rf (ml/rf/main_train_rf.cxx:18-70): rf_old::train around classRF (ml/rf/ml_rf_train.cxx:234, whose sources the
+ * reference tree does not hold) and rf_old::writeModelToBinaryFile (ml/rf/ml_rf_model.cxx:378-455).  The flags, their defaults, the
+ * sample-size and class-weight arithmetic (main_train_rf.cxx:11-15,40-61), the mtry default (ml_rf_train.cxx:362,376) and the file
+ * format are the reference's; the growing rule is this library's own, deterministic definition -- no parity with
+ * classRF's trees is possible or claimed.
+ * glia_hmt_train_opts replaces the tool's options (nTree, mTry, sampleSizeRatio, nodeSize, balance) + max_depth (0 = unlimited) and the
+ * seed everything random is hashed from. */
+typedef struct {
+  int ntree;              /* --nt, 255 */
+  int mtry;               /* --mt, 0 = floor(sqrt(dim)) */
+  double sample_ratio;    /* --sr, 0.7; <= 1e-6: as many draws as rows */
+  int nodesize;           /* --ns, 1 */
+  int balance;            /* --bal, 1 */
+  int max_depth;          /* 0 = unlimited */
+  uint64_t seed;          /* 0x9E3779B97F4A7C15 */
+} glia_hmt_train_opts;
+void glia_hmt_train_opts_default(glia_hmt_train_opts* opts);
+/* A trained model on the host: every array of rf_old::Model the model file holds (ml/rf/ml_rf.h:97-156). */
+typedef struct glia_hmt_forest_model glia_hmt_forest_model;
+/* h_rows: [n_rows][dim] doubles, h_labels: [n_rows]; opts NULL = the defaults.  GLIA_HMT_ERR_ARG with a message: no rows, no columns,
+ * a non-finite value, fewer than 2 or more than 8 distinct labels, a sample size outside [1, n_rows], more than 32767 columns.  A plan
+ * whose device memory does not fit: GLIA_HMT_ERR_UNSUPPORTED.  Two calls with the same arguments return identical models. */
+int glia_hmt_forest_train(glia_hmt_ctx* ctx, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels,
+                          const glia_hmt_train_opts* opts, glia_hmt_forest_model** out);
+/* Host-only: a model from its arrays (tests, converters): tree arrays [ntree][nrnodes] node fastest, treemap [ntree][nrnodes][2],
+ * 1-based daughters / variables / classes as the file holds them. */
+int glia_hmt_forest_model_from_arrays(int ntree, int nrnodes, int nclass, int mtry, const double* xbestsplit, const int* treemap,
+                                      const int* nodestatus, const int* nodeclass, const int* bestvar, const int* ndbigtree,
+                                      const double* classwt, const double* cutoff, const int* orig_labels, const int* new_labels,
+                                      glia_hmt_forest_model** out);
+int glia_hmt_forest_model_sizes(const glia_hmt_forest_model* model, int* ntree, int* nrnodes, int* nclass, int* mtry);
+/* copies the arrays (layout as above; any pointer may be NULL) */
+int glia_hmt_forest_model_arrays(const glia_hmt_forest_model* model, double* xbestsplit, int* treemap, int* nodestatus, int* nodeclass,
+                                 int* bestvar, int* ndbigtree, double* classwt, double* cutoff, int* orig_labels, int* new_labels);
+/* rf_old::writeModelToBinaryFile (ml/rf/ml_rf_model.cxx:378-455), every array dense; host-only */
+int glia_hmt_forest_model_write(const glia_hmt_forest_model* model, const char* path);
+void glia_hmt_forest_model_free(glia_hmt_forest_model* model);
+/* alg::RandomForest(predictLabel, modelFile) (alg/rf.hxx:22-33) without the trip through a file: the classifier
+ * glia_hmt_forest_predict and glia_hmt_merge_order_bc take. */
+int glia_hmt_forest_from_model(glia_hmt_ctx* ctx, const glia_hmt_forest_model* model, int predict_label, glia_hmt_forest** out);
+/* the stages of the last glia_hmt_forest_train call of this context (device times from events, ms_total wall clock) */
+typedef struct {
+  double ms_total, ms_upload, ms_bootstrap, ms_prepare, ms_gather, ms_sort, ms_scan, ms_split, ms_partition, ms_download;
+  int64_t levels;            /* tree levels grown, over all batches */
+  int64_t launches;
+  int64_t batches;           /* groups of trees grown side by side */
+  int64_t trees_in_flight;   /* trees of a full batch */
+  int64_t nodes;             /* nodes of all trees */
+  uint64_t device_bytes;     /* device memory planned for the call */
+} glia_hmt_forest_train_timing;
+int glia_hmt_last_forest_train_timing(const glia_hmt_ctx* ctx, glia_hmt_forest_train_timing* out);
+
 /* Length of one feature vector for the configuration the rag was built with (BoundaryClassificationFeats::dim,
  * hmt/bc_feat.hxx:225-230; or selectFeatures' length with --simpf). */
 int glia_hmt_feat_dim(const glia_hmt_rag* rag);
