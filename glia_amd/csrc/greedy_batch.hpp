@@ -209,6 +209,7 @@ __device__ unsigned long long g_edgeprof[3][2];           // created edges (narr
 #endif
 // The whole workgroup contracts ONE edge (more than kMemMax list entries): greedy_window_kernel's contraction, built from the same
 // pieces (win_stage_lists .. win_retire_edge) with the batch policies -- spill instead of flush, horizon, no load in the store stream.
+// LDS-table case (at most kMarkMax entries): the lists arrive in one round trip (win_stage_lists_small).
 __device__ __forceinline__ uint32_t batch_contract_wide(const WinState& st, WinShared& w, WinWork& s, BatchShared& b, int tid, uint32_t slot, double rootsal,
                                                       unsigned long long k, unsigned long long ne, unsigned long long pool_used, double smin, double scale, uint32_t* newcount_out) {
   const uint32_t e = w.e[slot], r0 = w.u[slot], r1 = w.v[slot];
@@ -231,7 +232,7 @@ __device__ __forceinline__ uint32_t batch_contract_wide(const WinState& st, WinS
     st.rdead[r0] = 1; st.rdead[r1] = 1;
   }
   const bool small = total <= kMarkMax;
-  win_stage_lists(st, s, tid, e, off0, len0, off1, len1, small);
+  if (small) win_stage_lists_small(st, s, tid, e, off0, len0, off1, len1); else win_stage_lists(st, s, tid, e, off0, len0, off1, len1, false);
   if (small) lds_barrier(); else full_barrier();      // (the global mark arrays are read by other threads below)   // [B:wide-lists]
   WIDE_T(1);
   if (wn_now + total > st.wcap && wn_now > st.wcap / 2u) win_compact(w, tid, st.wcap);      // (holes out; a full window spills, see win_evict)
@@ -396,17 +397,28 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_batch_kernel(WinState s
     // ---- compute: wave j works out member j (rank order) on its own, up to kMemP list entries per lane; wider members end the batch ----
     const bool narrow = member && total <= kMemMax;
     b.bitmap[wave][lane] = 0;   // [W:bitmap-clear]
+    // The member's list in one round trip: every lane loads kMemP entries back to back -- a lane past the end (and a wave without a narrow
+    // member, whose slot may hold anything) loads the pool's first entry instead of branching round the load -- and "not in the list" is
+    // a select once the data is there.  (A load inside `if (inlist)` ended in a wait of its own: two or three dependent round trips for
+    // a member of more than 64 entries.)
     FatEntry fe[kMemP];
+    FatHalves fh[kMemP];
     bool act[kMemP], side1[kMemP];
     uint32_t h[kMemP];
 #pragma unroll
     for (int p = 0; p < kMemP; ++p) {
       const uint32_t i = (uint32_t)lane + 64u * (uint32_t)p;
-      const bool inlist = narrow && i < total;
+      act[p] = narrow && i < total;
       side1[p] = i >= len0;
-      fe[p].eid = kNone; fe[p].rs = 0; fe[p].n = 0; fe[p].pos = 0; fe[p].off = 0; fe[p].len = 0; fe[p].mean = 0.0;
-      if (inlist) fe[p] = st.fpool[side1[p] ? off1 + (i - len0) : off0 + i];
-      act[p] = inlist;
+      fh[p] = fat_load(&st.fpool[act[p] ? (side1[p] ? off1 + (i - len0) : off0 + i) : 0u]);
+    }
+    static_assert(kMemP == 3, "fat_pin");
+    fat_pin(fh);
+#pragma unroll
+    for (int p = 0; p < kMemP; ++p) {
+      const bool in = act[p];
+      fe[p].eid = in ? fh[p].lo.x : kNone; fe[p].rs = in ? fh[p].lo.y : 0u; fe[p].n = in ? fh[p].lo.z : 0u; fe[p].pos = in ? fh[p].lo.w : 0u;
+      fe[p].off = in ? fh[p].hi.x : 0u; fe[p].len = in ? fh[p].hi.y : 0u; fe[p].mean = in ? fat_mean(fh[p]) : 0.0;
     }
     if (pend_e != kNone) { st.er[pend_e].next = pend_old; pend_e = kNone; }      // (last round's atomic has returned with these loads)
 #pragma unroll

@@ -435,6 +435,53 @@ __device__ __forceinline__ void win_stage_lists(const WinState& st, WinWork& s, 
     } else (side1 ? st.mark1 : st.mark0)[fe.rs] = i + 1u;
   }
 }
+// A list entry as its two 16-byte halves (FatEntry: eid, rs, n, pos | off, len, mean), and a fence that makes the compiler hold three
+// entries in registers at this point: their loads cannot sink under a later branch, and all six are issued before the one wait.
+struct FatHalves { uint4 lo, hi; };
+static_assert(sizeof(FatHalves) == sizeof(FatEntry), "FatEntry halves");
+__device__ __forceinline__ FatHalves fat_load(const FatEntry* p) {
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+  FatHalves f; f.lo = q[0]; f.hi = q[1];
+  return f;
+}
+__device__ __forceinline__ void fat_pin(const FatHalves (&f)[3]) {      // (inputs only: a tied output would be a copy, and a copy waits)
+  asm volatile("" :: "v"(f[0].lo.x), "v"(f[0].lo.y), "v"(f[0].lo.z), "v"(f[0].lo.w), "v"(f[0].hi.x), "v"(f[0].hi.y), "v"(f[0].hi.z), "v"(f[0].hi.w),
+               "v"(f[1].lo.x), "v"(f[1].lo.y), "v"(f[1].lo.z), "v"(f[1].lo.w), "v"(f[1].hi.x), "v"(f[1].hi.y), "v"(f[1].hi.z), "v"(f[1].hi.w),
+               "v"(f[2].lo.x), "v"(f[2].lo.y), "v"(f[2].lo.z), "v"(f[2].lo.w), "v"(f[2].hi.x), "v"(f[2].hi.y), "v"(f[2].hi.z), "v"(f[2].hi.w));
+}
+__device__ __forceinline__ double fat_mean(const FatHalves& f) { return __longlong_as_double((long long)(((unsigned long long)f.hi.w << 32) | f.hi.z)); }
+// win_stage_lists for the batch kernel's LDS-table case (192 < total <= kMarkMax, at most kStageP entries per lane): ONE round trip.
+// Every lane loads both halves of all its entries, lanes past the end from the list's last entry instead of branching round the load,
+// and `eid` is tested once everything has arrived.  (win_stage_lists fetches an entry in three pieces with a wait behind each -- the
+// early `continue` sinks the other fields under a branch -- and requests pass p + 1 behind pass p's table inserts.)
+constexpr int kStageP = (int)((kMarkMax + kGreedyThreads - 1) / kGreedyThreads);
+__device__ __forceinline__ void win_stage_lists_small(const WinState& st, WinWork& s, int tid, uint32_t e, uint32_t off0, uint32_t len0, uint32_t off1, uint32_t len1) {
+  const uint32_t total = len0 + len1, last = total - 1u;      // (total >= 1: the caller's contraction is wide)
+  FatHalves f[kStageP];
+#pragma unroll
+  for (int p = 0; p < kStageP; ++p) {
+    const uint32_t i = (uint32_t)tid + (uint32_t)p * kGreedyThreads, ic = i < total ? i : last;
+    f[p] = fat_load(&st.fpool[ic >= len0 ? off1 + (ic - len0) : off0 + ic]);
+  }
+  static_assert(kStageP == 3, "fat_pin");
+  fat_pin(f);
+#pragma unroll
+  for (int p = 0; p < kStageP; ++p) {
+    const uint32_t i = (uint32_t)tid + (uint32_t)p * kGreedyThreads;
+    const uint32_t eid = f[p].lo.x, rs = f[p].lo.y;
+    if (i >= total || eid == e || eid == kNone) continue;
+    uint4* dst = reinterpret_cast<uint4*>(&s.stage[i]);
+    dst[0] = f[p].lo; dst[1] = f[p].hi;
+    uint32_t h = (rs * 2654435761u) >> 21;
+    while (true) {
+      const uint32_t old = atomicCAS(&s.mk[h], 0u, rs + 1u);
+      if (old == 0u) { s.items[atomicAdd(&s.nitems, 1u)] = h; break; }
+      if (old == rs + 1u) break;
+      h = (h + 1u) & (kMarkSlots - 1u);
+    }
+    (i >= len0 ? s.mv1 : s.mv0)[h] = i + 1u;
+  }
+}
 // Work item i of a contraction: neighbour rs, which of (r0,rs) / (r1,rs) exist (h0, h1) and their entries f0, f1 (a missing one
 // repeats the other).  SMALL: item i of the LDS table, whose slot is cleared; else list entry i with the global marks.
 // Returns false when the item is no neighbour (contracted edge, tombstone, or a common neighbour seen from the r1 side).
