@@ -100,21 +100,35 @@ __global__ void win_collect_kernel(const EdgeRec* er, uint32_t n_edges, const ui
 // and a live partner.  The records of 30 M created edges are not read -- the live edges sit in at most 2 x E0 entries -- and need
 // not all exist: an edge created below the horizon of the interval that just ended (slot >= ne_base, cell < wch: store_new_edge's
 // predicate, with the interval's values still in st) gets its record here, rebuilt from the entry (edge_record.hpp); every other
-// edge has one.  counter[0] = items (cap = room in kseq / vals), counter[1] = records rebuilt.
-__global__ void win_collect_lists_kernel(WinState st, uint32_t n_regions, unsigned long long* kseq, uint32_t* vals, uint32_t cap, uint32_t* counter) {
-  const uint32_t r = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
-  if (r >= n_regions || st.rdead[r]) return;                             // (uniform per wave)
+// edge has one.  counter[0] = items (cap = room in kseq / ksal / vals), counter[1] = records rebuilt.
+// The item's saliency key comes from the entry: the saliency is -entry.mean (edge_fill: leaf_sal = -mean; store_new_edge's callers and
+// rebuild_edge_record: sal = -mean), so no later kernel of the chain asks a record for it.  The seq of a rebuilt record is computed
+// here, every other one is read from the record (the cat bits of a created edge are nowhere else).  Taking the seq of an initial
+// edge as eid + 1 instead (edge_fill) was measured and bought nothing, not even in the first baseline, where every edge is initial
+// (DESIGN 3.3): the pass waits for its chain of dependent loads and its counter, not for that one line.
+// No record is asked whether the edge is queued: in the batch kernel an entry with an edge, in the list of a live region and leading
+// to a live region, IS a queued edge.  The kernel rejects nothing (cond_n <= 0); a popped edge leaves two dead regions; of the edges
+// a contraction replaces, (r0, rs) and (r1, rs), both have a dead end, rs's entry of the one is overwritten in place by the new
+// edge and rs's entry of the other becomes a tombstone (eid = kNone).  A launch only ends between contractions.
+// W = lanes that walk one list (64 or 16); ballot and prefix run within that group of the wave.
+struct CollectOut { unsigned long long *kseq, *ksal; uint32_t *vals, *idx, *counter; uint32_t cap; };
+template <uint32_t W>
+__device__ __forceinline__ uint32_t win_collect_walk(const WinState& st, const CollectOut& out, uint32_t r) {
+  static_assert(W == 16u || W == 64u, "lanes per list");
+  const uint32_t lane = threadIdx.x & 63u, gl = lane & (W - 1u), gshift = lane & ~(W - 1u);
+  const unsigned long long gmask = W == 64u ? ~0ull : ((1ull << W) - 1ull);
   const uint32_t off = st.adj_off[r], len = st.adj_len[r];
   const double smin = st.wrange[0], scale = st.wrange[1];
   uint32_t rebuilt = 0;
-  for (uint32_t base = 0; base < len; base += 64u) {
-    const uint32_t i = base + lane;
-    unsigned long long q = 0;
+  for (uint32_t base = 0; base < len; base += W) {
+    const uint32_t i = base + gl;
+    unsigned long long q = 0, sk = 0;
     uint32_t e = kNone;
     if (i < len) {
       const FatEntry fe = st.fpool[off + i];
       if (fe.eid != kNone && fe.rs < r && !st.rdead[fe.rs]) {
         e = fe.eid;
+        sk = f64_ord(-fe.mean);
         if ((unsigned long long)e >= st.ne_base && win_cell(-fe.mean, smin, scale, st.wB) < st.wch) {
           const EdgeRec rec = rebuild_edge_record(fe, i, r, off, len, st.ecat[e], st.R0);
           st.er[e] = rec;
@@ -122,38 +136,100 @@ __global__ void win_collect_lists_kernel(WinState st, uint32_t n_regions, unsign
         } else q = st.er[e].seq;
       }
     }
-    const unsigned long long m = __ballot(q != 0);
+    // (the groups of one wave are not all here, or leave their loops at different times: a lane that is away votes 0, and only the
+    // group's own bits are used)
+    const unsigned long long m = (__ballot(e != kNone) >> gshift) & gmask;
     if (m == 0) continue;
     const int first = (int)__builtin_ctzll(m);
     uint32_t b0 = 0;
-    if ((int)lane == first) b0 = atomicAdd(&counter[0], (uint32_t)__popcll(m));
-    b0 = (uint32_t)__shfl((int)b0, first);
-    const uint32_t o = b0 + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if (q != 0 && o < cap) { kseq[o] = q; vals[o] = e; }                 // (more than cap items: the host stops on the count)
+    if ((int)gl == first) b0 = atomicAdd(&out.counter[0], (uint32_t)__popcll(m));
+    b0 = (uint32_t)__shfl((int)b0, (int)gshift + first);
+    const uint32_t o = b0 + (uint32_t)__popcll(m & ((1ull << gl) - 1ull));
+    if (e != kNone && o < out.cap) { out.kseq[o] = q; out.ksal[o] = sk; out.vals[o] = e; out.idx[o] = o; }      // (more than cap items: the host stops on the count)
   }
-  if (rebuilt) atomicAdd(&counter[1], rebuilt);
+  return rebuilt;
 }
-__global__ void win_salkey_kernel(const EdgeRec* er, const uint32_t* vals, uint32_t n, unsigned long long* ksal) {
+// G = 64: one wave per region.  G = 16: four regions per wave -- lists of ~14 entries leave 50 of 64 lanes idle -- each walked by its
+// group of 16 lanes if it has at most kCollectShort entries; the longer ones among the four (the hubs: thousands of entries late in
+// a run, 63 trips of 16 lanes where the wave needs 16) are then walked by the whole wave, one after the other.
+constexpr uint32_t kCollectShort = 32;
+template <uint32_t G>
+__global__ void win_collect_lists_kernel(WinState st, uint32_t n_regions, CollectOut out) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t rebuilt = 0;
+  if constexpr (G == 64u) {
+    const uint32_t r = t >> 6;
+    if (r >= n_regions || st.rdead[r]) return;                           // (uniform per wave)
+    rebuilt = win_collect_walk<64u>(st, out, r);
+  } else {
+    const uint32_t r = t / G;
+    if (r < n_regions && !st.rdead[r] && st.adj_len[r] <= kCollectShort) rebuilt = win_collect_walk<G>(st, out, r);
+    for (uint32_t j = 0; j < 64u / G; ++j) {
+      const uint32_t rj = (t >> 6) * (64u / G) + j;                      // (uniform per wave)
+      if (rj < n_regions && !st.rdead[rj] && st.adj_len[rj] > kCollectShort) rebuilt += win_collect_walk<64u>(st, out, rj);
+    }
+  }
+  if (rebuilt) atomicAdd(&out.counter[1], rebuilt);
+}
+// the record scan's items (win_collect_kernel) get their saliency keys from the records
+__global__ void win_salkey_kernel(const EdgeRec* er, const uint32_t* vals, uint32_t n, unsigned long long* ksal, uint32_t* idx) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) ksal[i] = f64_ord(er[vals[i]].sal);
+  if (i < n) { ksal[i] = f64_ord(er[vals[i]].sal); idx[i] = i; }
 }
-__global__ void win_baseline_fill_kernel(WinState st, uint32_t n, uint32_t* isort_w, unsigned long long* isort_seq) {
+// between the two sorts: the saliency keys in the order of the first (idx = item numbers sorted by descending seq)
+__global__ void win_gather_key_kernel(const unsigned long long* ksal, const uint32_t* idx, uint32_t n, unsigned long long* out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = ksal[idx[i]];
+}
+// behind the sorts: item i of the baseline is item idx[i] of the collection; its cell comes from its sorted key
+__global__ void win_baseline_fill_kernel(WinState st, uint32_t n, const unsigned long long* ksal_sorted, const uint32_t* idx, const unsigned long long* kseq, const uint32_t* vals,
+                                         uint32_t* isort_w, unsigned long long* isort_seq) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const EdgeRec r = st.er[isort_w[i]];
-  isort_seq[i] = r.seq;
-  atomicAdd(&st.wcnt[win_cell(r.sal, st.wrange[0], st.wrange[1], st.wB)], 1u);
+  const uint32_t j = idx[i];
+  isort_w[i] = vals[j]; isort_seq[i] = kseq[j];
+  atomicAdd(&st.wcnt[win_cell(f64_unord(ksal_sorted[i]), st.wrange[0], st.wrange[1], st.wB)], 1u);
 }
 // ige[c] = number of baseline items whose cell is >= c (c = 0..B): cell c's segment of the sorted array is [ige[c+1], ige[c])
-__global__ void win_segments_kernel(WinState st, const uint32_t* isort, uint32_t n, uint32_t* ige) {
+__global__ void win_segments_kernel(WinState st, const unsigned long long* ksal_sorted, uint32_t n, uint32_t* ige) {
   const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c > st.wB) return;
   uint32_t lo = 0, hi = n;                    // first index whose cell is < c
   while (lo < hi) {
     const uint32_t mid = (lo + hi) >> 1;
-    if (win_cell(st.er[isort[mid]].sal, st.wrange[0], st.wrange[1], st.wB) >= c) lo = mid + 1; else hi = mid;
+    if (win_cell(f64_unord(ksal_sorted[mid]), st.wrange[0], st.wrange[1], st.wB) >= c) lo = mid + 1; else hi = mid;
   }
   ige[c] = c == 0 ? n : lo;
+}
+// GLIA_HMT_BASELINE_AUDIT: a finished baseline of n items against its sources; *bad counts the mismatches.
+//   item j of the collection (j < n): its record's (seq, saliency key) equal the collected ones -- every collected edge has a record;
+//   item i of the sorted array: (key, seq) not above its predecessor's, equal to the record of isort[i], its cell not above the starting
+//     threshold cthr and its position inside its cell's segment [ige[cell + 1], ige[cell]);
+//   cell c (c <= B): ige does not rise with c, ige[0] = n, and wcnt[c] is the length of the segment.
+// With every item inside its cell's segment and ige falling from n, ige[c] IS the number of items whose cell is >= c: the items in
+// front of ige[c] are exactly those (an item of a cell >= c sits in front of ige[its cell] <= ige[c], one of a cell below c at or
+// behind ige[its cell + 1] >= ige[c]).
+__global__ void win_baseline_audit_kernel(WinState st, uint32_t n, const unsigned long long* kseq, const unsigned long long* ksal, const uint32_t* vals,
+                                          const unsigned long long* ksal_sorted, const uint32_t* isort, const unsigned long long* iseq, const uint32_t* ige,
+                                          long long cthr, uint32_t* bad) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t wrong = 0;
+  if (i < n) {
+    const EdgeRec a = st.er[vals[i]];
+    wrong += a.seq != kseq[i] || f64_ord(a.sal) != ksal[i] || kseq[i] == 0;
+    const EdgeRec b = st.er[isort[i]];
+    const unsigned long long ks = ksal_sorted[i], q = iseq[i];
+    wrong += b.seq != q || f64_ord(b.sal) != ks;
+    if (i > 0) wrong += ksal_sorted[i - 1] < ks || (ksal_sorted[i - 1] == ks && iseq[i - 1] <= q);
+    const uint32_t c = win_cell(f64_unord(ks), st.wrange[0], st.wrange[1], st.wB);
+    wrong += (long long)c > cthr;
+    wrong += !(ige[c + 1] <= i && i < ige[c]);
+  }
+  if (i <= st.wB) {
+    wrong += i == 0 ? ige[0] != n : ige[i] > ige[i - 1];
+    if (i < st.wB) wrong += ige[i] < ige[i + 1] || st.wcnt[i] != ige[i] - ige[i + 1];
+  }
+  if (wrong) atomicAdd(bad, wrong);
 }
 __global__ void adj_fill_fat(GreedyState g, WinState st, uint32_t E0, uint32_t* cursor) {
   const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -310,24 +386,31 @@ __global__ void fill_leaves_dead(PqTree t, uint32_t from) {
 
 // The window queue's BASELINE on the host: all live queue items sorted by descending (saliency, seq) -- two stable radix sorts
 // (by seq, then by the saliency's order-preserving image), per-cell segments and live counters; the cell lists start empty.
+// The collection leaves compact arrays (seq, saliency key, edge) and the sorts move item NUMBERS: the first sorts (seq, number), one
+// streaming pass gathers the saliency keys in that order, the second sorts (key, number); the fill pass writes isort / isort_seq
+// through the numbers, and it and the segment search take the cells from the sorted keys.  No kernel behind the collection reads a record.
 // Taken at the start (the initial edges) and whenever a launch ends before the queue is empty: the lists only shed their dead
 // nodes when their cell is loaded, so after a few million created edges walking them dominates; a re-sort is ~1 ms of whole-GPU work.
 struct WinBaseline {
-  unsigned long long *kseq = nullptr, *kseq2 = nullptr, *ksal = nullptr, *ksal2 = nullptr, *iseq = nullptr;
-  uint32_t *vals = nullptr, *vals2 = nullptr, *isort = nullptr, *ige = nullptr, *counter = nullptr;
+  unsigned long long *kseq = nullptr, *kseq2 = nullptr, *ksal = nullptr, *ksalg = nullptr, *ksal2 = nullptr, *iseq = nullptr;
+  uint32_t *vals = nullptr, *idx = nullptr, *idx1 = nullptr, *idx2 = nullptr, *isort = nullptr, *ige = nullptr, *counter = nullptr;
   void* tmp = nullptr; size_t tmp_bytes = 0;
   uint32_t E0 = 0;
   double h_range[2] = {0.0, 0.0};                                        // WinState::wrange on the host
   long long prev_top_cell = -1;
   unsigned long long prev_ne = 0;
+  uint32_t n_last = 0;                                                   // items of the last collection (init: the initial edges)
   double horizon_factor = 0.0;                                           // 0 = no horizon (set for the batch kernel)
   bool from_lists = false;                                               // the batch kernel: collect from the lists of the live regions (win_collect_lists_kernel)
   unsigned long long rebuilt_last = 0;                                   // records the last collection rebuilt
+  int seq_bits = 64;                                                     // a seq is (merge + 1) << 32 | cat << 30 | region, merge < R
+  uint32_t lanes_forced = 0;                                             // tests (GLIA_HMT_COLLECT_LANES): lanes per region of the collection pass
+  bool audit = false;                                                    // GLIA_HMT_BASELINE_AUDIT: check every baseline (win_baseline_audit_kernel)
 
   // the queue's device arrays for B saliency cells, and the saliency range of the n_initial initial edges
   int init(DeviceBuffers& buf, WinState& ws, const double* leaf_sal, uint32_t n_initial, uint32_t B, uint32_t R, hipStream_t stream) {
     int rc;
-    E0 = n_initial;
+    E0 = n_initial; n_last = n_initial;
     unsigned long long* mm; double* range;
     if ((rc = buf.get(&ws.rdead, 2 * (size_t)R, true, stream))) return rc;
     if ((rc = buf.get(&ws.whead, B, false, stream))) return rc;
@@ -340,11 +423,20 @@ struct WinBaseline {
     if ((rc = buf.get(&kseq, E0, false, stream))) return rc;
     if ((rc = buf.get(&kseq2, E0, false, stream))) return rc;
     if ((rc = buf.get(&ksal, E0, false, stream))) return rc;
+    if ((rc = buf.get(&ksalg, E0, false, stream))) return rc;
     if ((rc = buf.get(&ksal2, E0, false, stream))) return rc;
     if ((rc = buf.get(&vals, E0, false, stream))) return rc;
-    if ((rc = buf.get(&vals2, E0, false, stream))) return rc;
-    if ((rc = buf.get(&counter, 2, true, stream))) return rc;
-    GLIA_HIP_TRY(rocprim::radix_sort_pairs_desc(nullptr, tmp_bytes, kseq, kseq2, vals, vals2, (size_t)E0, 0, 64, stream));
+    if ((rc = buf.get(&idx, E0, false, stream))) return rc;
+    if ((rc = buf.get(&idx1, E0, false, stream))) return rc;
+    if ((rc = buf.get(&idx2, E0, false, stream))) return rc;
+    if ((rc = buf.get(&counter, 3, true, stream))) return rc;
+    GLIA_HIP_TRY(rocprim::radix_sort_pairs_desc(nullptr, tmp_bytes, kseq, kseq2, idx, idx1, (size_t)E0, 0, 64, stream));
+    seq_bits = 33;
+    while (seq_bits < 63 && ((unsigned long long)R >> (seq_bits - 32)) != 0) ++seq_bits;
+    seq_bits += 1;                                                         // 32 + bits of R + 1: the sort by seq looks at no bit above
+    std::string o_txt;
+    if (option("GLIA_HMT_COLLECT_LANES", &o_txt)) lanes_forced = (uint32_t)strtoul(o_txt.c_str(), nullptr, 10);
+    audit = option("GLIA_HMT_BASELINE_AUDIT", &o_txt) && o_txt[0] != '0';
     if ((rc = buf.get((char**)&tmp, tmp_bytes ? tmp_bytes : 16, false, stream))) return rc;
     ws.wrange = range; ws.isort = isort; ws.isort_seq = iseq; ws.ige = ige;
     const unsigned long long mm0[2] = {~0ull, 0ull};
@@ -356,37 +448,46 @@ struct WinBaseline {
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
     return GLIA_HMT_OK;
   }
-  // every live queue item (seq, edge) into kseq / vals, in any order: from the first n_edges edge records, or from the lists of the
-  // live regions among the first n_regions, rebuilding the records the batch kernel did not write (ws still holds the horizon and
-  // the edge count of the interval that just ended)
+  // every live queue item (seq, saliency key, edge, its own number) into kseq / ksal / vals / idx, in any order: from the first n_edges
+  // edge records, or from the lists of the live regions among the first n_regions, rebuilding the records the batch kernel did not
+  // write (ws still holds the horizon and the edge count of the interval that just ended).
+  // Lanes per region of the list walk: 16 while the lists are short, from numbers the host holds -- the live edges of the last
+  // collection (at the start: the initial edges), each in two lists, over the regions that are left (n_regions - R0 merges so far)
   int collect(const WinState& ws, uint32_t n_edges, uint32_t n_regions, hipStream_t stream, uint32_t* n_out) {
-    GLIA_HIP_TRY(hipMemsetAsync(counter, 0, 2 * sizeof(uint32_t), stream));
-    if (from_lists) hipLaunchKernelGGL(win_collect_lists_kernel, dim3((unsigned)(((unsigned long long)n_regions * 64ull + 255ull) / 256ull)), dim3(256), 0, stream, ws, n_regions, kseq, vals, E0, counter);
-    else hipLaunchKernelGGL(win_collect_kernel, dim3((n_edges + 255) / 256), dim3(256), 0, stream, ws.er, n_edges, ws.rdead, kseq, vals, counter);
+    GLIA_HIP_TRY(hipMemsetAsync(counter, 0, 3 * sizeof(uint32_t), stream));
+    if (from_lists) {
+      const unsigned long long live_regions = 2ull * ws.R0 > n_regions ? 2ull * ws.R0 - n_regions : 1ull;
+      const uint32_t G = lanes_forced == 16u || lanes_forced == 64u ? lanes_forced : 2ull * n_last <= 24ull * live_regions ? 16u : 64u;
+      const dim3 grid((unsigned)(((unsigned long long)n_regions * G + 255ull) / 256ull));
+      const CollectOut out = {kseq, ksal, vals, idx, counter, E0};
+      if (G == 16u) hipLaunchKernelGGL(win_collect_lists_kernel<16u>, grid, dim3(256), 0, stream, ws, n_regions, out);
+      else hipLaunchKernelGGL(win_collect_lists_kernel<64u>, grid, dim3(256), 0, stream, ws, n_regions, out);
+    } else hipLaunchKernelGGL(win_collect_kernel, dim3((n_edges + 255) / 256), dim3(256), 0, stream, ws.er, n_edges, ws.rdead, kseq, vals, counter);
     GLIA_HIP_TRY(hipGetLastError());
     uint32_t h[2] = {0, 0};
     GLIA_HIP_TRY(hipMemcpyAsync(h, counter, sizeof(h), hipMemcpyDeviceToHost, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
     if (h[0] > E0) { set_error("greedy: more live edges than initial edges (internal error)"); return GLIA_HMT_ERR_INTERNAL; }
-    *n_out = h[0]; rebuilt_last = h[1];
+    *n_out = h[0]; rebuilt_last = h[1]; n_last = h[0];
+    if (!from_lists && h[0]) { hipLaunchKernelGGL(win_salkey_kernel, dim3((h[0] + 255) / 256), dim3(256), 0, stream, ws.er, vals, h[0], ksal, idx); GLIA_HIP_TRY(hipGetLastError()); }
     return GLIA_HMT_OK;
   }
   // a fresh baseline of the first n_edges edges (the lists of the first R0 + merges regions); the threshold words of ctrl are reset to
-  // "everything is below it"
+  // "everything is below it": the end of the cell of the largest key
   int rebaseline(WinState& ws, uint32_t n_edges, unsigned long long* ctrl, hipStream_t stream) {
     uint32_t n = 0;
     if (int rc = collect(ws, n_edges, ws.R0 + (uint32_t)ctrl[CTRL_MERGES], stream, &n)) return rc;
     if (n) {
       size_t bytes = tmp_bytes;
-      GLIA_HIP_TRY(rocprim::radix_sort_pairs_desc(tmp, bytes, kseq, kseq2, vals, vals2, (size_t)n, 0, 64, stream));
-      hipLaunchKernelGGL(win_salkey_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, ws.er, vals2, n, ksal);
+      GLIA_HIP_TRY(rocprim::radix_sort_pairs_desc(tmp, bytes, kseq, kseq2, idx, idx1, (size_t)n, 0, (unsigned)seq_bits, stream));
+      hipLaunchKernelGGL(win_gather_key_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, ksal, idx1, n, ksalg);
       bytes = tmp_bytes;
-      GLIA_HIP_TRY(rocprim::radix_sort_pairs_desc(tmp, bytes, ksal, ksal2, vals2, isort, (size_t)n, 0, 64, stream));
+      GLIA_HIP_TRY(rocprim::radix_sort_pairs_desc(tmp, bytes, ksalg, ksal2, idx1, idx2, (size_t)n, 0, 64, stream));
     }
     GLIA_HIP_TRY(hipMemsetAsync(ws.whead, 0xFF, sizeof(uint32_t) * ws.wB, stream));
     GLIA_HIP_TRY(hipMemsetAsync(ws.wcnt, 0, sizeof(uint32_t) * ws.wB, stream));
-    if (n) hipLaunchKernelGGL(win_baseline_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, ws, n, isort, iseq);
-    hipLaunchKernelGGL(win_segments_kernel, dim3((ws.wB + 1 + 255) / 256), dim3(256), 0, stream, ws, isort, n, ige);
+    if (n) hipLaunchKernelGGL(win_baseline_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, ws, n, ksal2, idx2, kseq, vals, isort, iseq);
+    hipLaunchKernelGGL(win_segments_kernel, dim3((ws.wB + 1 + 255) / 256), dim3(256), 0, stream, ws, ksal2, n, ige);
     GLIA_HIP_TRY(hipGetLastError());
     ws.nsort = n;
     std::string renv;                                                      // created edges between baselines (tuning)
@@ -395,11 +496,14 @@ struct WinBaseline {
     // interval is given horizon_factor times that (scaled to its planned length; at least 1/512 of the cells) before a reload
     // would run into the horizon
     ws.wch = 0;
-    if (horizon_factor > 0.0 && n > 4096) {
+    long long top_cell = (long long)ws.wB - 1;                             // the cell of the largest key (nothing alive: the last cell)
+    if (n) {
       unsigned long long topkey = 0;
       GLIA_HIP_TRY(hipMemcpyAsync(&topkey, ksal2, sizeof(topkey), hipMemcpyDeviceToHost, stream));
       GLIA_HIP_TRY(hipStreamSynchronize(stream));
-      const long long top_cell = (long long)win_cell(f64_unord(topkey), h_range[0], h_range[1], ws.wB);
+      top_cell = (long long)win_cell(f64_unord(topkey), h_range[0], h_range[1], ws.wB);
+    }
+    if (horizon_factor > 0.0 && n > 4096) {
       if (prev_top_cell >= 0 && n_edges > prev_ne) {
         const double d = (double)std::max<long long>(0, prev_top_cell - top_cell);
         const double delta = std::max(horizon_factor * d * (double)ws.rebase_after / (double)(n_edges - prev_ne), (double)ws.wB / 512.0);
@@ -409,8 +513,19 @@ struct WinBaseline {
     }
     ws.ne_base = n_edges;
     const double inf = std::numeric_limits<double>::infinity();
-    ctrl[CTRL_CTHR] = (unsigned long long)(long long)(ws.wB - 1);                  // threshold: everything is below it
+    // threshold: the end of the top occupied cell -- everything alive is below it, and the first reload starts at that cell instead of
+    // walking down to it from the last one, 512 empty cells per step (greedy_window.hpp, header comment)
+    ctrl[CTRL_CTHR] = (unsigned long long)top_cell;
     memcpy(&ctrl[CTRL_TSAL], &inf, 8); ctrl[CTRL_TSEQ] = ~0ull; ctrl[CTRL_IPTR] = 0;
+    if (audit) {
+      hipLaunchKernelGGL(win_baseline_audit_kernel, dim3((std::max(n, ws.wB + 1u) + 255u) / 256u), dim3(256), 0, stream, ws, n, kseq, ksal, vals, ksal2, isort, iseq, ige,
+                         top_cell, counter + 2);
+      GLIA_HIP_TRY(hipGetLastError());
+      uint32_t bad = 0;
+      GLIA_HIP_TRY(hipMemcpyAsync(&bad, counter + 2, sizeof(bad), hipMemcpyDeviceToHost, stream));
+      GLIA_HIP_TRY(hipStreamSynchronize(stream));
+      if (bad) { set_error("greedy: the baseline audit found " + std::to_string(bad) + " mismatches (internal error)"); return GLIA_HMT_ERR_INTERNAL; }
+    }
     return GLIA_HMT_OK;
   }
 };

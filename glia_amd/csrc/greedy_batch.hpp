@@ -570,6 +570,8 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_batch_kernel(WinState s
                        atomicAdd(&g_edgeprof[2][0], 0ull), atomicAdd(&g_edgeprof[2][1], 0ull));
   if (tid == 0) printf("[batch profile] merges %llu: select %llu  compute %llu  validate %llu  commit %llu  scan %llu  loop-top %llu  reload %llu (cycles); rounds %llu candidates %llu committed %llu (cut by saliency %llu, by adjacency %llu) wide %llu\n",
                        k, bph[0], bph[1], bph[2], bph[3], bph[4], bph[5], bph[6], brounds, bmembers, bvalid, bcut_sal, bcut_dep, bwide);
+  if (tid == 0) printf("[batch profile] reload parts (cumulative cycles, thread 0): descent over blocks that load nothing %llu  whole-cell loads %llu  cell split %llu;  empty blocks %llu  reloads %llu\n",
+                       g_reloadprof[0], g_reloadprof[1], g_reloadprof[2], g_reloadprof[3], g_reloadprof[4]);
   if (tid == 0) printf("[batch profile] scan phases (cumulative cycles, wave 0): loads %llu  compare %llu  top2 %llu  top2 with a tied best %llu  barrier %llu  calls %llu  tied second %llu  tied best %llu\n",
                        g_scanprof[0], g_scanprof[1], g_scanprof[2], g_scanprof[3], g_scanprof[4], g_scanprof[7], g_scanprof[5], g_scanprof[6]);
   if (tid == 0) printf("[batch profile] scan fill (cumulative; n <= 512, <= 1024, more): after reload/evict %llu %llu %llu  after narrow round %llu %llu %llu  after wide %llu %llu %llu\n",

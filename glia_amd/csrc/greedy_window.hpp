@@ -14,6 +14,15 @@
 //     kernel writes none for an edge below the horizon (store_new_edge<true>), and nothing reads one before the next baseline -- the
 //     kovf look-up and win_take only see window or list items, which lie at or above the horizon; win_take_initial only sees baseline
 //     members.  Record slots of such edges that die are never touched.
+//   * A launch behind a baseline starts with tau at the END of the cell of the baseline's largest key (CTRL_CTHR = that cell, tsal = +inf,
+//     tseq = ~0: WinBaseline::rebaseline), not of the last cell.  It is the same state: nothing alive lies above it -- the baseline
+//     holds every live item, all in cells <= cthr, none above (cthr, +inf, ~0) -- and the window is empty either way.  An item CREATED
+//     above it is a window item under both thresholds' rule (win_above: cell > cthr; win_queue_edge<BATCH> spills to the list and raises
+//     tau if the window is full); with the last cell as threshold it went to its cell's list, and the first reload brought it back.
+//     The readers of w.cthr only compare cells with it: win_above, win_retire_edge (a baseline member dies below or in tau's cell with
+//     dsal < +inf: discounted from its cell, as before), win_queue_edge, win_reload (c_hi = cthr + 1: the first block of cells starts at
+//     the top occupied one instead of 512 cells per step below wB), win_flush / win_evict (raise tau to the cells they push to).  The
+//     horizon relation holds: wch <= the top cell whenever a horizon is placed, so tau's cell is at least wch - 1.  No live item: wB - 1.
 //   * k / ne / pool_used are private copies in every thread (see greedy_tree.hpp); s.newcount is read by all behind a barrier and
 //     cleared by thread 0 only behind the next one.  Audit table: DESIGN 3.3; tags [B:..] barrier, [R:..] read, [W:..] rewrite.
 #pragma once
@@ -274,6 +283,14 @@ __device__ __forceinline__ void win_take_initial(const WinState& st, WinShared& 
 // queue is empty, 2 = a cell's list does not fit the window, 3 = nothing left above the horizon (every thread calls;
 // contains barriers)
 constexpr uint32_t kSelMax = 384;           // list items a split cell hands over at most (bounded min-heap in LDS)
+#ifdef GLIA_HMT_PROFILE
+// where a reload's cycles go (cumulative, thread 0): [0] the descent over blocks of cells that load nothing, [1] whole-cell loads,
+// [2] the split of a cell; [3] blocks of the descent, [4] reloads
+__device__ unsigned long long g_reloadprof[5];
+#define RELOAD_T(i) do { if (tid == 0) { const unsigned long long tn_ = __builtin_readcyclecounter(); g_reloadprof[i] += tn_ - rl_; rl_ = tn_; } } while (0)
+#else
+#define RELOAD_T(i) do {} while (0)
+#endif
 __device__ __forceinline__ int win_reload(const WinState& st, WinShared& w, int tid, double* sel_sal, unsigned long long* sel_seq) {
   full_barrier();                       // (vmcnt(0) inside) this workgroup's list pushes and counter updates are done   // [B:reload-enter]
   if (tid == 0) { w.n = 0; w.need_tree = 0; }   // [W:reload-n]
@@ -281,6 +298,10 @@ __device__ __forceinline__ int win_reload(const WinState& st, WinShared& w, int 
   uint32_t c_hi = (uint32_t)(w.cthr + 1) < st.wB ? (uint32_t)(w.cthr + 1) : st.wB, loaded = 0, iptr = w.iptr;
   int result = 1;
   const uint32_t c_floor = st.wch < st.wB ? st.wch : 0u;      // the horizon: cells below it are not loaded
+#ifdef GLIA_HMT_PROFILE
+  unsigned long long rl_ = __builtin_readcyclecounter();
+  if (tid == 0) g_reloadprof[4] += 1;
+#endif
   while (c_hi > c_floor) {
     const bool valid = (uint32_t)tid < c_hi - c_floor;
     const uint32_t c = valid ? c_hi - 1u - (uint32_t)tid : 0u;
@@ -308,7 +329,11 @@ __device__ __forceinline__ int win_reload(const WinState& st, WinShared& w, int 
       loaded += w.bcast;   // [R:bcast-whole]
       c_hi = c_lo;
       if (loaded) result = 0;
-    }
+#ifdef GLIA_HMT_PROFILE
+      if (w.bcast == 0u) { if (tid == 0) g_reloadprof[3] += 1; RELOAD_T(0); }      // (cells with count 0 "fit whole": a block of them loads nothing)
+      else RELOAD_T(1);
+#endif
+    } else RELOAD_T(0);
     if (m < nvalid) {
       // Cell c* = c_hi - 1 does not fit whole (a tie group of thousands of equal means, typically): the threshold moves
       // INTO the cell.  Its items are a sorted array segment (initial edges) and an unordered list (created edges); thread 0
@@ -392,11 +417,13 @@ __device__ __forceinline__ int win_reload(const WinState& st, WinShared& w, int 
           full_barrier();   // [B:empty-cell]
           if (tid == 0) st_agent(&st.wcnt[cs], 0u);
           c_hi = cs;
+          RELOAD_T(2);
           continue;
         }
         if (tid == 0) { if (moved) atomicSub(&st.wcnt[cs], moved); w.cthr = (int)cs; w.tsal = tsal; w.tseq = tseq; w.iptr = iptr; }   // [W:split-tau]
         if (moved || w.bcast) result = 0;
         full_barrier();   // [B:split-end]
+        RELOAD_T(2);
         return result;
       }
       break;
