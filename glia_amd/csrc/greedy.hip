@@ -104,72 +104,175 @@ __global__ void win_collect_kernel(const EdgeRec* er, uint32_t n_edges, const ui
 // The item's saliency key comes from the entry: the saliency is -entry.mean (edge_fill: leaf_sal = -mean; store_new_edge's callers and
 // rebuild_edge_record: sal = -mean), so no later kernel of the chain asks a record for it.  The seq of a rebuilt record is computed
 // here, every other one is read from the record (the cat bits of a created edge are nowhere else).  Taking the seq of an initial
-// edge as eid + 1 instead (edge_fill) was measured and bought nothing, not even in the first baseline, where every edge is initial
-// (DESIGN 3.3): the pass waits for its chain of dependent loads and its counter, not for that one line.
+// edge as eid + 1 instead (edge_fill) was measured twice and bought nothing, not even in the first baseline, where every edge is
+// initial: neither the old pass nor the two-pass one below waits for that one line.
 // No record is asked whether the edge is queued: in the batch kernel an entry with an edge, in the list of a live region and leading
 // to a live region, IS a queued edge.  The kernel rejects nothing (cond_n <= 0); a popped edge leaves two dead regions; of the edges
 // a contraction replaces, (r0, rs) and (r1, rs), both have a dead end, rs's entry of the one is overwritten in place by the new
 // edge and rs's entry of the other becomes a tombstone (eid = kNone).  A launch only ends between contractions.
-// W = lanes that walk one list (64 or 16); ballot and prefix run within that group of the wave.
-struct CollectOut { unsigned long long *kseq, *ksal; uint32_t *vals, *idx, *counter; uint32_t cap; };
-template <uint32_t W>
-__device__ __forceinline__ uint32_t win_collect_walk(const WinState& st, const CollectOut& out, uint32_t r) {
-  static_assert(W == 16u || W == 64u, "lanes per list");
-  const uint32_t lane = threadIdx.x & 63u, gl = lane & (W - 1u), gshift = lane & ~(W - 1u);
-  const unsigned long long gmask = W == 64u ? ~0ull : ((1ull << W) - 1ull);
-  const uint32_t off = st.adj_off[r], len = st.adj_len[r];
+// The order of the items is free: the two stable sorts behind the pass order by (saliency, seq), and the seqs of live items are
+// distinct.  So where an item goes is decided without a shared counter, in TWO passes over the same lists: the first counts -- per
+// block the items of its short lists, per wave those of the long lists it walks -- an inclusive scan over these kCollectSlots numbers
+// per block turns them into ranges, and the second pass writes.  Measured on the way here (DESIGN 3.3 "Launch boundaries" 5): the
+// pass was bound by its returning atomics on one address, ~20 to 45 ns each however few there were -- one per block for the short
+// lists and one per trip of a walk was no faster than one per group of 16 lanes.
+// A slot is items | rebuilt records << 32 (the items of a run stay far below 2^32: nothing carries over); counter[0] and counter[1]
+// are written from the last slot of the scan.  counter[3] = the number of low key bits in which the collected saliency keys
+// differ at all (from the key of wrange[0], any fixed value would do): every key agrees with it in the bits above, so the sort
+// by key needs no pass over them.
+constexpr uint32_t kCollectSlots = 5;                                    // per block: its short lists, then the walks of each of its four waves
+struct CollectOut { unsigned long long *kseq, *ksal; uint32_t *vals, *idx, *counter; uint32_t cap; unsigned long long *slots, *ranges; };
+struct CollectItem { unsigned long long q, sk; uint32_t e; bool live, rebuild; };
+__device__ __forceinline__ uint32_t collect_key_bits(const CollectItem& it, unsigned long long kref) {
+  const unsigned long long x = it.sk ^ kref;
+  return it.live && x ? 64u - (uint32_t)__builtin_clzll(x) : 0u;
+}
+__device__ __forceinline__ void collect_store(const CollectOut& out, const CollectItem& it, uint32_t o) {
+  if (it.live && o < out.cap) { out.kseq[o] = it.q; out.ksal[o] = it.sk; out.vals[o] = it.e; out.idx[o] = o; }      // (more than cap items: the host stops on the count)
+}
+// K entries per lane of region r's list: entry i[k] where in[k] says that it exists and is this lane's.  Two round trips: the
+// entries; then the partner's rdead and, in the writing pass, the record's seq or the cat bits of a record to rebuild side by side
+// (the seq of an edge whose partner turns out dead is dropped: there are next to none, see above).  Only the rebuild of a record
+// sits under a branch, and it loads nothing: late in a run nearly every live edge was created below the last horizon and is
+// rebuilt here.  The counting pass reads neither records nor cat bits and writes nothing.
+template <int K, bool WRITE>
+__device__ __forceinline__ void win_collect_entries(const WinState& st, uint32_t r, uint32_t off, uint32_t len, const uint32_t (&i)[K], const bool (&in)[K],
+                                                    CollectItem (&it)[K]) {
   const double smin = st.wrange[0], scale = st.wrange[1];
-  uint32_t rebuilt = 0;
-  for (uint32_t base = 0; base < len; base += W) {
-    const uint32_t i = base + gl;
-    unsigned long long q = 0, sk = 0;
-    uint32_t e = kNone;
-    if (i < len) {
-      const FatEntry fe = st.fpool[off + i];
-      if (fe.eid != kNone && fe.rs < r && !st.rdead[fe.rs]) {
-        e = fe.eid;
-        sk = f64_ord(-fe.mean);
-        if ((unsigned long long)e >= st.ne_base && win_cell(-fe.mean, smin, scale, st.wB) < st.wch) {
-          const EdgeRec rec = rebuild_edge_record(fe, i, r, off, len, st.ecat[e], st.R0);
-          st.er[e] = rec;
-          q = rec.seq; ++rebuilt;
-        } else q = st.er[e].seq;
+  FatHalves f[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    f[k].lo = make_uint4(kNone, 0u, 0u, 0u); f[k].hi = make_uint4(0u, 0u, 0u, 0u);
+    if (in[k]) f[k] = fat_load(&st.fpool[off + i[k]]);
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k)      // (whole entries, here: else the fields only a rebuild needs are loaded again under its branch)
+    asm volatile("" :: "v"(f[k].lo.x), "v"(f[k].lo.y), "v"(f[k].lo.z), "v"(f[k].lo.w), "v"(f[k].hi.x), "v"(f[k].hi.y), "v"(f[k].hi.z), "v"(f[k].hi.w));
+  bool cand[K];
+  uint8_t pdead[K], cat[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const uint32_t e = f[k].lo.x, rs = f[k].lo.y;
+    cand[k] = in[k] && e != kNone && rs < r;
+    const bool below = win_cell(-fat_mean(f[k]), smin, scale, st.wB) < st.wch;      // (computed for every entry: a branch round it reloads the mean)
+    it[k].rebuild = cand[k] & ((unsigned long long)e >= st.ne_base) & below;
+    pdead[k] = 0; it[k].q = 0; cat[k] = 0;
+    if (cand[k]) pdead[k] = st.rdead[rs];
+    if constexpr (WRITE) {
+      if (cand[k] && !it[k].rebuild) it[k].q = st.er[e].seq;
+      if (it[k].rebuild) cat[k] = st.ecat[e];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    it[k].live = cand[k] && !pdead[k];
+    it[k].rebuild = it[k].rebuild && it[k].live;
+    it[k].e = f[k].lo.x;
+    it[k].sk = f64_ord(-fat_mean(f[k]));
+    if constexpr (WRITE) {
+      if (it[k].rebuild) {
+        FatEntry fe;
+        fe.eid = f[k].lo.x; fe.rs = f[k].lo.y; fe.n = f[k].lo.z; fe.pos = f[k].lo.w; fe.off = f[k].hi.x; fe.len = f[k].hi.y; fe.mean = fat_mean(f[k]);
+        const EdgeRec rec = rebuild_edge_record(fe, i[k], r, off, len, cat[k], st.R0);
+        st.er[fe.eid] = rec;
+        it[k].q = rec.seq;
       }
     }
-    // (the groups of one wave are not all here, or leave their loops at different times: a lane that is away votes 0, and only the
-    // group's own bits are used)
-    const unsigned long long m = (__ballot(e != kNone) >> gshift) & gmask;
-    if (m == 0) continue;
-    const int first = (int)__builtin_ctzll(m);
-    uint32_t b0 = 0;
-    if ((int)gl == first) b0 = atomicAdd(&out.counter[0], (uint32_t)__popcll(m));
-    b0 = (uint32_t)__shfl((int)b0, (int)gshift + first);
-    const uint32_t o = b0 + (uint32_t)__popcll(m & ((1ull << gl) - 1ull));
-    if (e != kNone && o < out.cap) { out.kseq[o] = q; out.ksal[o] = sk; out.vals[o] = e; out.idx[o] = o; }      // (more than cap items: the host stops on the count)
   }
-  return rebuilt;
 }
-// G = 64: one wave per region.  G = 16: four regions per wave -- lists of ~14 entries leave 50 of 64 lanes idle -- each walked by its
-// group of 16 lanes if it has at most kCollectShort entries; the longer ones among the four (the hubs: thousands of entries late in
-// a run, 63 trips of 16 lanes where the wave needs 16) are then walked by the whole wave, one after the other.
-constexpr uint32_t kCollectShort = 32;
-template <uint32_t G>
-__global__ void win_collect_lists_kernel(WinState st, uint32_t n_regions, CollectOut out) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t rebuilt = 0;
-  if constexpr (G == 64u) {
-    const uint32_t r = t >> 6;
-    if (r >= n_regions || st.rdead[r]) return;                           // (uniform per wave)
-    rebuilt = win_collect_walk<64u>(st, out, r);
-  } else {
-    const uint32_t r = t / G;
-    if (r < n_regions && !st.rdead[r] && st.adj_len[r] <= kCollectShort) rebuilt = win_collect_walk<G>(st, out, r);
-    for (uint32_t j = 0; j < 64u / G; ++j) {
-      const uint32_t rj = (t >> 6) * (64u / G) + j;                      // (uniform per wave)
-      if (rj < n_regions && !st.rdead[rj] && st.adj_len[rj] > kCollectShort) rebuilt += win_collect_walk<64u>(st, out, rj);
+// A whole wave walks the list of region r, kWalkK entries per lane and trip; every lane of the wave is here.  Counting: returns
+// items | rebuilt << 32 of the list (the same in every lane) and lifts *bits to the key bits of its items.  Writing: the items go to
+// o, o + 1, ...; returns their number.
+constexpr int kWalkK = 2;
+template <bool WRITE>
+__device__ __forceinline__ unsigned long long win_collect_walk(const WinState& st, const CollectOut& out, uint32_t r, uint32_t off, uint32_t len, uint32_t o,
+                                                               unsigned long long kref, uint32_t* bits) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  unsigned long long n = 0;
+  for (uint32_t base = 0; base < len; base += 64u * kWalkK) {
+    uint32_t i[kWalkK];
+    bool in[kWalkK];
+#pragma unroll
+    for (int k = 0; k < kWalkK; ++k) { i[k] = base + 64u * (uint32_t)k + lane; in[k] = i[k] < len; }
+    CollectItem it[kWalkK];
+    win_collect_entries<kWalkK, WRITE>(st, r, off, len, i, in, it);
+#pragma unroll
+    for (int k = 0; k < kWalkK; ++k) {
+      const unsigned long long m = __ballot(it[k].live);
+      if constexpr (WRITE) collect_store(out, it[k], o + (uint32_t)n + (uint32_t)__popcll(m & below));
+      else *bits = max(*bits, collect_key_bits(it[k], kref));
+      n += (unsigned long long)__popcll(m) | ((unsigned long long)__popcll(__ballot(it[k].rebuild)) << 32);
     }
   }
-  if (rebuilt) atomicAdd(&out.counter[1], rebuilt);
+  return n;
+}
+// G = 64: one wave per region.  G = 16: four regions per wave, sixteen per block -- lists of ~14 entries leave 50 of 64 lanes idle.
+// A list of at most kCollectShort entries is taken by its group of 16 lanes, both entries of a lane in one round trip; a ballot per
+// wave and the four sums in LDS give the block's count (slot 0 of the block) and, in the writing pass, where each wave starts in
+// the block's range.  EVERY thread of the block reaches the barrier: a dead region, one past n_regions and a long list contribute
+// nothing there (no return, no branch round it).  The long lists among a wave's four (the hubs: thousands of entries late in a
+// run) are walked by the whole wave BEHIND the barrier, one after the other, into the wave's own slot.
+// The header of a region -- rdead, adj_len, adj_off -- is three independent loads for every region (one past the end reads the
+// last one's), followed by selects.
+constexpr uint32_t kCollectShort = 32;
+template <uint32_t G, bool WRITE>
+__global__ void __launch_bounds__(256) win_collect_lists_kernel(WinState st, uint32_t n_regions, CollectOut out) {
+  static_assert(G == 16u || G == 64u, "lanes per list");
+  // (blocks start in the order of their numbers: the newest regions first -- the hubs, whose walks are the longest jobs of the pass)
+  const uint32_t blk = gridDim.x - 1u - blockIdx.x, t = blk * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t r = t / G, rc = r < n_regions ? r : n_regions - 1u;
+  const uint32_t dead = st.rdead[rc], len = st.adj_len[rc], off = st.adj_off[rc];
+  const bool alive = r < n_regions && !dead && len != 0u;
+  const unsigned long long kref = f64_ord(st.wrange[0]);
+  const uint32_t slot0 = blk * kCollectSlots, wslot = slot0 + 1u + wave;
+  // the scan is inclusive: a slot's range starts where the slot in front of it ends
+  const uint32_t wbase = WRITE ? (uint32_t)out.ranges[wslot - 1u] : 0u;
+  unsigned long long walked = 0;                                         // items | rebuilt << 32 of this wave's walks (uniform per wave)
+  uint32_t bits = 0;
+  if constexpr (G == 64u) {
+    if (alive) walked = win_collect_walk<WRITE>(st, out, r, off, len, wbase, kref, &bits);      // (uniform per wave)
+    if (!WRITE && threadIdx.x == 0) out.slots[slot0] = 0;
+  } else {
+    __shared__ uint32_t s_items[4], s_rebuilt[4];
+    const uint32_t gl = lane & (G - 1u);
+    const bool shortl = alive && len <= kCollectShort;
+    const uint32_t i[2] = {gl, gl + G};
+    const bool in[2] = {shortl && i[0] < len, shortl && i[1] < len};
+    CollectItem it[2];
+    win_collect_entries<2, WRITE>(st, rc, off, len, i, in, it);
+    const unsigned long long m0 = __ballot(it[0].live), m1 = __ballot(it[1].live);
+    const uint32_t c0 = (uint32_t)__popcll(m0), c1 = (uint32_t)__popcll(m1);
+    if (lane == 0) { s_items[wave] = c0 + c1; s_rebuilt[wave] = (uint32_t)__popcll(__ballot(it[0].rebuild)) + (uint32_t)__popcll(__ballot(it[1].rebuild)); }
+    if (!WRITE) bits = max(collect_key_bits(it[0], kref), collect_key_bits(it[1], kref));
+    __syncthreads();
+    if constexpr (WRITE) {
+      uint32_t o = slot0 ? (uint32_t)out.ranges[slot0 - 1u] : 0u;
+      for (uint32_t w = 0; w < wave; ++w) o += s_items[w];
+      const unsigned long long below = (1ull << lane) - 1ull;
+      collect_store(out, it[0], o + (uint32_t)__popcll(m0 & below));
+      collect_store(out, it[1], o + c0 + (uint32_t)__popcll(m1 & below));
+    } else if (threadIdx.x == 0)
+      out.slots[slot0] = (unsigned long long)(s_items[0] + s_items[1] + s_items[2] + s_items[3]) |
+                         ((unsigned long long)(s_rebuilt[0] + s_rebuilt[1] + s_rebuilt[2] + s_rebuilt[3]) << 32);
+    for (uint32_t j = 0; j < 64u / G; ++j) {                             // the header of the wave's region j sits in the lanes of its group
+      const uint32_t lenj = (uint32_t)__shfl((int)len, (int)(j * G)), offj = (uint32_t)__shfl((int)off, (int)(j * G));
+      const bool longj = __shfl((int)alive, (int)(j * G)) != 0 && lenj > kCollectShort;
+      if (longj) walked += win_collect_walk<WRITE>(st, out, (t >> 6) * (64u / G) + j, offj, lenj, wbase + (uint32_t)walked, kref, &bits);      // (uniform per wave)
+    }
+  }
+  if constexpr (WRITE) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {                           // the scan's last slot: everything
+      const unsigned long long all = out.ranges[gridDim.x * kCollectSlots - 1u];
+      out.counter[0] = (uint32_t)all; out.counter[1] = (uint32_t)(all >> 32);
+    }
+  } else {
+    if (lane == 0) out.slots[wslot] = walked;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) bits = max(bits, (uint32_t)__shfl_xor((int)bits, d));
+    // (few waves know of more bits than the counter holds by the time they ask)
+    if (lane == 0 && bits != 0u && bits > __hip_atomic_load(&out.counter[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&out.counter[3], bits);
+  }
 }
 // the record scan's items (win_collect_kernel) get their saliency keys from the records
 __global__ void win_salkey_kernel(const EdgeRec* er, const uint32_t* vals, uint32_t n, unsigned long long* ksal, uint32_t* idx) {
@@ -394,6 +497,7 @@ __global__ void fill_leaves_dead(PqTree t, uint32_t from) {
 struct WinBaseline {
   unsigned long long *kseq = nullptr, *kseq2 = nullptr, *ksal = nullptr, *ksalg = nullptr, *ksal2 = nullptr, *iseq = nullptr;
   uint32_t *vals = nullptr, *idx = nullptr, *idx1 = nullptr, *idx2 = nullptr, *isort = nullptr, *ige = nullptr, *counter = nullptr;
+  unsigned long long *slots = nullptr, *ranges = nullptr; size_t slots_cap = 0;      // the collection pass's counts and their inclusive scan
   void* tmp = nullptr; size_t tmp_bytes = 0;
   uint32_t E0 = 0;
   double h_range[2] = {0.0, 0.0};                                        // WinState::wrange on the host
@@ -404,7 +508,11 @@ struct WinBaseline {
   bool from_lists = false;                                               // the batch kernel: collect from the lists of the live regions (win_collect_lists_kernel)
   unsigned long long rebuilt_last = 0;                                   // records the last collection rebuilt
   int seq_bits = 64;                                                     // a seq is (merge + 1) << 32 | cat << 30 | region, merge < R
+  int key_bits = 64;                                                     // the collected saliency keys agree in every bit from this one up (the list walk finds it; the record scan: 64)
   uint32_t lanes_forced = 0;                                             // tests (GLIA_HMT_COLLECT_LANES): lanes per region of the collection pass
+  // GLIA_HMT_REBASE_END: an interval without a horizon in a run that has placed horizons is this many times shorter (1 = as long as
+  // any).  Swept at 1024^3: 1 / 2 / 4 / 8 / 16 / 32 = 727.1 / 716.2 / 714.2 / 713.2 / 714.8 / 719.1 ms of merge loop
+  unsigned long long rebase_end = 8;
   bool audit = false;                                                    // GLIA_HMT_BASELINE_AUDIT: check every baseline (win_baseline_audit_kernel)
 
   // the queue's device arrays for B saliency cells, and the saliency range of the n_initial initial edges
@@ -429,14 +537,22 @@ struct WinBaseline {
     if ((rc = buf.get(&idx, E0, false, stream))) return rc;
     if ((rc = buf.get(&idx1, E0, false, stream))) return rc;
     if ((rc = buf.get(&idx2, E0, false, stream))) return rc;
-    if ((rc = buf.get(&counter, 3, true, stream))) return rc;
+    if ((rc = buf.get(&counter, 4, true, stream))) return rc;                // items, records rebuilt, audit mismatches, key bits (CollectOut)
     GLIA_HIP_TRY(rocprim::radix_sort_pairs_desc(nullptr, tmp_bytes, kseq, kseq2, idx, idx1, (size_t)E0, 0, 64, stream));
+    // the collection pass's slots: kCollectSlots per block of 256 threads, at most one wave for each of the 2 R regions there can be
+    slots_cap = (((size_t)2 * R * 64 + 255) / 256) * kCollectSlots;
+    if ((rc = buf.get(&slots, slots_cap, false, stream))) return rc;
+    if ((rc = buf.get(&ranges, slots_cap, false, stream))) return rc;
+    size_t scan_bytes = 0;
+    GLIA_HIP_TRY(rocprim::inclusive_scan(nullptr, scan_bytes, slots, ranges, slots_cap, rocprim::plus<unsigned long long>(), stream));
+    tmp_bytes = std::max(tmp_bytes, scan_bytes);
     seq_bits = 33;
     while (seq_bits < 63 && ((unsigned long long)R >> (seq_bits - 32)) != 0) ++seq_bits;
     seq_bits += 1;                                                         // 32 + bits of R + 1: the sort by seq looks at no bit above
     std::string o_txt;
     if (option("GLIA_HMT_COLLECT_LANES", &o_txt)) lanes_forced = (uint32_t)strtoul(o_txt.c_str(), nullptr, 10);
     audit = option("GLIA_HMT_BASELINE_AUDIT", &o_txt) && o_txt[0] != '0';
+    if (option("GLIA_HMT_REBASE_END", &o_txt)) rebase_end = std::max(1ull, strtoull(o_txt.c_str(), nullptr, 10));
     if ((rc = buf.get((char**)&tmp, tmp_bytes ? tmp_bytes : 16, false, stream))) return rc;
     ws.wrange = range; ws.isort = isort; ws.isort_seq = iseq; ws.ige = ige;
     const unsigned long long mm0[2] = {~0ull, 0ull};
@@ -454,21 +570,29 @@ struct WinBaseline {
   // Lanes per region of the list walk: 16 while the lists are short, from numbers the host holds -- the live edges of the last
   // collection (at the start: the initial edges), each in two lists, over the regions that are left (n_regions - R0 merges so far)
   int collect(const WinState& ws, uint32_t n_edges, uint32_t n_regions, hipStream_t stream, uint32_t* n_out) {
-    GLIA_HIP_TRY(hipMemsetAsync(counter, 0, 3 * sizeof(uint32_t), stream));
+    GLIA_HIP_TRY(hipMemsetAsync(counter, 0, 4 * sizeof(uint32_t), stream));
     if (from_lists) {
       const unsigned long long live_regions = 2ull * ws.R0 > n_regions ? 2ull * ws.R0 - n_regions : 1ull;
       const uint32_t G = lanes_forced == 16u || lanes_forced == 64u ? lanes_forced : 2ull * n_last <= 24ull * live_regions ? 16u : 64u;
       const dim3 grid((unsigned)(((unsigned long long)n_regions * G + 255ull) / 256ull));
-      const CollectOut out = {kseq, ksal, vals, idx, counter, E0};
-      if (G == 16u) hipLaunchKernelGGL(win_collect_lists_kernel<16u>, grid, dim3(256), 0, stream, ws, n_regions, out);
-      else hipLaunchKernelGGL(win_collect_lists_kernel<64u>, grid, dim3(256), 0, stream, ws, n_regions, out);
+      const CollectOut out = {kseq, ksal, vals, idx, counter, E0, slots, ranges};
+      const size_t n_slots = (size_t)grid.x * kCollectSlots;
+      if (n_slots > slots_cap) { set_error("greedy: the collection pass has more blocks than slots (internal error)"); return GLIA_HMT_ERR_INTERNAL; }
+      // count, scan, write (the kernel's comment)
+      if (G == 16u) hipLaunchKernelGGL((win_collect_lists_kernel<16u, false>), grid, dim3(256), 0, stream, ws, n_regions, out);
+      else hipLaunchKernelGGL((win_collect_lists_kernel<64u, false>), grid, dim3(256), 0, stream, ws, n_regions, out);
+      size_t bytes = tmp_bytes;
+      GLIA_HIP_TRY(rocprim::inclusive_scan(tmp, bytes, slots, ranges, n_slots, rocprim::plus<unsigned long long>(), stream));
+      if (G == 16u) hipLaunchKernelGGL((win_collect_lists_kernel<16u, true>), grid, dim3(256), 0, stream, ws, n_regions, out);
+      else hipLaunchKernelGGL((win_collect_lists_kernel<64u, true>), grid, dim3(256), 0, stream, ws, n_regions, out);
     } else hipLaunchKernelGGL(win_collect_kernel, dim3((n_edges + 255) / 256), dim3(256), 0, stream, ws.er, n_edges, ws.rdead, kseq, vals, counter);
     GLIA_HIP_TRY(hipGetLastError());
-    uint32_t h[2] = {0, 0};
+    uint32_t h[4] = {0, 0, 0, 0};
     GLIA_HIP_TRY(hipMemcpyAsync(h, counter, sizeof(h), hipMemcpyDeviceToHost, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
     if (h[0] > E0) { set_error("greedy: more live edges than initial edges (internal error)"); return GLIA_HMT_ERR_INTERNAL; }
     *n_out = h[0]; rebuilt_last = h[1]; n_last = h[0];
+    key_bits = from_lists ? std::max(1, (int)h[3]) : 64;
     if (!from_lists && h[0]) { hipLaunchKernelGGL(win_salkey_kernel, dim3((h[0] + 255) / 256), dim3(256), 0, stream, ws.er, vals, h[0], ksal, idx); GLIA_HIP_TRY(hipGetLastError()); }
     return GLIA_HMT_OK;
   }
@@ -482,7 +606,7 @@ struct WinBaseline {
       GLIA_HIP_TRY(rocprim::radix_sort_pairs_desc(tmp, bytes, kseq, kseq2, idx, idx1, (size_t)n, 0, (unsigned)seq_bits, stream));
       hipLaunchKernelGGL(win_gather_key_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, ksal, idx1, n, ksalg);
       bytes = tmp_bytes;
-      GLIA_HIP_TRY(rocprim::radix_sort_pairs_desc(tmp, bytes, ksalg, ksal2, idx1, idx2, (size_t)n, 0, 64, stream));
+      GLIA_HIP_TRY(rocprim::radix_sort_pairs_desc(tmp, bytes, ksalg, ksal2, idx1, idx2, (size_t)n, 0, (unsigned)key_bits, stream));
     }
     GLIA_HIP_TRY(hipMemsetAsync(ws.whead, 0xFF, sizeof(uint32_t) * ws.wB, stream));
     GLIA_HIP_TRY(hipMemsetAsync(ws.wcnt, 0, sizeof(uint32_t) * ws.wB, stream));
@@ -511,6 +635,11 @@ struct WinBaseline {
       }
       prev_top_cell = top_cell; prev_ne = n_edges;
     }
+    // a run that placed horizons and is left without one -- no room (the top has come within delta of cell 0) or, what ends a
+    // 1024^3 run, too few items (n <= 4096): every created edge now gets its record, its list push and its count, nearly all die
+    // at the next contraction of the same hub, and the cell lists keep them until a baseline drops them.  The interval, tuned for
+    // 90 % of the created edges staying out of the lists, is cut by rebase_end
+    if (horizon_factor > 0.0 && prev_top_cell >= 0 && n_edges > E0 && ws.wch == 0) ws.rebase_after = std::max<unsigned long long>(1ull, ws.rebase_after / rebase_end);
     ws.ne_base = n_edges;
     const double inf = std::numeric_limits<double>::infinity();
     // threshold: the end of the top occupied cell -- everything alive is below it, and the first reload starts at that cell instead of
@@ -687,7 +816,7 @@ static int run_pb_loop(const RagArrays& rag, hipStream_t stream, const PbRequest
     GLIA_HIP_TRY(hipGetLastError());
     GLIA_HIP_TRY(hipMemcpyAsync(ctrl, st.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
-    if (trace) fprintf(stderr, "[trace] merge loop launch ended: status %llu, merges %llu of %u regions, edges %llu, list entries %llu, records rebuilt %llu\n", ctrl[CTRL_STATUS], ctrl[CTRL_MERGES], R, ctrl[CTRL_EDGES], ctrl[CTRL_ENTRIES], base.rebuilt_last);      // (rebuilt: by the baseline or hand-over in front of this launch)
+    if (trace) fprintf(stderr, "[trace] merge loop launch ended: status %llu, merges %llu of %u regions, edges %llu, list entries %llu, records rebuilt %llu, baseline items %u, horizon %u, interval %llu\n", ctrl[CTRL_STATUS], ctrl[CTRL_MERGES], R, ctrl[CTRL_EDGES], ctrl[CTRL_ENTRIES], base.rebuilt_last, ws.nsort, ws.wch, ws.rebase_after);      // (rebuilt: by the baseline or hand-over in front of this launch)
     base.rebuilt_last = 0;
     if (ctrl[CTRL_STATUS] == ST_DONE) break;
     switch (ctrl[CTRL_STATUS]) {

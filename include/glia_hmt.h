@@ -61,7 +61,7 @@ int glia_hmt_check_merge_order(const uint32_t* h_order, int64_t n_merges, int64_
  * session and __graft_entry__.smoke() assert it. */
 unsigned long long glia_hmt_internal_errors(void);
 /* Tuning and test switches of the loops, process-wide: which queue the pb-mean loop runs on (GLIA_HMT_PB_WINDOW, GLIA_HMT_PB_BATCH,
- * GLIA_HMT_FORCE_TREE), its window size / baseline interval / horizon (GLIA_HMT_WINCAP, GLIA_HMT_REBASE, GLIA_HMT_HORIZON), the
+ * GLIA_HMT_FORCE_TREE), its window size / baseline interval / horizon (GLIA_HMT_WINCAP, GLIA_HMT_REBASE, GLIA_HMT_REBASE_END, GLIA_HMT_HORIZON), the
  * classifier loop's helper workgroups and instance tier (GLIA_HMT_HELPERS, GLIA_HMT_BC_NOCOMMON, GLIA_HMT_BC_GENERIC), the libm
  * variant (GLIA_HMT_LIBM, read when a context is created), GLIA_HMT_TRACE, GLIA_HMT_DEBUG (profiling build).  No setting changes a
  * result.  value = NULL unsets.  The table starts from the environment variables of the same names, read once; nothing in the
