@@ -5,7 +5,7 @@
 // created below the horizon (WinState::wch) is neither queued nor counted, nobody can reach it before the next baseline, and nearly all
 // such edges die before one: its 64-byte record is not written.  Its two list entries are, and they hold every field of the record but
 // the two `cat` bits of its seq (greedy_tree.hpp, update_seq), which go to a byte array indexed by edge slot (WinState::ecat).  The
-// baseline's collection pass rebuilds the records of the survivors (greedy.hip, win_collect_lists_kernel).
+// baseline's collection pass rebuilds the records of the survivors (greedy_baseline.hpp, win_collect_lists_kernel).
 // Plain C++ as well as HIP: cli/edge_rebuild_check.cpp runs the rule on the host.
 #pragma once
 #include <stdint.h>

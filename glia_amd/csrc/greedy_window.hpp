@@ -15,7 +15,7 @@
 //     kovf look-up and win_take only see window or list items, which lie at or above the horizon; win_take_initial only sees baseline
 //     members.  Record slots of such edges that die are never touched.
 //   * A launch behind a baseline starts with tau at the END of the cell of the baseline's largest key (CTRL_CTHR = that cell, tsal = +inf,
-//     tseq = ~0: WinBaseline::rebaseline), not of the last cell.  It is the same state: nothing alive lies above it -- the baseline
+//     tseq = ~0: WinBaseline::rebaseline, greedy_baseline.hpp), not of the last cell.  It is the same state: nothing alive lies above it -- the baseline
 //     holds every live item, all in cells <= cthr, none above (cthr, +inf, ~0) -- and the window is empty either way.  An item CREATED
 //     above it is a window item under both thresholds' rule (win_above: cell > cthr; win_queue_edge<BATCH> spills to the list and raises
 //     tau if the window is full); with the last cell as threshold it went to its cell's list, and the first reload brought it back.
