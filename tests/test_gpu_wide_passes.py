@@ -20,14 +20,12 @@ batch kernel, and with the one-at-a-time window kernel (GLIA_HMT_PB_BATCH=0)."""
 import numpy as np
 import pytest
 
+from _hub_cases import CLASSES, hub_image, kGrid, kMargin, kRegions, width_classes      # noqa: F401 (kGrid, kMargin: part of the case)
+
 pytestmark = pytest.mark.gpu
 
 SETTINGS = [dict(), dict(GLIA_HMT_HORIZON=0), dict(GLIA_HMT_WINCAP=32), dict(GLIA_HMT_WINCAP=16, GLIA_HMT_REBASE=300), dict(GLIA_HMT_REBASE=100),
             dict(GLIA_HMT_FORCE_TREE=200)]
-CLASSES = [("global marks", 1409, None), ("three passes", 1025, 1408), ("two passes", 513, 1024), ("one pass", 193, 512),
-           ("narrow, three per lane", 129, 192), ("narrow, two per lane", 65, 128)]
-kMargin = 8
-kGrid, kRegions = 30, 1801
 
 
 @pytest.fixture(scope="module")
@@ -47,51 +45,6 @@ def _order(ctx, d_lab, d_pb, **env):
         o, s = rm.merge_order_pb(type=2)
         rm.close()
     return o, s
-
-
-def hub_image(levels):
-    """labels (uint32) and pb (float32, seeded random Q8, floored to `levels` levels if given)"""
-    lab = np.ones((6 * kGrid, 6 * kGrid), np.uint32)
-    nxt = 2
-    for cy in range(kGrid):
-        for cx in range(kGrid):
-            y, x = 6 * cy + 1, 6 * cx + 1
-            lab[y:y + 3, x:x + 2] = nxt
-            lab[y:y + 3, x + 2:x + 4] = nxt + 1
-            nxt += 2
-    assert nxt - 1 == kRegions
-    pb = np.random.default_rng(20251020).integers(0, 256, lab.shape).astype(np.float32) / np.float32(256)
-    if levels:
-        pb = np.floor(pb * levels).astype(np.float32) / np.float32(levels)
-    return lab, pb
-
-
-def width_classes(lab, order):
-    """Replays `order` (rows a, b, c: regions a and b become c) on neighbour sets.  Returns per class of CLASSES the number of merges
-    whose contraction is certain to fall into it (see the module docstring)."""
-    nb = {}
-    for a, b in ((lab[:, :-1], lab[:, 1:]), (lab[:-1, :], lab[1:, :])):
-        m = a != b
-        for u, v in set(zip(a[m].tolist(), b[m].tolist())):
-            nb.setdefault(u, set()).add(v)
-            nb.setdefault(v, set()).add(u)
-    length = {r: len(s) for r, s in nb.items()}
-    hits = [0] * len(CLASSES)
-    for a, b, c in order.tolist():
-        assert b in nb[a] and a in nb[b], "the order merges regions that are not neighbours"
-        live, entries = len(nb[a]) + len(nb[b]), length[a] + length[b]
-        assert live <= entries
-        for j, (_, lo, hi) in enumerate(CLASSES):
-            if live >= lo and (hi is None or entries <= hi - kMargin):
-                hits[j] += 1
-        new = (nb.pop(a) | nb.pop(b)) - {a, b}
-        for r in new:
-            nb[r] -= {a, b}
-            nb[r].add(c)
-        nb[c] = new
-        length[c] = len(new)
-    assert len(nb) == 1
-    return hits
 
 
 _cache = {}
