@@ -579,6 +579,133 @@ class FeatureStubClassifier(RandomForest):
         _check(lib().glia_hmt_forest_stub(ctx.h, C.c_int(index), C.byref(self.h)))
 
 
+def mlp_limits(n1=10, n2=10):
+    """glia_hmt_mlp_limits: the tier boundaries of MLP.predict under hidden layers of n1 and n2 units (0, 0: logsig) -- stage_max_dim (the
+    longest row staged in LDS; longer rows are read from global memory; 0: none), unit_block (hidden units a thread accumulates at a
+    time), slots (waves that split a layer), max_hidden, max_dim.  Host-only."""
+    v = [C.c_int() for _ in range(5)]
+    _check(lib().glia_hmt_mlp_limits(C.c_int(n1), C.c_int(n2), *[C.byref(x) for x in v]))
+    return dict(zip(("stage_max_dim", "unit_block", "slots", "max_hidden", "max_dim"), (x.value for x in v)))
+
+
+def mlp_tile_rows(dim, n1, n2):
+    """glia_hmt_mlp_predict_tile_rows: (rows of a workgroup's tile, whether rows of dim columns are staged in LDS).  Host-only."""
+    staged = C.c_int()
+    r = lib().glia_hmt_mlp_predict_tile_rows(C.c_int(dim), C.c_int(n1), C.c_int(n2), C.byref(staged))
+    if r < 0:
+        raise HmtError(r, lib().glia_hmt_last_error().decode())
+    return r, bool(staged.value)
+
+
+def mlp_file_parse(path):
+    """glia_hmt_mlp_file_parse: the weights of a model file (readData(w, file, true)).  Host-only."""
+    n = C.c_int64()
+    _check(lib().glia_hmt_mlp_file_parse(str(path).encode(), None, C.c_int64(0), C.byref(n)))
+    w = np.empty(n.value, np.float64)
+    _check(lib().glia_hmt_mlp_file_parse(str(path).encode(), _np(w), C.c_int64(n.value), C.byref(n)))
+    return w
+
+
+class MLP:
+    """alg::MLP2v / alg::EnsembleMLP2v (alg/nn.hxx) -- pred_mlp's classifier (sshmt/main_pred_mlp.cxx): one model file or three with
+    distributor_args = (dim0, dim1, threshold), hidden layers of n1 and n2 units, an optional min/max file to rescale rows by.
+    ctx = None gives a host-only model (predict_host).  The arithmetic: DESIGN 3.13."""
+
+    def __init__(self, ctx, model_files, n1, n2, minmax=None, distributor_args=None):
+        if isinstance(model_files, (str, os.PathLike)):
+            model_files = [model_files]
+        arr = (C.c_char_p * len(model_files))(*[str(m).encode() for m in model_files])
+        dist = (C.c_double * 3)(*distributor_args) if distributor_args is not None else None
+        self.h = C.c_void_p()
+        self.ctx = ctx
+        _check(lib().glia_hmt_mlp_load(ctx.h if ctx is not None else None, C.c_int(len(model_files)), arr, C.c_int(n1), C.c_int(n2),
+                                       str(minmax).encode() if minmax is not None else None, dist, C.byref(self.h)))
+
+    @classmethod
+    def from_arrays(cls, ctx, weights, n1, n2, mn=None, mx=None, distributor_args=None):
+        """glia_hmt_mlp_create: weights = one array or a list of three (the model files' values)"""
+        if isinstance(weights, np.ndarray):
+            weights = [weights]
+        ws = [np.ascontiguousarray(w, dtype=np.float64) for w in weights]
+        self = cls.__new__(cls)
+        self.h = C.c_void_p()
+        self.ctx = ctx
+        ptrs = (C.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
+        lens = (C.c_int64 * len(ws))(*[w.size for w in ws])
+        dist = (C.c_double * 3)(*distributor_args) if distributor_args is not None else None
+        if mn is not None:
+            mn = np.ascontiguousarray(mn, dtype=np.float64); mx = np.ascontiguousarray(mx, dtype=np.float64)
+        _check(lib().glia_hmt_mlp_create(ctx.h if ctx is not None else None, C.c_int(len(ws)), ptrs, lens, C.c_int(n1), C.c_int(n2),
+                                         _np(mn) if mn is not None else None, _np(mx) if mn is not None else None,
+                                         C.c_int64(min(mn.size, mx.size) if mn is not None else 0), dist, C.byref(self.h)))
+        return self
+
+    @property
+    def dim(self):
+        """glia_hmt_mlp_dim: the columns a row must have"""
+        return lib().glia_hmt_mlp_dim(self.h)
+
+    def predict_host(self, rows, want_logits=False):
+        """glia_hmt_mlp_predict_host: the definition's forward pass on the host, no GPU"""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        assert rows.ndim == 2
+        pred = np.empty(rows.shape[0], np.float64); logit = np.empty(rows.shape[0], np.float64)
+        _check(lib().glia_hmt_mlp_predict_host(self.h, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(pred), _np(logit)))
+        return (pred, logit) if want_logits else pred
+
+    def predict(self, rows, want_logits=False):
+        """pred_mlp (sshmt/main_pred_mlp.cxx:34-46): the classifier's value for every row of an [n, dim] float64 array.  A NumPy array
+        goes through glia_hmt_mlp_predict (rows streamed in chunks, the sigmoid applied on the host) and comes back as NumPy; a CUDA
+        tensor (rows contiguous, any row stride) goes through glia_hmt_mlp_predict_device (the sigmoid computed on the device) and comes
+        back as a tensor on the same device.  want_logits: (predictions, logits)."""
+        if self.ctx is None:
+            raise HmtError(ERR_ARG, "MLP.predict: a host-only model (ctx = None) has no device side; use predict_host")
+        if isinstance(rows, np.ndarray):
+            rows = np.ascontiguousarray(rows, dtype=np.float64)
+            assert rows.ndim == 2
+            pred = np.empty(rows.shape[0], np.float64); logit = np.empty(rows.shape[0], np.float64)
+            _check(lib().glia_hmt_mlp_predict(self.ctx.h, self.h, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(pred), _np(logit)))
+            return (pred, logit) if want_logits else pred
+        import torch
+        assert rows.is_cuda and rows.dtype == torch.float64 and rows.dim() == 2 and (rows.shape[1] == 0 or rows.stride(1) == 1)
+        assert rows.shape[0] <= 1 or rows.stride(0) >= rows.shape[1]
+        pred = torch.empty(rows.shape[0], dtype=torch.float64, device=rows.device)
+        logit = torch.empty(rows.shape[0], dtype=torch.float64, device=rows.device) if want_logits else None
+        _fence(rows)
+        _check(lib().glia_hmt_mlp_predict_device(self.ctx.h, self.h, C.c_void_p(rows.data_ptr()), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]),
+                                                 C.c_int64(rows.stride(0) if rows.shape[0] > 1 else rows.shape[1]), C.c_void_p(pred.data_ptr()),
+                                                 C.c_void_p(logit.data_ptr()) if want_logits else None))
+        self.ctx.sync()
+        return (pred, logit) if want_logits else pred
+
+    def close(self):
+        if self.h:
+            lib().glia_hmt_mlp_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Logsig(MLP):
+    """alg::Logsig (alg/function.hxx:33-34) -- pred_logsig's classifier (sshmt/main_pred_logsig.cxx): 1 / (1 + exp(-(x, 1) . w))."""
+
+    def __init__(self, ctx, model_file):
+        super().__init__(ctx, model_file, 0, 0)
+
+
+def mlp_predict_host(weights, n1, n2, rows, mn=None, mx=None, distributor_args=None):
+    """glia_hmt_mlp_predict_host on arrays: (predictions, logits) of the definition's forward pass; no GPU, no context."""
+    m = MLP.from_arrays(None, weights, n1, n2, mn, mx, distributor_args)
+    try:
+        return m.predict_host(rows, want_logits=True)
+    finally:
+        m.close()
+
+
 class TrainOpts(C.Structure):
     """glia_hmt_train_opts: train_rf's options (ml/rf/main_train_rf.cxx:11-15) + max_depth + seed"""
     _fields_ = [("ntree", C.c_int), ("mtry", C.c_int), ("sample_ratio", C.c_double), ("nodesize", C.c_int), ("balance", C.c_int),

@@ -287,6 +287,52 @@ int glia_hmt_forest_predict_device(glia_hmt_ctx* ctx, const glia_hmt_forest* for
  * length are not staged (dim > GLIA_HMT_PREDICT_STAGE_MAX_DIM).  For tests and tuning; no result depends on it. */
 int glia_hmt_forest_predict_tile_rows(int64_t n_rows, int dim);
 
+/* ---- the MLP and logsig batch predictors --------------------------------------------------------------
+ * Replace pred_mlp (sshmt/main_pred_mlp.cxx:18-48) and pred_logsig (sshmt/main_pred_logsig.cxx:12-32): alg::MLP2v /
+ * alg::EnsembleMLP2v (alg/nn.hxx:14-254; two ReLU hidden layers of n1 and n2 units, a sigmoid output) and alg::Logsig
+ * (alg/function.hxx:33-34; n1 = n2 = 0) over feature rows -- what bc_feat -b writes.  Per row: stats::rescale to [-1, 1] when a min/max
+ * table is given (util/stats.hxx:265-277), a 1.0 appended, for three models the pick of opt::ThresholdModelDistributor
+ * (type/function.hxx:80-84) on that RESCALED, bias-appended vector (indices in [0, dim]), the layers, 1 / (1 + exp(-logit)).
+ * The arithmetic is this library's own definition (glia_amd/csrc/mlp_model.hpp): every sum starts at 0.0 and takes
+ * its terms in ascending index order, multiply and add rounded separately.  The reference computes the same sums through Eigen, in an
+ * order that depends on how Eigen vectorises: parity with its last bits is not claimed.  Host forward pass and kernel agree bit for bit
+ * on the logits.
+ * A model is the reference's text file of weights (readData(w, file, true)): D * n1 + (n1 + 1) * n2 + n2 + 1 doubles with D = columns
+ * of a row + 1 (logsig: D doubles).  A count that gives no whole D, or D < 2: GLIA_HMT_ERR_ARG with a message (the reference
+ * truncates).  n1 or n2 above 256, rows of more than 65535 columns: GLIA_HMT_ERR_UNSUPPORTED.  Unlike alg::MLP2v(N1, N2, file)
+ * (nn.hxx:150-154), which reads the file and never copies the weights in, a single model is loaded.
+ * glia_hmt_mlp_file_parse (host-only): the doubles of a model file; h_w may be NULL to ask for *n_weights alone.
+ * glia_hmt_mlp_create / _load: ctx may be NULL for a host-only handle (glia_hmt_mlp_predict_host and glia_hmt_mlp_dim only).
+ * h_min / h_max: n_minmax >= dim entries each (extras ignored; fewer: GLIA_HMT_ERR_ARG), NULL = no rescale; the min/max file has two
+ * rows, minima then maxima.  distributor_args = {dim0, dim1, threshold}, required for three models.
+ * Prediction: any number of rows (beyond 2^23 tiles the work takes several launches); dim != glia_hmt_mlp_dim is GLIA_HMT_ERR_ARG, n_rows == 0 is GLIA_HMT_OK, two calls with the same arguments return
+ * identical bytes; h_pred / h_logit (d_pred / d_logit) may each be NULL, not both.
+ * glia_hmt_mlp_predict_host: the header's forward pass, no GPU.
+ * glia_hmt_mlp_predict_device: device rows (row i at d_rows + i * row_stride doubles, the padding is never read), ordered on the
+ * context's stream; the sigmoid is computed on the device (within a few ulps of the host's).
+ * glia_hmt_mlp_predict: host rows streamed through bounded device buffers; the kernel returns the logits and the sigmoid is applied on
+ * the host with the host's exp, so h_pred is what a host program computes from h_logit. */
+typedef struct glia_hmt_mlp glia_hmt_mlp;
+int glia_hmt_mlp_file_parse(const char* path, double* h_w, int64_t capacity, int64_t* n_weights);
+int glia_hmt_mlp_create(glia_hmt_ctx* ctx, int n_models /*1 or 3*/, const double* const* h_weights, const int64_t* n_weights, int n1, int n2,
+                        const double* h_min, const double* h_max /*NULL: no rescale*/, int64_t n_minmax,
+                        const double* distributor_args /*[3] or NULL*/, glia_hmt_mlp** out);
+int glia_hmt_mlp_load(glia_hmt_ctx* ctx, int n_models, const char* const* paths, int n1, int n2, const char* minmax_path /*or NULL*/,
+                      const double* distributor_args /*[3] or NULL*/, glia_hmt_mlp** out);
+int glia_hmt_mlp_dim(const glia_hmt_mlp* mlp);   /* the columns a row must have */
+void glia_hmt_mlp_free(glia_hmt_mlp* mlp);
+int glia_hmt_mlp_predict_host(const glia_hmt_mlp* mlp, const double* h_rows, int64_t n_rows, int dim, double* h_pred, double* h_logit);
+int glia_hmt_mlp_predict_device(glia_hmt_ctx* ctx, const glia_hmt_mlp* mlp, const double* d_rows, int64_t n_rows, int dim,
+                                int64_t row_stride /* doubles, >= dim */, double* d_pred /*or NULL*/, double* d_logit /*or NULL*/);
+int glia_hmt_mlp_predict(glia_hmt_ctx* ctx, const glia_hmt_mlp* mlp, const double* h_rows, int64_t n_rows, int dim, double* h_pred,
+                         double* h_logit /*or NULL*/);
+/* Host-only, for tests and tuning; no result depends on them.  glia_hmt_mlp_limits: the longest row that is staged in LDS under hidden
+ * layers of n1 and n2 units (longer rows are read from global memory), the most hidden units a thread accumulates at a time, the waves
+ * that split a layer's units, the largest n1 / n2 and the most columns.  glia_hmt_mlp_predict_tile_rows: the rows of a workgroup's tile
+ * (64, 32, 16 or 8; below 64 the upper lanes of every wave idle) and whether rows of dim columns are staged. */
+int glia_hmt_mlp_limits(int n1, int n2, int* stage_max_dim, int* unit_block, int* slots, int* max_hidden, int* max_dim);
+int glia_hmt_mlp_predict_tile_rows(int dim, int n1, int n2, int* staged);
+
 /* ---- training the boundary classifier ---------------------------------------------------------------
  * Replaces train_rf (ml/rf/main_train_rf.cxx:18-70): rf_old::train around classRF (ml/rf/ml_rf_train.cxx:234, whose sources the
  * reference tree does not hold) and rf_old::writeModelToBinaryFile (ml/rf/ml_rf_model.cxx:378-455).  The flags, their defaults, the
