@@ -1,7 +1,10 @@
-// cli/merge_order_bc.cpp -- drop-in for hmt/main_merge_order_bc.cxx (boundary classifier type 1: random forest).
+// cli/merge_order_bc.cpp -- drop-in for hmt/main_merge_order_bc.cxx (boundary classifier type 1: random forest; type 2: MLP2).
 //   merge_order_bc --bct 1 --bcm model.bin [--bcm m1 --bcm m2 --bcmd d0 --bcmd d1 --bcmd thr] -s seg.mha --pb pb.mha
 //                  [--rbi img --rbb bins --rbl lo --rbu hi] [--bt t0 t1 ..] [-n 0|1] [-l 0|1] [--simpf 0|1]
 //                  -o order.txt [--sal saliency.txt] [-b feats.txt]
+//   merge_order_bc --bct 2 --nn1 N --nn2 N --bcm model [--bcm m1 --bcm m2 --bcmd d0 --bcmd d1 --bcmd thr] [--bcfmm minmax] ...
+//     (:111-139; the hidden sizes default to 10 and 10, :21-22; the min/max file as pred_mlp's --fmm: without it rows are not rescaled;
+//     the -b rows are the raw rows; at most glia_hmt_mlp_loop_limits units per hidden layer)
 // Limits: at most eight images per list, four distinct (volume, histogram) channels in total, 384 feature columns before --simpf.
 //   --slabs N [--rank r --commId file]: the z-slab route (cli/merge_order_pb.cpp, include/glia_hmt.h): every image volume is read by
 //   plane range, slab by slab; rank 0 scores and merges.  No mask in this mode.
@@ -10,7 +13,7 @@
 using namespace cli;
 
 int main(int argc, char* argv[]) {
-  const std::string usage = "Usage: merge_order_bc --bct 1 --bcm <model>... -s <seg> --pb <pb> [--rbi/--rbb/--rbl/--rbu ...] [--bt ...] "
+  const std::string usage = "Usage: merge_order_bc --bct 1|2 [--nn1 N --nn2 N --bcfmm <minmax>] --bcm <model>... -s <seg> --pb <pb> [--rbi/--rbb/--rbl/--rbu ...] [--bt ...] "
                             "[-n b] [-l b] [--simpf b] -o <order> [--sal <file>] [-b <file>]   (flags as hmt/main_merge_order_bc.cxx:172-242)\n";
   std::vector<std::string> known = {"bct", "nn1", "nn2", "bcm", "bcfmm", "bcmd", "segImage", "rbi", "rbb", "rbl", "rbu", "rli", "rlb", "rll", "rlu",
                                     "ri", "rb", "rl", "ru", "bi", "bb", "bl", "bu", "pb", "maskImage", "bt", "ns", "logs", "simpf", "histf", "medf", "mergeOrder",
@@ -18,9 +21,11 @@ int main(int argc, char* argv[]) {
   Args a = parse(argc, argv, {{"s", "segImage"}, {"m", "maskImage"}, {"n", "ns"}, {"l", "logs"}, {"o", "mergeOrder"}, {"b", "bfeat"}}, known, usage);
   for (const char* req : {"bct", "bcm", "segImage", "pb", "mergeOrder"})
     if (!a.has(req)) { std::cerr << "Error: the option '--" << req << "' is required but missing\n" << usage; perr("Error: unable to parse input arguments"); }
-  if (atoi(a.str("bct").c_str()) != 1) perr("Error: unsupported classifier type...");     // MLP2 (--bct 2) is out of scope
+  const int bct = atoi(a.str("bct").c_str());
+  if (bct != 1 && bct != 2) perr("Error: unsupported classifier type...");     // :125
+  if (a.all("bcm").size() > 1 && a.all("bcmd").size() != 3) perr("Error: model distributor needs 3 arguments...");   // :103-104, :117-118
   FeatInputs f;
-  glia_hmt_ctx* ctx; glia_hmt_rag* rag = nullptr; glia_hmt_forest* bc;
+  glia_hmt_ctx* ctx; glia_hmt_rag* rag = nullptr; glia_hmt_forest* bc = nullptr; glia_hmt_mlp* mlp = nullptr;
   const int slabs = atoi(a.str("slabs", "0").c_str());
   if (slabs > 0) {
     if (a.has("maskImage")) perr("Error: the slab route takes no mask...");
@@ -58,19 +63,24 @@ int main(int argc, char* argv[]) {
   double dist[3] = {0, 0, 0};
   if (models.size() > 1) {
     auto d = a.all("bcmd");
-    if (d.size() != 3) perr("Error: model distributor needs 3 arguments...");   // :103-104
     for (int i = 0; i < 3; ++i) dist[i] = atof(d[i].c_str());
   }
-  check(glia_hmt_forest_load(ctx, (int)paths.size(), paths.data(), /*BC_LABEL_MERGE*/ -1, models.size() > 1 ? dist : nullptr, &bc));
+  if (bct == 1) check(glia_hmt_forest_load(ctx, (int)paths.size(), paths.data(), /*BC_LABEL_MERGE*/ -1, models.size() > 1 ? dist : nullptr, &bc));
+  else {
+    const std::string fmm = a.str("bcfmm");
+    check(glia_hmt_mlp_load(ctx, (int)paths.size(), paths.data(), atoi(a.str("nn1", "10").c_str()), atoi(a.str("nn2", "10").c_str()),
+                            fmm.empty() ? nullptr : fmm.c_str(), models.size() > 1 ? dist : nullptr, &mlp));
+  }
   int64_t cap = glia_hmt_rag_num_regions(rag), n = 0;
   const int d = glia_hmt_feat_dim(rag);
   std::vector<uint32_t> order(3 * (cap ? cap : 1));
   std::vector<double> sal(cap ? cap : 1), feats(a.has("bfeat") ? (size_t)(cap ? cap : 1) * d : 0);
-  check(glia_hmt_merge_order_bc(ctx, rag, bc, order.data(), sal.data(), a.has("bfeat") ? feats.data() : nullptr, cap, &n));
+  if (bct == 1) check(glia_hmt_merge_order_bc(ctx, rag, bc, order.data(), sal.data(), a.has("bfeat") ? feats.data() : nullptr, cap, &n));
+  else check(glia_hmt_merge_order_bc_mlp(ctx, rag, mlp, order.data(), sal.data(), a.has("bfeat") ? feats.data() : nullptr, cap, &n));
   writeOrder(a.str("mergeOrder"), order, n);                                     // :148-157
   if (a.has("sal")) writeDoubles(a.str("sal"), sal.data(), n);
   if (a.has("bfeat")) writeRows(a.str("bfeat"), feats.data(), n, d, /*FLT_PREC*/ 8);
-  glia_hmt_forest_free(bc); glia_hmt_rag_free(rag); glia_hmt_ctx_destroy(ctx);
+  glia_hmt_forest_free(bc); glia_hmt_mlp_free(mlp); glia_hmt_rag_free(rag); glia_hmt_ctx_destroy(ctx);
   if (f.dLab) (void)hipFree(f.dLab);
   if (f.dPb) (void)hipFree(f.dPb);
   return EXIT_SUCCESS;

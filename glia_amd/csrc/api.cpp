@@ -96,8 +96,8 @@ static LibmSel probe_host_libm() {
   for (int i = 0; i < 3000; ++i) xs.push_back(1.0 + ((double)(int64_t)(next() % 2000001) - 1000000.0) * 1e-7);
   for (int i = 0; i < 3000; ++i) xs.push_back(std::ldexp(1.0 + (double)(next() >> 12) * 0x1p-52, (int)(next() % 120) - 60));
   for (int e = -1074; e < 1024; e += 37) xs.push_back(std::ldexp(1.0, e));
-  LibmSel sel = {kLibmDevice, kLibmDevice, kLibmDevice};
-  bool l2 = true, ls = true, lf = true, ps = true, pf = true;
+  LibmSel sel = {kLibmDevice, kLibmDevice, kLibmDevice, kLibmDevice};
+  bool l2 = true, ls = true, lf = true, ps = true, pf = true, es = true, ef = true;
   for (double x : xs) {
     volatile double vx = x;
     const double h2 = std::log2(vx), h1 = std::log(vx);
@@ -113,6 +113,22 @@ static LibmSel probe_host_libm() {
     ps = ps && h == glibc::as_u64(glibc::pow_sse2(x, 1.5));
     pf = pf && h == glibc::as_u64(glibc::pow_fma(x, 1.5));
   }
+  // std::exp of the MLP's sigmoid (alg/nn.hxx; mlp_model.hpp): logits and their negatives over the range a sigmoid resolves, the
+  // special-cased range beyond 512, and three arguments on which the two builds are known to differ
+  {
+    std::vector<double> es_x = {0x1.abe9a7aa19388p-1, 0x1.2993abd96c7dp+4, -0x1.31e0da89a5188p-2, 0.0, -0.0, 0x1p-54, -0x1p-55, 512.0, -512.0,
+                                709.782712893384, 710.0, -745.2, -1024.0, 1e308};
+    for (int i = 0; i < 6000; ++i) es_x.push_back(((double)(int64_t)(next() % 100000001) - 50000000.0) * 1e-6);      // [-50, 50]
+    for (int i = 0; i < 3000; ++i) es_x.push_back(((double)(int64_t)(next() % 2000001) - 1000000.0) * 1e-3);         // [-1000, 1000]
+    for (int i = 0; i < 3000; ++i) es_x.push_back((i & 1 ? -1.0 : 1.0) * (500.0 + (double)(next() % 2200001) * 1e-4)); // +-[500, 720]
+    for (double x : es_x) {
+      volatile double vx = x;
+      const uint64_t h = glibc::as_u64(std::exp(vx));
+      es = es && h == glibc::as_u64(glibc::exp_sse2(x));
+      ef = ef && h == glibc::as_u64(glibc::exp_fma(x));
+    }
+  }
+  if (ef) sel.exp_variant = kLibmFma; else if (es) sel.exp_variant = kLibmSse2;
   if (l2) sel.log2_variant = kLibmSse2;
   if (lf) sel.log_variant = kLibmFma; else if (ls) sel.log_variant = kLibmSse2;
   if (pf) sel.pow_variant = kLibmFma; else if (ps) sel.pow_variant = kLibmSse2;
@@ -120,7 +136,7 @@ static LibmSel probe_host_libm() {
   if (option("GLIA_HMT_LIBM", &ov)) {
     const char* e = ov.c_str();
     const int v = !strcmp(e, "sse2") ? kLibmSse2 : !strcmp(e, "fma") ? kLibmFma : kLibmDevice;
-    sel.log_variant = v; sel.log2_variant = v == kLibmFma ? kLibmSse2 : v; sel.pow_variant = v;
+    sel.log_variant = v; sel.log2_variant = v == kLibmFma ? kLibmSse2 : v; sel.pow_variant = v; sel.exp_variant = v;
   }
   return sel;
 }
@@ -183,6 +199,18 @@ int glia_hmt_ctx_libm_pow(const glia_hmt_ctx* c, int* pow_variant) {
   return GLIA_HMT_OK;
 }
 
+int glia_hmt_ctx_libm_exp(const glia_hmt_ctx* c, int* exp_variant) {
+  if (!c || !exp_variant) return GLIA_HMT_ERR_ARG;
+  *exp_variant = c->libm.exp_variant;
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_host_libm_probe_exp(int* exp_variant) {
+  if (!exp_variant) return GLIA_HMT_ERR_ARG;
+  *exp_variant = probe_host_libm().exp_variant;
+  return GLIA_HMT_OK;
+}
+
 int glia_hmt_host_libm_probe_pow(int* pow_variant) {
   if (!pow_variant) return GLIA_HMT_ERR_ARG;
   *pow_variant = probe_host_libm().pow_variant;
@@ -207,20 +235,22 @@ int glia_hmt_host_libm_probe(int* log2_variant, int* log_variant) {
 }
 
 int glia_hmt_host_libm_eval(int function, int variant, const double* h_in, double* h_out, int64_t n) {
-  if (!h_in || !h_out || n < 0 || function < 0 || function > 2 || (variant != kLibmSse2 && variant != kLibmFma)) {
+  if (!h_in || !h_out || n < 0 || function < 0 || function > 4 || (variant != kLibmSse2 && variant != kLibmFma)) {
     set_error("host_libm_eval: invalid argument");
     return GLIA_HMT_ERR_ARG;
   }
   for (int64_t i = 0; i < n; ++i) {
     const double x = h_in[i];
-    if (function == 2) h_out[i] = !glibc::pow_in_domain(x, 1.5) ? std::pow(x, 1.5) : variant == kLibmFma ? glibc::pow_fma(x, 1.5) : glibc::pow_sse2(x, 1.5);
+    if (function == 3) h_out[i] = variant == kLibmFma ? glibc::exp_fma(x) : glibc::exp_sse2(x);
+    else if (function == 4) h_out[i] = glibc::sigmoid(x, variant);
+    else if (function == 2) h_out[i] = !glibc::pow_in_domain(x, 1.5) ? std::pow(x, 1.5) : variant == kLibmFma ? glibc::pow_fma(x, 1.5) : glibc::pow_sse2(x, 1.5);
     else h_out[i] = function == 0 ? glibc::log2_sse2(x) : variant == kLibmFma ? glibc::log_fma(x) : glibc::log_sse2(x);
   }
   return GLIA_HMT_OK;
 }
 
 int glia_hmt_libm_eval(glia_hmt_ctx* c, int function, int variant, const double* d_in, double* d_out, int64_t n) {
-  if (!c || !d_in || !d_out || n < 0 || function < 0 || function > 2) { set_error("libm_eval: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  if (!c || !d_in || !d_out || n < 0 || function < 0 || function > 4) { set_error("libm_eval: invalid argument"); return GLIA_HMT_ERR_ARG; }
   GLIA_HIP_TRY(hipSetDevice(c->device));
   return launch_libm_eval(function, variant, d_in, d_out, n, c->stream);
 }

@@ -20,6 +20,7 @@ GLIA_DECLARE_GREEDY_BC(greedy_bc) {
   if (cfg.libm_log2 == kLibmSse2 && cfg.libm_log == kLibmFma && cfg.libm_pow == kLibmFma) fn = common ? &greedy_bc_fma_common : &greedy_bc_fma;
   else if (cfg.libm_log2 == kLibmSse2 && cfg.libm_log == kLibmSse2 && cfg.libm_pow == kLibmSse2) fn = common ? &greedy_bc_sse2_common : &greedy_bc_sse2;
   if (option("GLIA_HMT_BC_GENERIC")) fn = &greedy_bc_generic;       // tests: the run-time-dispatch instance
+  if (clf.kind == 2) fn = &greedy_bc_mlp;                           // the one instance that holds the MLP scorer
   const int rc = fn(rag, cfg, clf, stream, req, out);
   return req.init_only ? rc : finish_merge_order(rc, out->order.data(), out->n, (uint32_t)rag.R, stream);
 }
@@ -374,6 +375,23 @@ static int bc_setup(glia_hmt_ctx* c, const glia_hmt_rag* rag, const glia_hmt_for
   return GLIA_HMT_OK;
 }
 
+// the loop with any classifier (checked by the caller); `who` prefixes the messages
+static int merge_order_bc_with(glia_hmt_ctx* c, glia_hmt_rag* rag, const BcCfg& cfg, const DeviceClassifier& clf, const char* who, uint32_t* h_order,
+                               double* h_sal, double* h_feats, int64_t capacity, int64_t* n_merges, const DeviceMlp* mlp = nullptr) {
+  int rc;
+  *n_merges = 0;
+  if (rag->arr.R == 0 || rag->arr.P == 0) return GLIA_HMT_OK;
+  BcRequest req;
+  req.rows = h_feats != nullptr;
+  req.mlp = mlp; req.exp_variant = c->libm.exp_variant;
+  MergeResult res;
+  if ((rc = greedy_bc(rag->arr, cfg, clf, c->stream, req, &res))) return rc;
+  keep_timing(rag, res);
+  if ((rc = order_to_keys(rag, res, who, false, capacity, h_order, h_sal, n_merges))) return rc;
+  if (h_feats) std::copy(res.rows.begin(), res.rows.end(), h_feats);
+  return GLIA_HMT_OK;
+}
+
 int glia_hmt_merge_order_bc(glia_hmt_ctx* c, glia_hmt_rag* rag, const glia_hmt_forest* forest, uint32_t* h_order,
                             double* h_sal, double* h_feats, int64_t capacity, int64_t* n_merges) {
   if (!c || !rag || !forest || !h_order || !h_sal || !n_merges || rag->ctx != c) {
@@ -381,18 +399,40 @@ int glia_hmt_merge_order_bc(glia_hmt_ctx* c, glia_hmt_rag* rag, const glia_hmt_f
     return GLIA_HMT_ERR_ARG;
   }
   BcCfg cfg;
-  int rc;
-  if ((rc = bc_setup(c, rag, forest, "merge_order_bc", &cfg))) return rc;
-  *n_merges = 0;
-  if (rag->arr.R == 0 || rag->arr.P == 0) return GLIA_HMT_OK;
-  BcRequest req;
-  req.rows = h_feats != nullptr;
-  MergeResult res;
-  if ((rc = greedy_bc(rag->arr, cfg, forest->dc, c->stream, req, &res))) return rc;
-  keep_timing(rag, res);
-  if ((rc = order_to_keys(rag, res, "merge_order_bc", false, capacity, h_order, h_sal, n_merges))) return rc;
-  if (h_feats) std::copy(res.rows.begin(), res.rows.end(), h_feats);
+  if (int rc = bc_setup(c, rag, forest, "merge_order_bc", &cfg)) return rc;
+  return merge_order_bc_with(c, rag, cfg, forest->dc, "merge_order_bc", h_order, h_sal, h_feats, capacity, n_merges);
+}
+
+// The MLP as the loop's classifier (hmt/main_merge_order_bc.cxx:111-139): what the loop cannot hold is refused here, before any
+// HIP call.  The loop scores with the weights the handle already holds on the device.
+static int mlp_classifier(glia_hmt_ctx* c, const glia_hmt_rag* rag, const glia_hmt_mlp* mlp, const char* who, BcCfg* cfg, DeviceClassifier* clf) {
+  auto bad = [&](const std::string& what) { set_error(std::string(who) + ": " + what); return GLIA_HMT_ERR_ARG; };
+  if (!make_bc_cfg(rag, cfg) || rag->only_contour) return bad("the region map must be built with a feature configuration and with region points");
+  if (rag->cfg.use_median_features) { (void)refuse_median_in_loop(rag, who); return GLIA_HMT_ERR_ARG; }
+  const HostMlp& h = mlp->host;
+  if (h.n1 == 0) return bad("the logsig model (no hidden layer) is a batch predictor only (glia_hmt_mlp_predict), not a classifier of the loop");
+  if (h.n1 > kMlpLoopMaxHidden || h.n2 > kMlpLoopMaxHidden)
+    return bad("hidden layers of " + std::to_string(h.n1) + " and " + std::to_string(h.n2) + " units, but the loop takes at most " +
+               std::to_string(kMlpLoopMaxHidden) + " units per hidden layer (glia_hmt_mlp_loop_limits)");
+  if (h.D - 1 != cfg->fdim)
+    return bad("the model is for rows of " + std::to_string(h.D - 1) + " columns, but the region map's feature vector has " + std::to_string(cfg->fdim));
+  if (mlp->device != c->device) return bad("the model was not created on this context's device");
+  memset(clf, 0, sizeof(*clf));
+  clf->kind = 2; clf->n_models = h.n_models;      // (the weights go beside it: BcRequest::mlp)
+  GLIA_HIP_TRY(hipSetDevice(c->device));
   return GLIA_HMT_OK;
+}
+
+int glia_hmt_merge_order_bc_mlp(glia_hmt_ctx* c, glia_hmt_rag* rag, const glia_hmt_mlp* mlp, uint32_t* h_order, double* h_sal, double* h_feats,
+                                int64_t capacity, int64_t* n_merges) {
+  if (!c || !rag || !mlp || !h_order || !h_sal || !n_merges || rag->ctx != c) {
+    set_error("merge_order_bc_mlp: invalid argument");
+    return GLIA_HMT_ERR_ARG;
+  }
+  BcCfg cfg;
+  DeviceClassifier clf;
+  if (int rc = mlp_classifier(c, rag, mlp, "merge_order_bc_mlp", &cfg, &clf)) return rc;
+  return merge_order_bc_with(c, rag, cfg, clf, "merge_order_bc_mlp", h_order, h_sal, h_feats, capacity, n_merges, &mlp->dm);
 }
 
 int glia_hmt_pre_merge(glia_hmt_ctx* c, glia_hmt_rag* rag, const int* size_thresholds, int n_thresholds,
@@ -601,22 +641,15 @@ int glia_hmt_score_initial_edges(glia_hmt_ctx* c, glia_hmt_rag* rag, const glia_
   return GLIA_HMT_OK;
 }
 
-int glia_hmt_score_initial_edges_shard(glia_hmt_ctx* c, glia_hmt_rag* rag, const glia_hmt_forest* forest, int shard, int n_shards,
-                                       double* h_scores, int64_t capacity, int64_t* n_records) {
-  if (!c || !rag || !forest || rag->ctx != c || n_shards < 1 || shard < 0 || shard >= n_shards || !n_records) {
-    set_error("score_initial_edges_shard: invalid argument");
-    return GLIA_HMT_ERR_ARG;
-  }
-  BcCfg cfg;
-  int rc;
-  MedianFeatIn median;
-  if ((rc = bc_setup(c, rag, forest, "score_initial_edges", &cfg, &median))) return rc;
-  // one record per unordered leaf pair; the count is needed before the scores can be copied out
+// one record per unordered leaf pair; the count is needed before the scores can be copied out
+static int score_initial_with(glia_hmt_ctx* c, glia_hmt_rag* rag, const BcCfg& cfg, const DeviceClassifier& clf, const MedianFeatIn* median, int shard,
+                              int n_shards, double* h_scores, int64_t capacity, int64_t* n_records, const DeviceMlp* mlp = nullptr) {
   BcRequest req;
+  req.mlp = mlp; req.exp_variant = c->libm.exp_variant;
   req.init_only = true; req.scores = h_scores != nullptr; req.shard = shard; req.n_shards = n_shards;
-  if (rag->cfg.use_median_features) req.median = &median;
+  req.median = median;
   MergeResult res;
-  if ((rc = greedy_bc(rag->arr, cfg, forest->dc, c->stream, req, &res))) return rc;
+  if (int rc = greedy_bc(rag->arr, cfg, clf, c->stream, req, &res)) return rc;
   keep_timing(rag, res);
   *n_records = res.n;
   if (h_scores) {
@@ -624,6 +657,30 @@ int glia_hmt_score_initial_edges_shard(glia_hmt_ctx* c, glia_hmt_rag* rag, const
     std::copy(res.sal.begin(), res.sal.begin() + res.n, h_scores);
   }
   return GLIA_HMT_OK;
+}
+
+int glia_hmt_score_initial_edges_shard(glia_hmt_ctx* c, glia_hmt_rag* rag, const glia_hmt_forest* forest, int shard, int n_shards,
+                                       double* h_scores, int64_t capacity, int64_t* n_records) {
+  if (!c || !rag || !forest || rag->ctx != c || n_shards < 1 || shard < 0 || shard >= n_shards || !n_records) {
+    set_error("score_initial_edges_shard: invalid argument");
+    return GLIA_HMT_ERR_ARG;
+  }
+  BcCfg cfg;
+  MedianFeatIn median;
+  if (int rc = bc_setup(c, rag, forest, "score_initial_edges", &cfg, &median)) return rc;
+  return score_initial_with(c, rag, cfg, forest->dc, rag->cfg.use_median_features ? &median : nullptr, shard, n_shards, h_scores, capacity, n_records);
+}
+
+int glia_hmt_score_initial_edges_shard_mlp(glia_hmt_ctx* c, glia_hmt_rag* rag, const glia_hmt_mlp* mlp, int shard, int n_shards, double* h_scores,
+                                           int64_t capacity, int64_t* n_records) {
+  if (!c || !rag || !mlp || rag->ctx != c || n_shards < 1 || shard < 0 || shard >= n_shards || !n_records) {
+    set_error("score_initial_edges_shard_mlp: invalid argument");
+    return GLIA_HMT_ERR_ARG;
+  }
+  BcCfg cfg;
+  DeviceClassifier clf;
+  if (int rc = mlp_classifier(c, rag, mlp, "score_initial_edges_shard_mlp", &cfg, &clf)) return rc;
+  return score_initial_with(c, rag, cfg, clf, nullptr, shard, n_shards, h_scores, capacity, n_records, &mlp->dm);
 }
 
 // hmt/main_bc_label_ri.cxx:27-153 (F1 / RI, --optSplit, --opt) and hmt/main_bc_label_vi.cxx:27-128 (VI, majority over truths, --opt):

@@ -6,13 +6,6 @@
 #include "api_types.hpp"
 #include "mlp.hpp"
 
-struct glia_hmt_mlp {
-  int device = -1;               // -1: a host-only handle (created without a context)
-  glia::HostMlp host;
-  glia::DeviceMlp dm;
-  OwnedArrays allocs;
-};
-
 static int upload_doubles(glia_hmt_mlp* m, const std::vector<double>& v, const double** out, hipStream_t stream) {
   double* d = nullptr;
   if (int rc = m->allocs.alloc(&d, v.size())) return rc;
@@ -89,6 +82,11 @@ int glia_hmt_mlp_limits(int n1, int n2, int* stage_max_dim, int* unit_block, int
   if (slots) *slots = kMlpSlots;
   if (max_hidden) *max_hidden = kMlpMaxHidden;
   if (max_dim) *max_dim = kMlpMaxDim;
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_mlp_loop_limits(int* max_hidden) {
+  if (max_hidden) *max_hidden = kMlpLoopMaxHidden;
   return GLIA_HMT_OK;
 }
 

@@ -6,6 +6,7 @@
 #include "glibc_math.hpp"
 #include "greedy_common.hpp"
 #include "hmt_internal.hpp"
+#include "mlp.hpp"
 
 using namespace glia;
 
@@ -24,7 +25,7 @@ struct glia_hmt_ctx {
   glia_hmt_eval_timing evt = {0, 0, 0};   // the last glia_hmt_label_overlap / glia_hmt_eval call
   glia_hmt_forest_train_timing trt = {};  // the last glia_hmt_forest_train call
   int tz = kTZ;                  // tile depth of the accumulation pass; halved when the LDS tables of a pass overflowed a lot
-  LibmSel libm = {kLibmDevice, kLibmDevice, kLibmDevice};   // restatement of the host's log2 / log the kernels use (glibc_math.hpp)
+  LibmSel libm = {kLibmDevice, kLibmDevice, kLibmDevice, kLibmDevice};   // restatement of the host's log2 / log / pow / exp the kernels use (glibc_math.hpp)
 };
 
 struct glia_hmt_rag {
@@ -58,6 +59,13 @@ struct glia_hmt_forest {
   glia::DeviceClassifier dc;
   OwnedArrays allocs;            // the packed trees of every model
   int max_var = 0;
+};
+
+struct glia_hmt_mlp {
+  int device = -1;               // -1: a host-only handle (created without a context)
+  glia::HostMlp host;
+  glia::DeviceMlp dm;
+  OwnedArrays allocs;
 };
 
 struct glia_hmt_forest_model {

@@ -44,9 +44,12 @@ int pack_forest(const HostForest& hf, std::vector<PackedNode>* nodes, std::vecto
 int pack_forest_triples(const HostForest& hf, std::vector<PackedTriple>* lines, std::vector<int>* roots);
 
 // What fBcPred evaluates (hmt/main_merge_order_bc.cxx:127-137): one forest, or three forests behind a
-// ThresholdModelDistributor (type/function.hxx:71-85), or -- diagnostics only -- 1 - x[index].
+// ThresholdModelDistributor (type/function.hxx:71-85), or -- diagnostics only -- 1 - x[index]; or (:111-126) the MLP, whose weights
+// travel beside this struct (BcRequest::mlp: the struct is part of the loop kernels' argument, and the instances that score with
+// forests keep the argument they had).  Only a forest has work for the loop's helper workgroups; the stub and the MLP are scored by
+// the loop's own workgroup.
 struct DeviceClassifier {
-  int kind;              // 0 = forest(s), 1 = feature stub
+  int kind;              // 0 = forest(s), 1 = feature stub, 2 = MLP
   int n_models;          // 1 or 3
   DeviceForest f[3];
   int dim0, dim1;

@@ -11,12 +11,15 @@
 //   log2:  one build only (not an IFUNC in 2.35): the non-FMA path with the {chi, clo} table       -> log2_sse2
 //   log :  IFUNC __log_finite: __log_sse2 / __log_avx (same operations)                            -> log_sse2
 //                              __log_fma (gcc contracted the polynomial, transcribed from the code) -> log_fma
+//   exp :  IFUNC: __exp_sse2 / __exp_fma, the exp_inline of pow plus its special cases (below)         -> exp_sse2, exp_fma
 // glia_hmt_ctx_create probes the host's std::log2 / std::log on a fixed vector and selects the variant that
 // reproduces it bit for bit (api.cpp: probe_host_libm); with no match the device falls back to its own libm and the
 // context reports the feature as unpinned.  Everything here must be compiled with -ffp-contract=off: fused operations
 // are written as __builtin_fma where (and only where) the machine code has them.
 #pragma once
 #include <stdint.h>
+
+#include <cmath>
 
 namespace glia {
 namespace glibc {
@@ -296,12 +299,74 @@ GLIBC_FN double pow_sse2(double x, double y) {
   return pow_exp_fma_tail(ehi, elo, false);
 }
 #undef PA_
+
+// ---- exp(x) (e_exp.c; the IFUNC __exp1 picks __exp_fma or __exp_sse2) -----------------------------------------------------------
+// For 2^-54 <= |x| < 512 exp() IS exp_inline above with elo = 0; what pow never reaches is added here: tiny and huge arguments, and
+// specialcase() for 512 <= |x| < 1024, where 2^(k/128) does not fit a double's exponent -- the scale is taken 2^1009 smaller (k > 0)
+// or 2^1022 larger (k < 0) and the product scaled back; a result in the subnormal range is rounded once (the hi / lo step).
+// The classifier loop's sigmoid (mlp_model.hpp: 1 / (1 + exp(-h))) is what calls it: its probabilities are queue keys, so they must
+// be the host's bits.
+__host__ __device__ inline double exp_any(double x, bool fma) {
+  const uint64_t ix = as_u64(x);
+  const uint32_t top = (uint32_t)(ix >> 52) & 0x7ffu;
+  if (top - 0x3c9u < 0x408u - 0x3c9u) return pow_exp_fma_tail(x, 0.0, fma);
+  if (top < 0x3c9u) return 1.0 + x;
+  if (top >= 0x409u) {
+    if (x != x) return x + x;
+    return (ix >> 63) ? 0.0 : __builtin_inf();
+  }
+  const double invln2n = as_f64(kExpHead[0]), shift = as_f64(kExpHead[1]), nhi = as_f64(kExpHead[2]), nlo = as_f64(kExpHead[3]);
+  double kd = fma ? __builtin_fma(x, invln2n, shift) : invln2n * x + shift;
+  const uint64_t ki = as_u64(kd);
+  kd = kd - shift;
+  double r = fma ? __builtin_fma(kd, nlo, __builtin_fma(kd, nhi, x)) : (x + kd * nhi) + kd * nlo;
+  r = r + 0.0;
+  const uint64_t idx = 2 * (ki & 127);
+  const double tail = as_f64(kExpTab[idx]);
+  uint64_t sbits = kExpTab[idx + 1] + (ki << 45);
+  const double r2 = r * r;
+  double tmp;
+  if (fma) {
+    const double a = __builtin_fma(r, EC_(1), EC_(0));
+    const double b = __builtin_fma(r, EC_(3), EC_(2));
+    tmp = __builtin_fma(b, r2 * r2, __builtin_fma(a, r2, tail + r));
+  } else {
+    tmp = ((tail + r) + r2 * (EC_(0) + r * EC_(1))) + (r2 * r2) * (EC_(2) + r * EC_(3));
+  }
+  if ((ki & 0x80000000ull) == 0) {       // k > 0: overflows to +inf by itself
+    sbits -= 1009ull << 52;
+    const double scale = as_f64(sbits);
+    return 0x1p1009 * (fma ? __builtin_fma(scale, tmp, scale) : scale + scale * tmp);
+  }
+  // k < 0.  The product scale * tmp is used twice, and the FMA build keeps it a product: neither sum is fused in either build
+  // (checked against both on 2 million arguments in [-760, -500])
+  sbits += 1022ull << 52;
+  const double scale = as_f64(sbits);
+  double y = scale + scale * tmp;
+  if (y < 1.0) {
+    double lo = (scale - y) + scale * tmp;
+    const double hi = 1.0 + y;
+    lo = ((1.0 - hi) + y) + lo;
+    y = (hi + lo) - 1.0;
+    if (y == 0.0) y = 0.0;               // (no -0.0)
+  }
+  return 0x1p-1022 * y;
+}
 #undef EC_
+GLIBC_FN double exp_sse2(double x) { return exp_any(x, false); }
+GLIBC_FN double exp_fma(double x) { return exp_any(x, true); }
+// 1 / (1 + exp(-h)) with the host's exp: variant 1 = exp_sse2, 2 = exp_fma; any other value: the libm of whoever runs this
+// (unpinned).  h >= 512: 1 + exp(-h) == 1 exactly.  NaN stays NaN.
+__host__ __device__ inline double sigmoid(double h, int variant) {
+  if (variant != 1 && variant != 2) return 1.0 / (1.0 + ::exp(-h));
+  if (h >= 512.0) return 1.0;
+  return 1.0 / (1.0 + (variant == 2 ? exp_fma(-h) : exp_sse2(-h)));
+}
 
 }  // namespace glibc
 
 // Variant selection (glia_hmt_ctx_create -> kernels): which restatement reproduces the host's libm.
 enum : int { kLibmDevice = 0 /* unpinned: device libm */, kLibmSse2 = 1, kLibmFma = 2 };
-struct LibmSel { int log2_variant, log_variant, pow_variant; };
+struct LibmSel { int log2_variant, log_variant, pow_variant, exp_variant; };
 
 }  // namespace glia

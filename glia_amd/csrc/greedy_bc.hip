@@ -37,6 +37,9 @@
 #include "greedy_common.hpp"
 #include "median_layout.hpp"
 #include "rmap_order.hpp"
+#ifdef GLIA_BC_MLP
+#include "mlp.hpp"
+#endif
 
 namespace glia {
 
@@ -117,6 +120,10 @@ struct BcState {
   unsigned long long forced_n;
   BcCfg cfg;
   DeviceClassifier clf;
+#ifdef GLIA_BC_MLP
+  DeviceMlp mlp;                 // clf.kind == 2 (this instance only: hmt_internal.hpp)
+  int exp_variant;
+#endif
 };
 
 namespace {
@@ -426,12 +433,46 @@ __device__ __forceinline__ int pick_model(const DeviceClassifier& c, const doubl
   if (x[c.dim0] < c.threshold) return 1;
   return 2;
 }
+#ifdef GLIA_BC_MLP
+// ---- the MLP (kind 2; DESIGN 3.13, the arithmetic is mlp_forward.hpp's) ----
+__device__ __forceinline__ MlpWeights mlp_member(const DeviceMlp& m, int i) {
+  MlpWeights w;
+  w.D = m.D; w.n1 = m.n1; w.n2 = m.n2; w.ub1 = m.ub1; w.ub2 = m.ub2;
+  w.w0 = i == 1 ? m.w0[1] : i == 2 ? m.w0[2] : m.w0[0];
+  w.w1 = i == 1 ? m.w1[1] : i == 2 ? m.w1[2] : m.w1[0];
+  w.w2 = i == 1 ? m.w2[1] : i == 2 ? m.w2[2] : m.w2[0];
+  return w;
+}
+// a raw row of D - 1 columns seen as the rescaled, bias-appended vector
+struct MlpRawRow {
+  const double* p; const double* mn; const double* den;
+  int dim, rescale;
+  __device__ __forceinline__ double operator()(int j) const {
+    if (j >= dim) return 1.0;
+    const double v = p[j];
+    return rescale ? mlp_rescale_den(v, mn[j], den[j]) : v;
+  }
+};
+// one thread, one row: the initial edges (the hidden layers fit kMlpLoopMaxHidden: checked by the entry points)
+__device__ __forceinline__ double mlp_serial(const DeviceMlp& m, int exp_variant, const double* x) {
+  const MlpRawRow row{x, m.mn, m.den, m.D - 1, m.rescale};
+  double a1[kMlpLoopMaxHidden], a2[kMlpLoopMaxHidden];
+  const int pick = mlp_pick_of(m.n_models, m.dim0, m.dim1, m.threshold, row);
+  return glibc::sigmoid(mlp_logit(mlp_member(m, pick), row, a1, a2), exp_variant);
+}
+#endif
 __device__ __forceinline__ double classify_serial(const DeviceClassifier& c, const double* x) {
   if (c.kind == 1) return 1.0 - x[c.stub_index];
   const DeviceForest& f = c.f[pick_model(c, x)];
   int votes = 0;
   for (int t = 0; t < f.ntree; ++t) votes += forest_vote(f, t, x);
   return (double)votes / (double)f.ntree;               // ml/rf/rf.hxx:366-369
+}
+__device__ __forceinline__ double classify_edge(const BcState& st, const double* x) {
+#ifdef GLIA_BC_MLP
+  if (st.clf.kind == 2) return mlp_serial(st.mlp, st.exp_variant, x);
+#endif
+  return classify_serial(st.clf, x);
 }
 
 // ---- initialisation kernels ---------------------------------------------------------------------------
@@ -581,7 +622,7 @@ __global__ void bc_init_score(BcState st, uint32_t E0) {
   }
   double x[kMaxFeat];
   edge_features_global(st, first, second, e, ex, x);
-  st.pq.leaf_sal[e] = classify_serial(st.clf, x);
+  st.pq.leaf_sal[e] = classify_edge(st, x);
 }
 
 // The same with the GLIA_USE_MEDIAN_AS_FEATS layout, for the records [e0, e1): the statistics-based vector as above, expanded with
@@ -609,7 +650,7 @@ __global__ void bc_init_score_median(BcState st, uint32_t e0, uint32_t e1, const
   const int k = median_splice(st.cfg, x, y,
                               [&](int blk, int img, int q) { return reg[((slot * 3 + kreg[blk]) * nr + img) * 3 + q]; },
                               [&](int blk, int img, int q) { return bnd[((slot * 4 + (blk < 3 ? kreg[blk] : 3)) * nb + img) * 3 + q]; });
-  st.pq.leaf_sal[e] = k < 0 ? __builtin_nan("") : classify_serial(st.clf, y);      // (k < 0: a layout error; the driver has checked the lengths)
+  st.pq.leaf_sal[e] = k < 0 ? __builtin_nan("") : classify_edge(st, y);      // (k < 0: a layout error; the driver has checked the lengths)
 }
 
 // ---- the loop ----------------------------------------------------------------------------------------------
@@ -669,12 +710,22 @@ struct BcShared {
 };
 // workspace of one scoring round of up to `cap` records: the staged copy of the region being created (per channel) | the records'
 // staged inputs (per record and channel) | feature vectors | precomputed entropies / distances | headers
+// | with an MLP (the loop's own workgroup only): mlp_words doubles per record, the rescaled vector and the activations (mlp_chunk)
+#ifdef GLIA_BC_MLP
+struct ScoreWs { uint32_t cap; int fstride, npre; R2In* r2; RecIn* in; double* feat; double* fx; RecHdr* hdr; double* mlp; uint32_t mlp_words; };
+// doubles of LDS a record takes for an MLP: the rescaled vector with its 1.0, which the second layer's activations overwrite, and the
+// first layer's activations
+__device__ __forceinline__ uint32_t mlp_ws_x(const DeviceMlp& m) { return (uint32_t)(m.D > m.n2 + 1 ? m.D : m.n2 + 1); }
+__device__ __forceinline__ uint32_t mlp_ws_words(const BcState& st) { return st.clf.kind == 2 ? mlp_ws_x(st.mlp) + (uint32_t)st.mlp.n1 + 1u : 0u; }
+#else
 struct ScoreWs { uint32_t cap; int fstride, npre; R2In* r2; RecIn* in; double* feat; double* fx; RecHdr* hdr; };
-__device__ __forceinline__ ScoreWs ws_layout(const BcCfg& c, unsigned char* pool, uint32_t cap_limit = (uint32_t)kChunk, uint32_t* used = nullptr) {
+#endif
+__device__ __forceinline__ ScoreWs ws_layout(const BcCfg& c, unsigned char* pool, uint32_t cap_limit = (uint32_t)kChunk, uint32_t* used = nullptr,
+                                             uint32_t mlp_words = 0) {
   ScoreWs W;
   const uint32_t K = (uint32_t)BC_K(c);
   W.fstride = bc_full_dim(c); W.npre = feat::pre_count(c);
-  const uint32_t per = (uint32_t)sizeof(RecHdr) + (uint32_t)sizeof(RecIn) * K + 8u * (uint32_t)W.fstride + 8u * (uint32_t)W.npre;
+  const uint32_t per = (uint32_t)sizeof(RecHdr) + (uint32_t)sizeof(RecIn) * K + 8u * (uint32_t)W.fstride + 8u * (uint32_t)W.npre + 8u * mlp_words;
   const uint32_t cap = (kWsBytes - (uint32_t)sizeof(R2In) * K) / per;
   W.cap = cap < cap_limit ? cap : cap_limit;
   W.r2 = reinterpret_cast<R2In*>(pool);
@@ -682,7 +733,12 @@ __device__ __forceinline__ ScoreWs ws_layout(const BcCfg& c, unsigned char* pool
   W.feat = reinterpret_cast<double*>(W.in + (size_t)W.cap * K);
   W.fx = W.feat + (size_t)W.cap * W.fstride;
   W.hdr = reinterpret_cast<RecHdr*>(W.fx + (size_t)W.cap * W.npre);
+#ifdef GLIA_BC_MLP
+  W.mlp = reinterpret_cast<double*>(W.hdr + W.cap); W.mlp_words = mlp_words;
+  if (used) *used = ((uint32_t)(reinterpret_cast<unsigned char*>(W.mlp + (size_t)W.cap * mlp_words) - pool) + 15u) & ~15u;
+#else
   if (used) *used = ((uint32_t)(reinterpret_cast<unsigned char*>(W.hdr + W.cap) - pool) + 15u) & ~15u;
+#endif
   return W;
 }
 
@@ -1073,7 +1129,7 @@ __device__ __forceinline__ bool score_chunk(const BcState& st, BcShared& s, cons
   if ((uint32_t)tid < n && W.hdr[tid].on) {
     double* x = &W.feat[tid * W.fstride];
     feat::simple_selection(cf, x);
-    W.hdr[tid].model = st.clf.kind == 1 ? 0 : pick_model(st.clf, x);
+    W.hdr[tid].model = st.clf.kind != 0 ? 0 : pick_model(st.clf, x);      // (an MLP ensemble picks on the rescaled vector: mlp_chunk)
   }
   __syncthreads();
   SPH(5);
@@ -1097,6 +1153,59 @@ __device__ __forceinline__ void forest_chunk(const BcState& st, BcShared& s, con
   }
   __syncthreads();
 }
+
+#ifdef GLIA_BC_MLP
+// The MLP's logits for the n vectors of a scoring round (every thread calls; ends with a barrier): record j's logit is left in
+// W.mlp[j * W.mlp_words], its member in W.hdr[j].model.  The raw vectors in W.feat are read, never written.  A record's block of
+// W.mlp: x [max(D, n2 + 1)] the rescaled vector with its 1.0, later the second layer's activations | a1 [n1 + 1].  Four steps, a
+// barrier behind each -- every LDS word below is written in one step and read in a later one, by other waves:
+//   M0  thread per (record, column): x                        M1  thread per record: the member, from x
+//   M2  thread per (record, unit of layer 1): a1, from x      M3  thread per (record, unit of layer 2): a2 over x, from a1
+// and after the last barrier the record's own thread sums the logit from a2 and overwrites x[0] with it (read by itself alone).
+// A dot product is one thread's chain (mlp_unit); the weights are the model handle's blocked arrays, read through the caches.
+__device__ __forceinline__ void mlp_chunk(const BcState& st, const ScoreWs& W, uint32_t n) {
+  const int tid = threadIdx.x;
+  const DeviceMlp& m = st.mlp;
+  const int D = m.D, dim = D - 1, n1 = m.n1, n2 = m.n2;
+  const uint32_t xw = mlp_ws_x(m), mw = W.mlp_words;
+  for (uint32_t i = tid; i < n * (uint32_t)D; i += kBcThreads) {                                  // M0
+    const uint32_t j = i / (uint32_t)D;
+    const int c = (int)(i - j * (uint32_t)D);
+    if (!W.hdr[j].on) continue;
+    const MlpRawRow row{&W.feat[j * W.fstride], m.mn, m.den, dim, m.rescale};
+    W.mlp[j * mw + c] = row(c);
+  }
+  __syncthreads();
+  if ((uint32_t)tid < n && W.hdr[tid].on)                                                          // M1
+    W.hdr[tid].model = mlp_pick_of(m.n_models, m.dim0, m.dim1, m.threshold, MlpBiased{&W.mlp[tid * mw], D});
+  __syncthreads();
+  for (uint32_t i = tid; i < n * (uint32_t)(n1 + 1); i += kBcThreads) {                           // M2
+    const uint32_t j = i / (uint32_t)(n1 + 1);
+    const int k = (int)(i - j * (uint32_t)(n1 + 1));
+    if (!W.hdr[j].on) continue;
+    const MlpWeights w = mlp_member(m, W.hdr[j].model);
+    double* a1 = &W.mlp[j * mw + xw];
+    a1[k] = k == n1 ? 1.0 : mlp_relu(mlp_unit(w.w0, D, w.ub1, k, MlpBiased{&W.mlp[j * mw], D}));
+  }
+  __syncthreads();
+  for (uint32_t i = tid; i < n * (uint32_t)(n2 + 1); i += kBcThreads) {                           // M3
+    const uint32_t j = i / (uint32_t)(n2 + 1);
+    const int k = (int)(i - j * (uint32_t)(n2 + 1));
+    if (!W.hdr[j].on) continue;
+    const MlpWeights w = mlp_member(m, W.hdr[j].model);
+    double* a2 = &W.mlp[j * mw];
+    a2[k] = k == n2 ? 1.0 : mlp_relu(mlp_unit(w.w1, n1 + 1, w.ub2, k, MlpBiased{&W.mlp[j * mw + xw], n1 + 1}));
+  }
+  __syncthreads();
+  if ((uint32_t)tid < n && W.hdr[tid].on) {
+    const MlpWeights w = mlp_member(m, W.hdr[tid].model);
+    double* a2 = &W.mlp[tid * mw];
+    const double h3 = mlp_unit(w.w2, n2 + 1, 1, 0, MlpBiased{a2, n2 + 1});
+    a2[0] = h3;
+  }
+  __syncthreads();
+}
+#endif
 
 // Helper workgroups: wait for a job, score the records h, h + H, ... of it from start to finish (staging, extremes, shared sets,
 // entropies, vector, forest), answer with one tagged 64-bit word per record.  The job descriptor is one of kJobBufs slots; a
@@ -1267,7 +1376,11 @@ __global__ __launch_bounds__(kBcThreads) void greedy_bc_kernel(const BcState st)
   uint32_t status = ST_RUN;
   const int fdim = st.cfg.fdim;
   const int K = BC_K(st.cfg);
+#ifdef GLIA_BC_MLP
+  const ScoreWs W = ws_layout(st.cfg, s.pool, (uint32_t)kChunk, nullptr, mlp_ws_words(st));
+#else
   const ScoreWs W = ws_layout(st.cfg, s.pool);
+#endif
   if (tid == 0) { s.pq.wln[0] = s.pq.wln[1] = 0; s.pq.ovf = 0; s.pq.spill = 0; s.lost = 0; s.pre_e = kNone; s.nlog = (uint32_t)feat::log_slots(st.cfg, s.logpos); s.cand.sal = -__builtin_inf(); s.cand.seq = 0; s.cand.arg = 0; }
   bool deferred = false;         // inserts of the last contraction are waiting in the worklist (uniform)
   for (int i = tid; i < glibc::kLog2TabWords; i += blockDim.x) s.log2tab[i] = i < 18 ? glibc::kLog2Head[i] : i < 18 + 128 ? glibc::kLog2Tab[i - 18] : glibc::kLog2Tab2[i - 18 - 128];
@@ -1732,11 +1845,20 @@ __global__ __launch_bounds__(kBcThreads) void greedy_bc_kernel(const BcState st)
         (void)score_chunk<false>(st, s, W, cn, newcount, []() { return true; });
         PH(4);
         if (st.clf.kind == 0) forest_chunk(st, s, W, cn);
+#ifdef GLIA_BC_MLP
+        else if (st.clf.kind == 2) mlp_chunk(st, W, cn);
+#endif
         PH(5);
         if ((uint32_t)tid < cn && W.hdr[tid].model >= 0) {
           const uint32_t rec = W.hdr[tid].rec;
+#ifdef GLIA_BC_MLP
+          const double sal = st.clf.kind == 1   ? 1.0 - W.feat[tid * W.fstride + st.clf.stub_index]
+                             : st.clf.kind == 2 ? glibc::sigmoid(W.mlp[tid * W.mlp_words], st.exp_variant)
+                                                : (double)s.votes[tid] / (double)st.clf.f[W.hdr[tid].model].ntree;
+#else
           const double sal = st.clf.kind == 1 ? 1.0 - W.feat[tid * W.fstride + st.clf.stub_index]
                                               : (double)s.votes[tid] / (double)st.clf.f[W.hdr[tid].model].ntree;
+#endif
           const uint32_t cat = st.e_posv[rec] >> 30;
           st.pq.leaf_sal[rec] = sal;
           st.pq.leaf_seq[rec] = ((k + 1ull) << 32) | ((unsigned long long)cat << 30) | W.hdr[tid].rs;
@@ -1804,6 +1926,14 @@ GLIA_DECLARE_GREEDY_BC(GLIA_BC_ENTRY) {
   BcState st;
   memset(&st, 0, sizeof(st));
   st.R0 = R; st.P = P; st.cfg = cfg; st.clf = clf;
+#ifdef GLIA_BC_MLP
+  if (clf.kind == 2) {
+    if (!req.mlp) { set_error("merge_order_bc: an MLP classifier without its model (internal error)"); return GLIA_HMT_ERR_INTERNAL; }
+    st.mlp = *req.mlp; st.exp_variant = req.exp_variant;
+  }
+#else
+  if (clf.kind == 2) { set_error("merge_order_bc: this instance of the loop holds no MLP scorer (internal error)"); return GLIA_HMT_ERR_INTERNAL; }
+#endif
   st.shard = (uint32_t)req.shard; st.n_shards = (uint32_t)(req.n_shards > 0 ? req.n_shards : 1);
 
   // reference region-map iteration order (rmap_order.cpp): leaves sorted by first voxel on the device, the hashtable replay on the host

@@ -181,6 +181,7 @@ struct PbRequest {
 int greedy_mean(const RagArrays& rag, hipStream_t stream, const PbRequest& req, MergeResult* out);
 struct BcCfg;
 struct DeviceClassifier;
+struct DeviceMlp;
 // the classifier loop
 struct BcRequest {
   const uint32_t* forced = nullptr;             // a given order (bc_feat): dense region pairs [n_forced][2]; the classifier is not run
@@ -190,11 +191,15 @@ struct BcRequest {
   bool scores = false;                          // init_only: MergeResult::sal = the records' scores
   const MedianFeatIn* median = nullptr;         // init_only: score the median layout (GLIA_USE_MEDIAN_AS_FEATS) -- the images and the volume of the map
   int shard = 0, n_shards = 1;
+  const DeviceMlp* mlp = nullptr;               // DeviceClassifier::kind == 2: the model (its weights on the device) ...
+  int exp_variant = 0;                          // ... and the restatement of the host's exp its sigmoid uses (glibc_math.hpp; 0 = the device's exp)
 };
 // greedy_bc.hip is compiled five times: with the libm restatements of the feature code (glibc_math.hpp) selected at run time
 // (any combination, incl. "unpinned"), and with the two combinations real hosts have -- glibc's FMA build and its non-FMA
 // build -- fixed at compile time (a run-time choice between three logarithms at every call site costs the classifier loop
-// 5 %).  greedy_bc() picks the instance from cfg.libm_* (api_loops.cpp).
+// 5 %).  greedy_bc() picks the instance from cfg.libm_* (api_loops.cpp).  A sixth instance, greedy_bc_mlp (GLIA_BC_MLP, libm at run
+// time), is the only one that holds the MLP scorer (DeviceClassifier::kind == 2): compiled into the other five it cost the forest's
+// loop a third of its rate (more spilled registers, a larger kernel argument), so they are built without it and refuse kind 2.
 #define GLIA_DECLARE_GREEDY_BC(name) \
   int name(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier& clf, hipStream_t stream, const BcRequest& req, MergeResult* out)
 GLIA_DECLARE_GREEDY_BC(greedy_bc_generic);
@@ -202,6 +207,7 @@ GLIA_DECLARE_GREEDY_BC(greedy_bc_fma);
 GLIA_DECLARE_GREEDY_BC(greedy_bc_sse2);
 GLIA_DECLARE_GREEDY_BC(greedy_bc_fma_common);      // + GLIA_BC_COMMON (bc_features.hpp): one image on the region and boundary lists, no --logs / --simpf / histogram columns
 GLIA_DECLARE_GREEDY_BC(greedy_bc_sse2_common);
+GLIA_DECLARE_GREEDY_BC(greedy_bc_mlp);
 GLIA_DECLARE_GREEDY_BC(greedy_bc);
 // bc_feat for a given order as a batch computation over the known merge tree (bc_feat_batch.hip): rows [M][cfg.fdim] in the layout
 // greedy_bc writes them.  forced: dense region pairs of the merges, validated by the caller.

@@ -1,7 +1,8 @@
 // glia_amd/csrc/mlp_model.hpp -- the second boundary classifier on the host: alg::MLP2v / alg::EnsembleMLP2v (alg/nn.hxx:14-254: two
 // ReLU hidden layers, a sigmoid output) and alg::Logsig (alg/function.hxx:33-34), as sshmt/main_pred_mlp.cxx and
 // sshmt/main_pred_logsig.cxx apply them to feature rows.  This header holds the parser of the model and min/max files, the shape
-// arithmetic, the layout the kernel takes (mlp_predict.hip) and a plain forward pass -- THE definition of the arithmetic:
+// arithmetic, the layout the kernel takes (mlp_predict.hip) and a plain forward pass over rows, written with mlp_forward.hpp -- THE
+// definition of the arithmetic, which the classifier loop shares:
 // every sum starts at 0.0 and takes its terms in ascending index order, a multiply and an add rounded separately (no FMA).  Host-only
 // and header-only: the library uses it (api_mlp.cpp, mlp_predict.hip) and cli/mlp_model_check.cpp builds it alone.
 #pragma once
@@ -13,11 +14,14 @@
 #include <string>
 #include <vector>
 
+#include "mlp_forward.hpp"
+
 namespace glia {
 
 constexpr double kMlpFeps = 2.22e-16;      // FEPS of stats::rescale (util/stats.hxx:265-277, glia_base.hxx)
 constexpr int kMlpMaxHidden = 256;         // N1, N2 <= this
 constexpr int kMlpMaxDim = 65535;          // columns of a row <= this
+constexpr int kMlpLoopMaxHidden = 32;      // N1, N2 <= this inside the classifier loop (greedy_bc.hip: per-thread arrays of the initial-edge kernel)
 constexpr int kMlpSlots = 4;               // waves of a workgroup: they share a tile of rows and split a layer's units
 constexpr int kMlpUnitBlock = 16;          // hidden units a thread accumulates in registers at a time, at most
 constexpr int kMlpLdsBytes = 64 * 1024;    // tile budget of a workgroup
@@ -139,44 +143,33 @@ inline std::string mlp_check(const HostMlp& m) {
   return std::string();
 }
 
-inline double mlp_rescale(double x, double mn, double mx) { return ((2.0 * (x - mn)) / ((mx - mn) + kMlpFeps)) + (-1.0); }
+inline double mlp_rescale(double x, double mn, double mx) { return mlp_rescale_den(x, mn, (mx - mn) + kMlpFeps); }
+struct MlpRowPtr {         // a vector that is all there
+  const double* p;
+  double operator()(int j) const { return p[j]; }
+};
 inline int mlp_pick(const HostMlp& m, const double* x) {     // x: rescaled, bias appended
-  if (m.n_models == 1) return 0;
-  return x[m.dim1] < m.threshold ? 0 : (x[m.dim0] < m.threshold ? 1 : 2);
+  return mlp_pick_of(m.n_models, m.dim0, m.dim1, m.threshold, MlpRowPtr{x});
 }
-inline double mlp_relu(double h) { return h > 0.0 ? h : 0.0; }
 inline double mlp_sigmoid(double h3) { return 1.0 / (1.0 + std::exp(-h3)); }
+// model i as the forward pass takes it: the file's matrices, column-major
+inline MlpWeights mlp_host_weights(const HostMlp& m, int i) {
+  const double* w = m.w[i].data();
+  MlpWeights v;
+  v.D = m.D; v.n1 = m.n1; v.n2 = m.n2; v.ub1 = 1; v.ub2 = 1;
+  v.w0 = w; v.w1 = w + (size_t)m.D * m.n1; v.w2 = m.n1 ? v.w1 + (size_t)(m.n1 + 1) * m.n2 : w;
+  return v;
+}
 
-// The forward pass: rows [n_rows][D - 1] at a stride of row_stride doubles; pred and logit may each be NULL.
+// The forward pass (mlp_forward.hpp): rows [n_rows][D - 1] at a stride of row_stride doubles; pred and logit may each be NULL.
 inline void mlp_forward(const HostMlp& m, const double* rows, int64_t n_rows, int64_t row_stride, double* pred, double* logit) {
-  const int D = m.D, dim = D - 1, N1 = m.n1, N2 = m.n2;
-  std::vector<double> x((size_t)D), a1((size_t)N1 + 1), a2((size_t)N2 + 1);
+  const int D = m.D, dim = D - 1;
+  std::vector<double> x((size_t)D), a1((size_t)m.n1 + 1), a2((size_t)m.n2 + 1);
   for (int64_t r = 0; r < n_rows; ++r) {
     const double* src = rows + r * row_stride;
     for (int j = 0; j < dim; ++j) x[j] = m.rescale ? mlp_rescale(src[j], m.mn[j], m.mx[j]) : src[j];
     x[dim] = 1.0;
-    const double* w = m.w[mlp_pick(m, x.data())].data();
-    double h3 = 0.0;
-    if (N1 == 0) {
-      for (int j = 0; j < D; ++j) { const double t = x[j] * w[j]; h3 = h3 + t; }
-    } else {
-      const double* w0 = w;
-      const double* w1 = w0 + (size_t)D * N1;
-      const double* w2 = w1 + (size_t)(N1 + 1) * N2;
-      for (int k = 0; k < N1; ++k) {
-        double h = 0.0;
-        for (int j = 0; j < D; ++j) { const double t = x[j] * w0[j + (size_t)D * k]; h = h + t; }
-        a1[k] = mlp_relu(h);
-      }
-      a1[N1] = 1.0;
-      for (int k = 0; k < N2; ++k) {
-        double h = 0.0;
-        for (int j = 0; j <= N1; ++j) { const double t = a1[j] * w1[j + (size_t)(N1 + 1) * k]; h = h + t; }
-        a2[k] = mlp_relu(h);
-      }
-      a2[N2] = 1.0;
-      for (int j = 0; j <= N2; ++j) { const double t = a2[j] * w2[j]; h3 = h3 + t; }
-    }
+    const double h3 = mlp_logit(mlp_host_weights(m, mlp_pick(m, x.data())), MlpRowPtr{x.data()}, a1.data(), a2.data());
     if (logit) logit[r] = h3;
     if (pred) pred[r] = mlp_sigmoid(h3);
   }

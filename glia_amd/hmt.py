@@ -224,8 +224,15 @@ class Context:
         _check(lib().glia_hmt_ctx_libm_pow(self.h, C.byref(a)))
         return a.value
 
+    def libm_exp(self):
+        """variant of std::exp the classifier loop's MLP sigmoid uses (same codes as libm()); not part of libm_pinned()"""
+        a = C.c_int(0)
+        _check(lib().glia_hmt_ctx_libm_exp(self.h, C.byref(a)))
+        return a.value
+
     def libm_eval(self, function, variant, x):
-        """Device restatement of the host libm over a CUDA f64 tensor: function 0 = log2, 1 = log, 2 = pow(x, 1.5)."""
+        """Device restatement of the host libm over a CUDA f64 tensor: function 0 = log2, 1 = log, 2 = pow(x, 1.5), 3 = exp,
+        4 = the sigmoid 1 / (1 + exp(-x))."""
         import torch
         out = torch.empty_like(x)
         _check(lib().glia_hmt_libm_eval(self.h, C.c_int(function), C.c_int(variant), C.c_void_p(x.data_ptr()),
@@ -586,6 +593,13 @@ def mlp_limits(n1=10, n2=10):
     v = [C.c_int() for _ in range(5)]
     _check(lib().glia_hmt_mlp_limits(C.c_int(n1), C.c_int(n2), *[C.byref(x) for x in v]))
     return dict(zip(("stage_max_dim", "unit_block", "slots", "max_hidden", "max_dim"), (x.value for x in v)))
+
+
+def mlp_loop_limits():
+    """glia_hmt_mlp_loop_limits: the most units per hidden layer of an MLP that RegionMap.merge_order_bc takes.  Host-only."""
+    v = C.c_int()
+    _check(lib().glia_hmt_mlp_loop_limits(C.byref(v)))
+    return {"max_hidden": v.value}
 
 
 def mlp_tile_rows(dim, n1, n2):
@@ -1042,15 +1056,16 @@ class RegionMap:
         return lib().glia_hmt_feat_dim(self.h)
 
     def merge_order_bc(self, classifier, want_feats=False):
-        """hmt/main_merge_order_bc.cxx (--bct 1).  Returns (order, saliency[, feats])."""
+        """hmt/main_merge_order_bc.cxx: --bct 1 with a RandomForest, --bct 2 with an MLP (its probability is the saliency; hidden
+        layers up to mlp_loop_limits()).  Returns (order, saliency[, feats]); feats are the raw rows."""
         cap = max(self.num_regions, 1)
         order = np.empty((cap, 3), np.uint32)
         sal = np.empty(cap, np.float64)
         d = self.feat_dim()
         feats = np.empty((cap, d), np.float64) if want_feats else None
         n = C.c_int64(0)
-        _check(lib().glia_hmt_merge_order_bc(self.ctx.h, self.h, classifier.h, _np(order), _np(sal), _np(feats),
-                                             C.c_int64(cap), C.byref(n)))
+        fn = lib().glia_hmt_merge_order_bc_mlp if isinstance(classifier, MLP) else lib().glia_hmt_merge_order_bc
+        _check(fn(self.ctx.h, self.h, classifier.h, _np(order), _np(sal), _np(feats), C.c_int64(cap), C.byref(n)))
         if want_feats:
             return order[:n.value].copy(), sal[:n.value].copy(), feats[:n.value].copy()
         return order[:n.value].copy(), sal[:n.value].copy()
@@ -1132,12 +1147,13 @@ class RegionMap:
 
     def score_initial_edges_shard(self, classifier, shard, n_shards):
         """scores of the initial records e with e % n_shards == shard (-inf elsewhere); max over shards = all scores.  Works with
-        use_median_features as well (whole-volume maps; merge_order_bc still refuses that layout)."""
+        use_median_features as well (whole-volume maps; merge_order_bc still refuses that layout) -- with a forest; an MLP takes the
+        statistics layout only."""
         cap = max(self.num_pairs, 1)
         out = np.empty(cap, np.float64)
         n = C.c_int64(0)
-        _check(lib().glia_hmt_score_initial_edges_shard(self.ctx.h, self.h, classifier.h, C.c_int(shard), C.c_int(n_shards), _np(out),
-                                                        C.c_int64(cap), C.byref(n)))
+        fn = lib().glia_hmt_score_initial_edges_shard_mlp if isinstance(classifier, MLP) else lib().glia_hmt_score_initial_edges_shard
+        _check(fn(self.ctx.h, self.h, classifier.h, C.c_int(shard), C.c_int(n_shards), _np(out), C.c_int64(cap), C.byref(n)))
         return out[:n.value].copy()
 
     def boundary_confidence(self, trees):

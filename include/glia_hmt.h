@@ -75,14 +75,20 @@ int glia_hmt_ctx_sync(glia_hmt_ctx* ctx);
  * by probing the host's libm when it is created, the one that reproduces it bit for bit: 1 = non-FMA build ("sse2"),
  * 2 = FMA build, 0 = no restatement matches this host (device libm, within 1 ulp: entropy features then UNPINNED).
  * glia_hmt_host_libm_probe runs the same probe without a GPU; glia_hmt_libm_eval evaluates function (0 = log2, 1 = log,
- * 2 = the pow(perim, 1.5) of type/feat.hxx:78-79) in the given variant over a device array (parity tests). */
+ * 2 = the pow(perim, 1.5) of type/feat.hxx:78-79, 3 = exp, 4 = the sigmoid 1 / (1 + exp(-h)) built on it) in the given variant over
+ * a device array (parity tests).
+ * std::exp is probed too (glia_hmt_ctx_libm_exp): the MLP of the classifier loop (glia_hmt_merge_order_bc_mlp) turns its logit into
+ * the queue key with it, as alg/nn.hxx does on the host.  0 there: the loop uses the device's exp and its saliencies are within a
+ * few ulps of the host's, unpinned.  It is not part of glia_hmt_ctx_libm_status, which speaks of the feature columns. */
 int glia_hmt_ctx_libm(const glia_hmt_ctx* ctx, int* log2_variant, int* log_variant);
 int glia_hmt_ctx_libm_pow(const glia_hmt_ctx* ctx, int* pow_variant);        /* same, for std::pow(perim, 1.5) (type/feat.hxx:78-79) */
+int glia_hmt_ctx_libm_exp(const glia_hmt_ctx* ctx, int* exp_variant);        /* same, for std::exp (the MLP's sigmoid) */
 /* 1 = all three host functions are reproduced bit for bit, 0 = at least one is not (glia_hmt_ctx_create then also leaves a
  * "warning: ..." text in glia_hmt_last_error(); the tools print it to stderr), < 0 = error */
 int glia_hmt_ctx_libm_status(const glia_hmt_ctx* ctx);
 int glia_hmt_host_libm_probe(int* log2_variant, int* log_variant);
 int glia_hmt_host_libm_probe_pow(int* pow_variant);
+int glia_hmt_host_libm_probe_exp(int* exp_variant);
 int glia_hmt_host_libm_eval(int function, int variant, const double* h_in, double* h_out, int64_t n);  /* host code of the same restatement, no GPU */
 int glia_hmt_libm_eval(glia_hmt_ctx* ctx, int function, int variant, const double* d_in, double* d_out, int64_t n);
 /* Which region is "region 0" of an initial edge, everything else being equal, follows the iteration order of the reference's
@@ -332,6 +338,8 @@ int glia_hmt_mlp_predict(glia_hmt_ctx* ctx, const glia_hmt_mlp* mlp, const doubl
  * (64, 32, 16 or 8; below 64 the upper lanes of every wave idle) and whether rows of dim columns are staged. */
 int glia_hmt_mlp_limits(int n1, int n2, int* stage_max_dim, int* unit_block, int* slots, int* max_hidden, int* max_dim);
 int glia_hmt_mlp_predict_tile_rows(int dim, int n1, int n2, int* staged);
+/* Host-only: the most units per hidden layer a model may have inside the classifier loop (glia_hmt_merge_order_bc_mlp). */
+int glia_hmt_mlp_loop_limits(int* max_hidden);
 
 /* ---- training the boundary classifier ---------------------------------------------------------------
  * Replaces train_rf (ml/rf/main_train_rf.cxx:18-70): rf_old::train around classRF (ml/rf/ml_rf_train.cxx:234, whose sources the
@@ -396,6 +404,16 @@ int glia_hmt_feat_dim(const glia_hmt_rag* rag);
  * merged edge was scored with (the -b output, :148-157). */
 int glia_hmt_merge_order_bc(glia_hmt_ctx* ctx, glia_hmt_rag* rag, const glia_hmt_forest* forest, uint32_t* h_order,
                             double* h_saliency, double* h_feats, int64_t capacity, int64_t* n_merges);
+/* The same loop with the second classifier of hmt/main_merge_order_bc.cxx:111-139 (bcType 2): alg::MLP2v, or three of them behind
+ * the ThresholdModelDistributor, which reads the RESCALED, bias-appended vector.  The saliency of an edge is the probability
+ * 1 / (1 + exp(-logit)) with the arithmetic of glia_hmt_mlp_predict_host and the host's exp (glia_hmt_ctx_libm_exp):
+ * a saturated model gives many edges exactly 1.0 and the tie rule decides among them, as in the reference.  h_feats receives the raw
+ * rows (not rescaled).  The loop's own workgroup scores; helper workgroups serve forests only.
+ * GLIA_HMT_ERR_ARG with a message, before any kernel: a model with more than glia_hmt_mlp_loop_limits units in a hidden layer, the
+ * logsig model (0 / 0), glia_hmt_mlp_dim != glia_hmt_feat_dim of the rag, a model not created on this context's device.  The median
+ * layout is refused as for the forest. */
+int glia_hmt_merge_order_bc_mlp(glia_hmt_ctx* ctx, glia_hmt_rag* rag, const glia_hmt_mlp* mlp, uint32_t* h_order,
+                                double* h_saliency, double* h_feats, int64_t capacity, int64_t* n_merges);
 
 /* Replaces the merge engine of pre_merge (gadget/main_pre_merge.cxx:20-76): pb-mean linkage with updateRegion = true
  * and the size condition -- an edge may merge only if its smaller region has fewer than size_thresholds[0] voxels, or
@@ -564,6 +582,9 @@ int glia_hmt_score_initial_edges(glia_hmt_ctx* ctx, glia_hmt_rag* rag, const gli
  * element-wise maximum over the shards is the full result.  h_scores may be NULL to query *n_records (<= directed pairs). */
 int glia_hmt_score_initial_edges_shard(glia_hmt_ctx* ctx, glia_hmt_rag* rag, const glia_hmt_forest* forest, int shard,
                                        int n_shards, double* h_scores, int64_t capacity, int64_t* n_records);
+/* The same with the MLP (hmt/main_merge_order_bc.cxx:111-139); the limits of glia_hmt_merge_order_bc_mlp apply. */
+int glia_hmt_score_initial_edges_shard_mlp(glia_hmt_ctx* ctx, glia_hmt_rag* rag, const glia_hmt_mlp* mlp, int shard,
+                                           int n_shards, double* h_scores, int64_t capacity, int64_t* n_records);
 
 /* Phase timings of the last merge_order_* call on this rag (ms): edge-table build, init, greedy loop. */
 int glia_hmt_last_merge_timing(const glia_hmt_rag* rag, double* ms_table, double* ms_init, double* ms_loop,
