@@ -1,0 +1,199 @@
+// glia_amd/csrc/api_mlp_train.cpp -- C ABI: training the MLP / logsig classifier (mlp_backward.hpp: the definition and the trainer;
+// mlp_train.hip: the device evaluator).
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+
+#include "api_types.hpp"
+#include "mlp_backward.hpp"
+
+struct glia_hmt_mlp_model {
+  glia::MlpTrainResult r;
+};
+
+namespace {
+
+struct DeviceEval : MlpTrainEval {
+  MlpTrainDevice* st = nullptr;
+  ~DeviceEval() override { mlp_train_device_free(st); }
+  int eval(const double* w, double* L, double* grad) override { return mlp_train_device_eval(st, w, L, grad); }
+};
+
+// everything both entry points check and prepare; *rc_out != 0: refused
+struct Prepared {
+  glia_hmt_mlp_train_opts o;
+  int D = 0;
+  std::vector<double> X, t, w;
+};
+
+int prepare(const char* who, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_mlp_train_opts* opts,
+            const double* h_min, const double* h_max, const double* h_init, glia_hmt_mlp_model** out, Prepared* P) {
+  const std::string me = std::string(who) + ": ";
+  if (!out || n_rows < 0 || dim < 1 || (n_rows > 0 && (!h_rows || !h_labels))) { set_error(me + "invalid argument"); return GLIA_HMT_ERR_ARG; }
+  *out = nullptr;
+  if ((h_min == nullptr) != (h_max == nullptr)) { set_error(me + "minima and maxima come together"); return GLIA_HMT_ERR_ARG; }
+  if (opts) P->o = *opts; else mlp_train_opts_default(&P->o);
+  const glia_hmt_mlp_train_opts& o = P->o;
+  std::string bad = mlp_train_bad_opts(o);
+  if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_ARG; }
+  bad = mlp_train_unsupported(o);
+  if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_UNSUPPORTED; }
+  if (dim > kMlpTrainMaxDim) { set_error("mlp_train: rows of more than " + std::to_string(kMlpTrainMaxDim) + " columns are not supported"); return GLIA_HMT_ERR_UNSUPPORTED; }
+  for (int64_t i = 0; i < n_rows * dim; ++i)
+    if (!std::isfinite(h_rows[i])) { set_error("mlp_train: row " + std::to_string(i / dim) + " holds a value that is not finite"); return GLIA_HMT_ERR_ARG; }
+  for (int j = 0; h_min && j < dim; ++j)
+    if (!std::isfinite(h_min[j]) || !std::isfinite(h_max[j])) { set_error("mlp_train: the min/max table holds a value that is not finite"); return GLIA_HMT_ERR_ARG; }
+  P->D = dim + 1;
+  const long long d = mlp_train_n_weights(P->D, o.n1, o.n2);
+  P->w.resize((size_t)d);
+  if (h_init) {
+    for (long long p = 0; p < d; ++p) {
+      if (!std::isfinite(h_init[p])) { set_error("mlp_train: initial weight " + std::to_string(p) + " is not finite"); return GLIA_HMT_ERR_ARG; }
+      P->w[p] = h_init[p];
+    }
+  } else if (o.n1 > 0) {
+    for (long long p = 0; p < d; ++p) P->w[p] = mlp_init_weight(o.seed, (uint64_t)p);
+  }
+  mlp_train_prepare(h_rows, n_rows, dim, h_labels, h_min, h_max, o.pos_target, o.neg_target, &P->X, &P->t);
+  if (P->t.empty()) { set_error("mlp_train: no row is labelled +1 or -1"); return GLIA_HMT_ERR_ARG; }
+  for (double v : P->X)
+    if (!std::isfinite(v)) { set_error("mlp_train: a rescaled row holds a value that is not finite"); return GLIA_HMT_ERR_ARG; }
+  return GLIA_HMT_OK;
+}
+
+int finish(Prepared& P, MlpTrainEval& ev, const double* h_min, const double* h_max, glia_hmt_mlp_model** out) {
+  glia_hmt_mlp_model* m = new glia_hmt_mlp_model;
+  MlpTrainResult& R = m->r;
+  R.D = P.D; R.n1 = P.o.n1; R.n2 = P.o.n2; R.n_used = (int64_t)P.t.size();
+  if (h_min) { R.mn.assign(h_min, h_min + (P.D - 1)); R.mx.assign(h_max, h_max + (P.D - 1)); }
+  if (int rc = mlp_train_run(P.o, R.n_used, P.w, ev, &R)) { delete m; return rc; }
+  if (R.round_w.empty()) R.round_w.push_back(P.w);
+  *out = m;
+  return GLIA_HMT_OK;
+}
+
+int pick_round(const glia_hmt_mlp_model* m, int round, const char* who) {
+  const int n = (int)m->r.round_w.size();
+  if (round == -1) round = n - 1;
+  if (round < 0 || round >= n) { set_error(std::string(who) + ": the model holds rounds 0 to " + std::to_string(n - 1)); return -1; }
+  return round;
+}
+
+}  // namespace
+
+extern "C" {
+
+void glia_hmt_mlp_train_opts_default(glia_hmt_mlp_train_opts* opts) {
+  if (opts) mlp_train_opts_default(opts);
+}
+
+int glia_hmt_mlp_train_host(const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_mlp_train_opts* opts,
+                            const double* h_min, const double* h_max, const double* h_init, glia_hmt_mlp_model** out) {
+  Prepared P;
+  if (int rc = prepare("mlp_train_host", h_rows, n_rows, dim, h_labels, opts, h_min, h_max, h_init, out, &P)) return rc;
+  MlpTrainHostEval ev;
+  ev.D = P.D; ev.n1 = P.o.n1; ev.n2 = P.o.n2; ev.X = P.X.data(); ev.t = P.t.data(); ev.n = (int64_t)P.t.size();
+  return finish(P, ev, h_min, h_max, out);
+}
+
+int glia_hmt_mlp_train(glia_hmt_ctx* c, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels,
+                       const glia_hmt_mlp_train_opts* opts, const double* h_min, const double* h_max, const double* h_init,
+                       glia_hmt_mlp_model** out) {
+  if (!c) return glia_hmt_mlp_train_host(h_rows, n_rows, dim, h_labels, opts, h_min, h_max, h_init, out);
+  const auto t0 = std::chrono::steady_clock::now();
+  Prepared P;
+  if (int rc = prepare("mlp_train", h_rows, n_rows, dim, h_labels, opts, h_min, h_max, h_init, out, &P)) return rc;
+  GLIA_HIP_TRY(hipSetDevice(c->device));
+  c->mlt = glia_hmt_mlp_train_timing();
+  DeviceEval ev;
+  if (int rc = mlp_train_device_create(P.X.data(), P.t.data(), (long long)P.t.size(), P.D, P.o.n1, P.o.n2, c->libm.exp_variant, c->stream, &ev.st))
+    return rc;
+  const int rc = finish(P, ev, h_min, h_max, out);
+  if (rc == GLIA_HMT_OK) {
+    for (const glia_hmt_mlp_train_record& r : (*out)->r.trace) c->mlt.iterations += r.kind == 0;
+    c->mlt.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    mlp_train_device_timing(ev.st, &c->mlt);
+  }
+  return rc;
+}
+
+int glia_hmt_mlp_model_info(const glia_hmt_mlp_model* m, int* rounds, int64_t* n_weights, int64_t* n_trace, int* stopped_nonfinite,
+                            int64_t* n_used_rows, int* n_sigma) {
+  if (!m) { set_error("mlp_model_info: NULL model"); return GLIA_HMT_ERR_ARG; }
+  if (rounds) *rounds = (int)m->r.round_w.size();
+  if (n_weights) *n_weights = (int64_t)m->r.round_w[0].size();
+  if (n_trace) *n_trace = (int64_t)m->r.trace.size();
+  if (stopped_nonfinite) *stopped_nonfinite = m->r.stopped_nonfinite;
+  if (n_used_rows) *n_used_rows = m->r.n_used;
+  if (n_sigma) *n_sigma = (int)m->r.sigma2.size();
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_mlp_model_weights(const glia_hmt_mlp_model* m, int round, double* h_w) {
+  if (!m || !h_w) { set_error("mlp_model_weights: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  if ((round = pick_round(m, round, "mlp_model_weights")) < 0) return GLIA_HMT_ERR_ARG;
+  memcpy(h_w, m->r.round_w[round].data(), sizeof(double) * m->r.round_w[round].size());
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_mlp_model_trace(const glia_hmt_mlp_model* m, glia_hmt_mlp_train_record* h_records) {
+  if (!m || (!h_records && !m->r.trace.empty())) { set_error("mlp_model_trace: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  if (!m->r.trace.empty()) memcpy(h_records, m->r.trace.data(), sizeof(glia_hmt_mlp_train_record) * m->r.trace.size());
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_mlp_model_sigmas(const glia_hmt_mlp_model* m, double* h_sigma2, double* h_sigma2_eval) {
+  if (!m) { set_error("mlp_model_sigmas: NULL model"); return GLIA_HMT_ERR_ARG; }
+  if (h_sigma2) std::copy(m->r.sigma2.begin(), m->r.sigma2.end(), h_sigma2);
+  if (h_sigma2_eval) std::copy(m->r.sigma2_eval.begin(), m->r.sigma2_eval.end(), h_sigma2_eval);
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_mlp_model_write(const glia_hmt_mlp_model* m, const char* path, int round) {
+  if (!m || !path) { set_error("mlp_model_write: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  if ((round = pick_round(m, round, "mlp_model_write")) < 0) return GLIA_HMT_ERR_ARG;
+  FILE* f = fopen(path, "w");
+  if (!f) { set_error(std::string("Error: cannot open file ") + path); return GLIA_HMT_ERR_IO; }
+  bool ok = true;
+  for (double v : m->r.round_w[round]) ok = fprintf(f, "%.17g\n", v) > 0 && ok;
+  ok = fclose(f) == 0 && ok;
+  if (!ok) { set_error(std::string("mlp_model_write: cannot write ") + path); return GLIA_HMT_ERR_IO; }
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_mlp_model_create_mlp(glia_hmt_ctx* c, const glia_hmt_mlp_model* m, int round, glia_hmt_mlp** out) {
+  if (!m || !out) { set_error("mlp_model_create_mlp: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  if ((round = pick_round(m, round, "mlp_model_create_mlp")) < 0) return GLIA_HMT_ERR_ARG;
+  const double* w = m->r.round_w[round].data();
+  const int64_t nw = (int64_t)m->r.round_w[round].size();
+  const bool mm = !m->r.mn.empty();
+  return glia_hmt_mlp_create(c, 1, &w, &nw, m->r.n1, m->r.n2, mm ? m->r.mn.data() : nullptr, mm ? m->r.mx.data() : nullptr, (int64_t)m->r.mn.size(),
+                             nullptr, out);
+}
+
+void glia_hmt_mlp_model_free(glia_hmt_mlp_model* m) { delete m; }
+
+int glia_hmt_mlp_train_limits(int* chunk_rows, int* max_hidden, int* max_dim) {
+  if (chunk_rows) *chunk_rows = kMlpTrainChunk;
+  if (max_hidden) *max_hidden = kMlpTrainMaxHidden;
+  if (max_dim) *max_dim = kMlpTrainMaxDim;
+  return GLIA_HMT_OK;
+}
+
+double glia_hmt_mlp_init_weight(uint64_t seed, uint64_t p) { return mlp_init_weight(seed, p); }
+
+int glia_hmt_rows_minmax(const double* const* h_blocks, const int64_t* n_rows, int n_blocks, int dim, double* h_min, double* h_max) {
+  if (!h_blocks || !n_rows || n_blocks < 0 || dim < 1 || !h_min || !h_max) { set_error("rows_minmax: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  for (int b = 0; b < n_blocks; ++b)
+    if (n_rows[b] < 0 || (n_rows[b] > 0 && !h_blocks[b])) { set_error("rows_minmax: invalid block"); return GLIA_HMT_ERR_ARG; }
+  mlp_rows_minmax(h_blocks, n_rows, n_blocks, dim, h_min, h_max);
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_last_mlp_train_timing(const glia_hmt_ctx* c, glia_hmt_mlp_train_timing* out) {
+  if (!c || !out) { set_error("last_mlp_train_timing: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  *out = c->mlt;
+  return GLIA_HMT_OK;
+}
+
+}  // extern "C"

@@ -23,4 +23,15 @@ struct DeviceMlp {
 int launch_mlp_predict(const DeviceMlp& mlp, const double* d_rows, long long n_rows, long long row_stride, double* d_pred, double* d_logit,
                        hipStream_t stream);
 
+// ---- training (mlp_train.hip; the definition: mlp_backward.hpp) ----
+// The device evaluator of the trainer: prepared rows X [n][D] and targets [n] resident for the state's lifetime.  create: a memory plan
+// beyond 85 % of the free device memory is GLIA_HMT_ERR_UNSUPPORTED.  eval: L = sum e^2 and, when h_grad != NULL, grad = -sum g_i e_i
+// for the weights h_w, in the two-level order of the definition.
+struct MlpTrainDevice;
+int mlp_train_device_create(const double* h_X, const double* h_t, long long n, int D, int n1, int n2, int exp_variant, hipStream_t stream,
+                            MlpTrainDevice** out);
+int mlp_train_device_eval(MlpTrainDevice* st, const double* h_w, double* L, double* h_grad);
+void mlp_train_device_timing(const MlpTrainDevice* st, glia_hmt_mlp_train_timing* out);      // adds the device times, sets device_bytes
+void mlp_train_device_free(MlpTrainDevice* st);
+
 }  // namespace glia

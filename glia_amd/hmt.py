@@ -720,6 +720,142 @@ def mlp_predict_host(weights, n1, n2, rows, mn=None, mx=None, distributor_args=N
         m.close()
 
 
+class MLPTrainOpts(C.Structure):
+    """glia_hmt_mlp_train_opts: the options of train_sshmt_mlp's supervised part (sshmt/main_train_sshmt_mlp.cxx:20-47); the fields
+    after seed ask for what is not built and are refused unless they hold their defaults"""
+    _fields_ = [("n1", C.c_int), ("n2", C.c_int), ("wr", C.c_double), ("ws", C.c_double), ("sigma_s", C.c_double), ("update_sigma_s", C.c_int),
+                ("optimizer", C.c_int), ("step", C.c_double), ("step_decay", C.c_double), ("fixed_step_decay_iterations", C.c_int),
+                ("sigma_update_step_period", C.c_int), ("max_iterations", C.c_int), ("n_sigma_updates", C.c_int), ("pos_target", C.c_double),
+                ("neg_target", C.c_double), ("min_sigma2", C.c_double), ("seed", C.c_uint64), ("wu", C.c_double), ("update_sigma_u", C.c_int),
+                ("sup_batch_size", C.c_int), ("uns_batch_size", C.c_int), ("balance_sup_batch", C.c_int), ("alt_su", C.c_int)]
+
+
+class MLPTrainTiming(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("ms_total", "ms_upload", "ms_weights", "ms_chunk", "ms_fold", "ms_readback")] + \
+               [(k, C.c_int64) for k in ("evals", "grad_evals", "iterations")] + [("device_bytes", C.c_uint64)]
+
+
+MLP_TRAIN_RECORD = np.dtype([("fx", np.float64), ("xnorm", np.float64), ("gnorm", np.float64), ("step", np.float64), ("sigma2", np.float64),
+                             ("round", np.int32), ("t", np.int32), ("kind", np.int32), ("rollbacks", np.int32)])      # glia_hmt_mlp_train_record
+
+
+def mlp_train_limits():
+    """glia_hmt_mlp_train_limits: rows of a chunk of the gradient's reduction, the most hidden units, the most columns"""
+    v = [C.c_int() for _ in range(3)]
+    _check(lib().glia_hmt_mlp_train_limits(*[C.byref(x) for x in v]))
+    return dict(zip(("chunk_rows", "max_hidden", "max_dim"), (x.value for x in v)))
+
+
+def mlp_init_weights(seed, n):
+    """glia_hmt_mlp_init_weight: the first n initial weights of an MLP under seed.  Host-only."""
+    f = lib().glia_hmt_mlp_init_weight
+    f.restype = C.c_double
+    return np.array([f(C.c_uint64(seed), C.c_uint64(p)) for p in range(n)], np.float64)
+
+
+def rows_minmax(blocks):
+    """glia_hmt_rows_minmax: the (minima, maxima) normalize_sample finds over several [n_i, dim] row blocks (util/stats.hxx:280-314)"""
+    if isinstance(blocks, np.ndarray) and blocks.ndim == 2:
+        blocks = [blocks]
+    keep = [np.ascontiguousarray(b, dtype=np.float64) for b in blocks]
+    dim = keep[0].shape[1]
+    assert all(b.ndim == 2 and b.shape[1] == dim for b in keep)
+    ptrs = (C.c_void_p * len(keep))(*[b.ctypes.data for b in keep])
+    lens = (C.c_int64 * len(keep))(*[b.shape[0] for b in keep])
+    mn = np.empty(dim, np.float64); mx = np.empty(dim, np.float64)
+    _check(lib().glia_hmt_rows_minmax(ptrs, lens, C.c_int(len(keep)), C.c_int(dim), _np(mn), _np(mx)))
+    return mn, mx
+
+
+class MLPModel:
+    """A trained MLP / logsig model on the host (glia_hmt_mlp_model): the weights after every sigma round, the optimiser's trace, the
+    sigmas, whether training stopped on a value that was not finite."""
+
+    def __init__(self, handle, n1, n2):
+        self.h = handle
+        self.n1, self.n2 = n1, n2
+        v = (C.c_int(), C.c_int64(), C.c_int64(), C.c_int(), C.c_int64(), C.c_int())
+        _check(lib().glia_hmt_mlp_model_info(self.h, *[C.byref(x) for x in v]))
+        self.rounds, self.n_weights, n_trace, stopped, self.n_used_rows, n_sigma = (x.value for x in v)
+        self.stopped_nonfinite = bool(stopped)
+        self.trace = np.zeros(n_trace, MLP_TRAIN_RECORD)
+        _check(lib().glia_hmt_mlp_model_trace(self.h, _np(self.trace) if n_trace else None))
+        self.sigma2 = np.zeros(n_sigma); self.sigma2_eval = np.zeros(n_sigma)
+        _check(lib().glia_hmt_mlp_model_sigmas(self.h, _np(self.sigma2), _np(self.sigma2_eval)))
+
+    def weights(self, round=-1):
+        w = np.empty(self.n_weights, np.float64)
+        _check(lib().glia_hmt_mlp_model_weights(self.h, C.c_int(round), _np(w)))
+        return w
+
+    def write(self, path, round=-1):
+        """one %.17g double per line: reads back bit for bit (mlp_file_parse, MLP(...))"""
+        _check(lib().glia_hmt_mlp_model_write(self.h, str(path).encode(), C.c_int(round)))
+
+    def mlp(self, ctx, round=-1):
+        """the classifier MLP.predict / RegionMap.merge_order_bc take, with the min/max table the training used; ctx None: host-only"""
+        m = MLP.__new__(MLP)
+        m.h = C.c_void_p()
+        m.ctx = ctx
+        _check(lib().glia_hmt_mlp_model_create_mlp(ctx.h if ctx is not None else None, self.h, C.c_int(round), C.byref(m.h)))
+        return m
+
+    def close(self):
+        if self.h:
+            lib().glia_hmt_mlp_model_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def train_mlp(ctx, rows, labels, n1=10, n2=10, minmax=None, init=None, **opts):
+    """train_sshmt_mlp / train_sshmt_logsig without the unsupervised term: rows [n, dim] float64, labels [n] (+1 / -1; any
+    other label drops the row), n1 = n2 = 0 for logsig, minmax = (minima, maxima) to rescale rows by, init = initial weights.  Options:
+    the fields of MLPTrainOpts (wr, ws, sigma_s, update_sigma_s, optimizer, step, step_decay, fixed_step_decay_iterations,
+    sigma_update_step_period, max_iterations, n_sigma_updates, pos_target, neg_target, min_sigma2, seed).  Forward pass, backward pass and
+    the gradient's reduction run on the device; ctx = None runs the definition on one host thread (train_mlp_host)."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+    assert rows.ndim == 2 and labels.shape[0] == rows.shape[0]
+    o = MLPTrainOpts()
+    lib().glia_hmt_mlp_train_opts_default(C.byref(o))
+    o.n1, o.n2 = n1, n2
+    for k, v in opts.items():
+        if k not in dict(MLPTrainOpts._fields_):
+            raise TypeError("train_mlp: unknown option " + k)
+        setattr(o, k, v)
+    mn = mx = None
+    if minmax is not None:
+        mn = np.ascontiguousarray(minmax[0], dtype=np.float64); mx = np.ascontiguousarray(minmax[1], dtype=np.float64)
+        if min(mn.size, mx.size) < rows.shape[1]:
+            raise HmtError(ERR_ARG, "train_mlp: fewer min/max entries than columns")
+    if init is not None:
+        init = np.ascontiguousarray(init, dtype=np.float64)
+        D = rows.shape[1] + 1
+        if init.size != (D * n1 + (n1 + 1) * n2 + n2 + 1 if n1 else D):
+            raise HmtError(ERR_ARG, "train_mlp: %d initial weights do not fit the model" % init.size)
+    h = C.c_void_p()
+    _check(lib().glia_hmt_mlp_train(ctx.h if ctx is not None else None, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(labels),
+                                    C.byref(o), _np(mn) if mn is not None else None, _np(mx) if mx is not None else None,
+                                    _np(init) if init is not None else None, C.byref(h)))
+    return MLPModel(h, n1, n2)
+
+
+def train_mlp_host(rows, labels, n1=10, n2=10, minmax=None, init=None, **opts):
+    """glia_hmt_mlp_train_host: the definition of DESIGN 3.14 on one host thread; no GPU, no context"""
+    return train_mlp(None, rows, labels, n1, n2, minmax, init, **opts)
+
+
+def last_mlp_train_timing(ctx):
+    t = MLPTrainTiming()
+    _check(lib().glia_hmt_last_mlp_train_timing(ctx.h, C.byref(t)))
+    return {k: getattr(t, k) for k, _ in MLPTrainTiming._fields_}
+
+
 class TrainOpts(C.Structure):
     """glia_hmt_train_opts: train_rf's options (ml/rf/main_train_rf.cxx:11-15) + max_depth + seed"""
     _fields_ = [("ntree", C.c_int), ("mtry", C.c_int), ("sample_ratio", C.c_double), ("nodesize", C.c_int), ("balance", C.c_int),

@@ -394,6 +394,86 @@ typedef struct {
 } glia_hmt_forest_train_timing;
 int glia_hmt_last_forest_train_timing(const glia_hmt_ctx* ctx, glia_hmt_forest_train_timing* out);
 
+/* ---- training the MLP / logsig classifier --------------------------------------------------------------
+ * Replaces the supervised part of train_sshmt_mlp / train_sshmt_logsig (sshmt/main_train_sshmt_mlp.cxx:96-168): the energy
+ * wr * |w|^2 / 2 + ws * (0.5 * L / sigma^2 + n * log(sigma^2) / 2) with L = sum (t_i - f_i)^2 over the rows labelled +1 / -1
+ * (type/energy_function.hxx:164-230, alg/function.hxx:171-267), the vanilla / Adam / momentum updates with a fixed or an adaptive step
+ * (alg/gd.hxx) and the sigma rule and outer loop of sshmt_util.hxx:140-207.  The arithmetic is this library's own definition
+ * (glia_amd/csrc/mlp_backward.hpp): no parity with Eigen's sums, Boost's Gaussian or the OpenMP partial sums is
+ * possible or claimed.  The unsupervised term, batch samplers and altSU are not built: an opts struct that asks for them is
+ * GLIA_HMT_ERR_UNSUPPORTED with a message naming the field.  sigma^2 is updated only when update_sigma_s is set (the reference's tool
+ * also updates it whenever it runs with --v 0).
+ * glia_hmt_mlp_train_opts: the tool's options and defaults; min_sigma2 is the floor the tool passes (0.0); seed keys the initial
+ * weights of an MLP (a logsig model starts at zeros; h_init, when given, takes precedence over both). */
+typedef struct {
+  int n1, n2;                        /* --nn1 10, --nn2 10; 0 / 0: logsig */
+  double wr, ws;                     /* --wr 0, --ws 0 */
+  double sigma_s;                    /* --ss 0 */
+  int update_sigma_s;                /* --uss 0 */
+  int optimizer;                     /* --topt 1: vanilla, 2: Adam, 3: momentum */
+  double step, step_decay;           /* --lr 0, --lrd 1 (1: fixed step) */
+  int fixed_step_decay_iterations;   /* --lrdi -1 */
+  int sigma_update_step_period;      /* --lrds -1 */
+  int max_iterations;                /* --tw 0 */
+  int n_sigma_updates;               /* --ts 0 */
+  double pos_target, neg_target;     /* 0.05, 0.95 */
+  double min_sigma2;                 /* 0.0 */
+  uint64_t seed;                     /* 0 */
+  /* not supported; anything but the defaults is refused */
+  double wu;                         /* --wu 0 */
+  int update_sigma_u;                /* --usu 0 */
+  int sup_batch_size, uns_batch_size;/* --bss -1, --bsu -1 */
+  int balance_sup_batch;             /* --bb 0 */
+  int alt_su;                        /* 0 */
+} glia_hmt_mlp_train_opts;
+void glia_hmt_mlp_train_opts_default(glia_hmt_mlp_train_opts* opts);
+/* One evaluation of the optimiser: kind 0 = an iteration (fx, |x|, |g| before its step; step and, with the adaptive rule, the number of
+ * roll-backs after it), 1 = the final statistics of a round (the reference's last "gd:" line), 2 = the evaluation that was not finite. */
+typedef struct {
+  double fx, xnorm, gnorm, step, sigma2;
+  int32_t round, t, kind, rollbacks;
+} glia_hmt_mlp_train_record;
+typedef struct glia_hmt_mlp_model glia_hmt_mlp_model;
+/* h_rows [n_rows][dim], h_labels [n_rows]: rows with a label other than +1 / -1 are dropped.  h_min / h_max [dim] (both or neither):
+ * rows are rescaled once, as glia_hmt_mlp_predict rescales them.  h_init: the D * N1 + (N1 + 1) * N2 + N2 + 1 (logsig: D) initial weights
+ * or NULL.  GLIA_HMT_ERR_ARG with a message, before any kernel: ws and wr both off, sigma_s == 0 without update_sigma_s, n1 == 0 xor
+ * n2 == 0, no labelled row, a row or weight that is not finite.  Hidden layers of more than 32 units, rows of more than 384 columns, a
+ * memory plan beyond 85 % of the free device memory: GLIA_HMT_ERR_UNSUPPORTED.  If fx or sum g^2 is not finite after an iteration the
+ * call stops, restores the weights from before that step and says so in the model (stopped_nonfinite); that is not an error.
+ * glia_hmt_mlp_train_host: the same on one host thread, no GPU -- the definition's executable form. */
+int glia_hmt_mlp_train(glia_hmt_ctx* ctx, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels,
+                       const glia_hmt_mlp_train_opts* opts, const double* h_min, const double* h_max, const double* h_init,
+                       glia_hmt_mlp_model** out);
+int glia_hmt_mlp_train_host(const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_mlp_train_opts* opts,
+                            const double* h_min, const double* h_max, const double* h_init, glia_hmt_mlp_model** out);
+/* rounds: sigma rounds whose weights the model holds; n_sigma: entries of glia_hmt_mlp_model_sigmas (one per sigma update) */
+int glia_hmt_mlp_model_info(const glia_hmt_mlp_model* model, int* rounds, int64_t* n_weights, int64_t* n_trace, int* stopped_nonfinite,
+                            int64_t* n_used_rows, int* n_sigma);
+/* round in [0, rounds), or -1: the last.  A model trained with n_sigma_updates == 0 holds one round: the initial weights. */
+int glia_hmt_mlp_model_weights(const glia_hmt_mlp_model* model, int round, double* h_w);
+int glia_hmt_mlp_model_trace(const glia_hmt_mlp_model* model, glia_hmt_mlp_train_record* h_records);
+int glia_hmt_mlp_model_sigmas(const glia_hmt_mlp_model* model, double* h_sigma2, double* h_sigma2_eval);
+/* One %.17g double per line: a file that reads back bit for bit (the reference writes the stream's default precision). */
+int glia_hmt_mlp_model_write(const glia_hmt_mlp_model* model, const char* path, int round);
+/* The classifier glia_hmt_mlp_predict and glia_hmt_merge_order_bc_mlp take, with the min/max table the training used (ctx NULL: host-only). */
+int glia_hmt_mlp_model_create_mlp(glia_hmt_ctx* ctx, const glia_hmt_mlp_model* model, int round, glia_hmt_mlp** out);
+void glia_hmt_mlp_model_free(glia_hmt_mlp_model* model);
+/* Host-only: rows of a chunk of the reduction (part of the definition), the most units per hidden layer, the most columns. */
+int glia_hmt_mlp_train_limits(int* chunk_rows, int* max_hidden, int* max_dim);
+/* Host-only: the initial weight p of an MLP under seed. */
+double glia_hmt_mlp_init_weight(uint64_t seed, uint64_t p);
+/* Host-only: the per-column minima and maxima stats::rescale finds over several row blocks (util/stats.hxx:280-314). */
+int glia_hmt_rows_minmax(const double* const* h_blocks, const int64_t* n_rows, int n_blocks, int dim, double* h_min, double* h_max);
+/* the last glia_hmt_mlp_train call of this context: device times from events, summed over all evaluations */
+typedef struct {
+  double ms_total, ms_upload;        /* wall clock of the call; rows and targets to the device */
+  double ms_weights, ms_chunk, ms_fold, ms_readback;   /* weights up, chunk kernel, fold kernel, L and gradient down */
+  int64_t evals, grad_evals;         /* evaluations of L; those that also computed the gradient */
+  int64_t iterations;                /* optimiser iterations (trace records of kind 0) */
+  uint64_t device_bytes;
+} glia_hmt_mlp_train_timing;
+int glia_hmt_last_mlp_train_timing(const glia_hmt_ctx* ctx, glia_hmt_mlp_train_timing* out);
+
 /* Length of one feature vector for the configuration the rag was built with (BoundaryClassificationFeats::dim,
  * hmt/bc_feat.hxx:225-230; or selectFeatures' length with --simpf). */
 int glia_hmt_feat_dim(const glia_hmt_rag* rag);
