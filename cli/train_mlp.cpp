@@ -5,8 +5,9 @@
 // Flags and defaults are the reference's (main_train_sshmt_mlp.cxx:171-236); --seed keys this library's initial weights and --fmm
 // rescales the rows inside, as pred_mlp --fmm does (the reference expects normalize_sample to have run).  --omp is a printf pattern
 // taking the round index; a model is written every --si rounds and after the last.  --v 1 (the default) prints the reference's "gd:"
-// and "learn-" lines from the trace.  The tools are not named train_sshmt_*: the semi-supervised term is not built -- --uo, --uf, a
-// non-zero --wu, --bsu, --bss > 0, --bb 1 and --usu 1 end with a message naming the flag and exit status 1.
+// and "learn-" lines from the trace.  The tools are not named train_sshmt_*: they train without the semi-supervised term (train_sshmt_mlp
+// and train_sshmt_logsig have it) -- --uo, --uf, a non-zero --wu, --bsu, --bss > 0, --bb 1 and --usu 1 end with a message naming the flag
+// and exit status 1.
 #include <climits>
 
 #include "common.hpp"

@@ -1,0 +1,153 @@
+// cli/train_sshmt_mlp.cpp -- sshmt/main_train_sshmt_mlp.cxx and main_train_sshmt_logsig.cxx with the merge-path (unsupervised) term:
+// trains the MLP (train_sshmt_mlp) or the logsig model (train_sshmt_logsig: the same source with the hidden layers fixed at 0 / 0) on
+// labelled feature rows and on the merge paths of unlabelled volumes, on the GPU.
+//   train_sshmt_mlp [--sl labels... --sf feats...] [--uo orders... --uf feats...] [--im model] [--nn1 10 --nn2 10] --wr w --wu w --ws w
+//                   --su sigma --ss sigma [--usu 1] [--uss 1] [--topt 1|2|3] --lr step [--lrd decay] [--lrdi n] [--lrds n] --tw iterations
+//                   --ts rounds [--si n] --omp pattern [--v 1] [--seed s] [--fmm minmax]
+// Flags and defaults are the reference's (main_train_sshmt_mlp.cxx:171-236); --seed, --fmm, --omp, --si and the printed lines are
+// train_mlp's.  --uo / --uf come in equal numbers: file k of --uf holds one row per merge of file k of --uo (bc_feat's output for that
+// order).  --sl / --sf may be left out when --ws is 0.  Mini-batches are not built: --bsu, --bss > 0, --bb 1 and --te / --tb other than
+// 1 end with a message naming the flag and exit status 1.
+#include <climits>
+
+#include "common.hpp"
+
+using namespace cli;
+
+#ifdef GLIA_TRAIN_LOGSIG
+static const char* const kTool = "train_sshmt_logsig";
+#else
+static const char* const kTool = "train_sshmt_mlp";
+#endif
+
+int main(int argc, char* argv[]) {
+  const std::string usage = std::string("Usage: ") + kTool + " [--sl <labels>... --sf <feats>...] [--uo <orders>... --uf <feats>...] [--im <model>] "
+#ifndef GLIA_TRAIN_LOGSIG
+                            "[--nn1 <N>] [--nn2 <N>] "
+#endif
+                            "[--wr <w>] [--wu <w>] [--ws <w>] [--su <sigma>] [--ss <sigma>] [--usu <0|1>] [--uss <0|1>] [--topt <1|2|3>] [--lr <step>] "
+                            "[--lrd <decay>] [--lrdi <n>] [--lrds <n>] [--tw <iterations>] [--ts <rounds>] [--si <n>] --omp <pattern> [--v <0|1>] "
+                            "[--seed <s>] [--fmm <minmax>]\n"
+                            "  (flags as sshmt/main_train_sshmt_mlp.cxx:171-236; not supported: --bsu --bss --bb, --te / --tb other than 1)\n";
+  Args a = parse(argc, argv, {}, {"sl", "sf", "im", "nn1", "nn2", "wr", "ws", "ss", "uss", "topt", "lr", "lrd", "lrdi", "lrds", "tw", "ts", "si", "omp", "v",
+                                  "seed", "fmm", "uo", "uf", "wu", "su", "usu", "bsu", "bss", "bb", "te", "tb"}, usage);
+  auto refuse = [&](const char* flag, const char* what) { perr(std::string("Error: ") + kTool + ": --" + flag + " is not supported (" + what + ")"); };
+  if (a.has("bsu") && atoi(a.str("bsu", "-1").c_str()) > 0) refuse("bsu", "batch samplers");
+  if (a.has("bss") && atoi(a.str("bss", "-1").c_str()) > 0) refuse("bss", "batch samplers");
+  if (flagOf(a, "bb")) refuse("bb", "batch samplers");
+  if (a.has("te") && atoi(a.str("te", "1").c_str()) != 1) refuse("te", "batch samplers");
+  if (a.has("tb") && atoi(a.str("tb", "1").c_str()) != 1) refuse("tb", "batch samplers");
+  if (!a.has("omp") || a.all("omp").empty()) { std::cerr << "Error: the option '--omp' is required but missing\n" << usage; return EXIT_FAILURE; }
+  glia_hmt_sshmt_train_opts so;
+  glia_hmt_sshmt_train_opts_default(&so);
+  glia_hmt_mlp_train_opts& o = so.base;
+#ifdef GLIA_TRAIN_LOGSIG
+  o.n1 = o.n2 = 0;
+#else
+  o.n1 = atoi(a.str("nn1", "10").c_str()); o.n2 = atoi(a.str("nn2", "10").c_str());
+#endif
+  o.wr = atof(a.str("wr", "0").c_str()); o.ws = atof(a.str("ws", "0").c_str()); o.sigma_s = atof(a.str("ss", "0").c_str());
+  o.wu = atof(a.str("wu", "0").c_str()); so.sigma_u = atof(a.str("su", "0").c_str());
+  o.update_sigma_s = flagOf(a, "uss"); o.update_sigma_u = flagOf(a, "usu");
+  o.optimizer = atoi(a.str("topt", "1").c_str());
+  o.step = atof(a.str("lr", "0").c_str()); o.step_decay = atof(a.str("lrd", "1").c_str());
+  o.fixed_step_decay_iterations = atoi(a.str("lrdi", "-1").c_str()); o.sigma_update_step_period = atoi(a.str("lrds", "-1").c_str());
+  o.max_iterations = atoi(a.str("tw", "0").c_str()); o.n_sigma_updates = atoi(a.str("ts", "0").c_str());
+  o.seed = strtoull(a.str("seed", "0").c_str(), nullptr, 0);
+  const int saveInterval = a.has("si") ? atoi(a.str("si").c_str()) : INT_MAX;
+  const bool verbose = a.has("v") ? flagOf(a, "v") : true;
+  const std::string pattern = a.str("omp");
+
+  const auto featFiles = a.has("sf") ? a.all("sf") : std::vector<std::string>(), labelFiles = a.has("sl") ? a.all("sl") : std::vector<std::string>();
+  const auto unsFeatFiles = a.has("uf") ? a.all("uf") : std::vector<std::string>(), orderFiles = a.has("uo") ? a.all("uo") : std::vector<std::string>();
+  if (unsFeatFiles.size() != orderFiles.size())
+    perr(std::string("Error: ") + kTool + ": --uo and --uf must come in equal numbers (" + std::to_string(orderFiles.size()) + " and " + std::to_string(unsFeatFiles.size()) + ")");
+  if (std::fabs(o.ws) >= 2.22e-16 && (featFiles.empty() || labelFiles.empty())) perr(std::string("Error: ") + kTool + ": --sl and --sf are required unless --ws is 0");
+  // the rows of all feature files in file order, the labels of all label files (sshmt_util.hxx:11-27)
+  std::vector<double> rows;
+  std::vector<int32_t> labels;
+  int dim = 0;
+  for (auto& f : featFiles) {
+    int64_t r = 0;
+    int d = 0;
+    const std::vector<double> x = readRows(f, &r, &d);
+    if (r > 0 && dim > 0 && d != dim) perr("Error: invalid data file dimension in " + f);
+    if (r > 0) dim = d;
+    rows.insert(rows.end(), x.begin(), x.end());
+  }
+  for (auto& f : labelFiles) {
+    std::ifstream is(f);
+    if (!is) perr("Error: cannot open file " + f);
+    long long v;
+    while (is >> v) labels.push_back((int32_t)v);
+  }
+  // one block per (--uo, --uf) pair (sshmt_util.hxx:30-52)
+  std::vector<std::vector<double>> urows(orderFiles.size());
+  std::vector<std::vector<uint32_t>> orders(orderFiles.size());
+  std::vector<glia_hmt_sshmt_block> blocks(orderFiles.size());
+  for (size_t b = 0; b < orderFiles.size(); ++b) {
+    orders[b] = readOrder(orderFiles[b]);
+    int64_t r = 0;
+    int d = 0;
+    urows[b] = readRows(unsFeatFiles[b], &r, &d);
+    if (r > 0 && dim > 0 && d != dim) perr("Error: invalid data file dimension in " + unsFeatFiles[b]);
+    if (r > 0) dim = d;
+    if ((int64_t)(orders[b].size() / 3) != r)
+      perr("Error: " + std::to_string(r) + " rows in " + unsFeatFiles[b] + " for " + std::to_string(orders[b].size() / 3) + " merges in " + orderFiles[b] + "...");
+    blocks[b].rows = urows[b].data(); blocks[b].order = orders[b].data(); blocks[b].n_merges = r;
+  }
+  if (dim == 0) perr("Error: no rows in the feature files...");
+  const int64_t n = (int64_t)(rows.size() / (size_t)dim);
+  if ((int64_t)labels.size() != n) perr("Error: " + std::to_string(labels.size()) + " labels for " + std::to_string(n) + " rows...");
+  std::vector<double> mn, mx, init;
+  if (a.has("fmm")) {
+    int64_t r = 0;
+    int d = 0;
+    const std::vector<double> t = readRows(a.str("fmm"), &r, &d);
+    if (r < 2 || d < dim) perr("Error: the min/max file needs two rows of at least " + std::to_string(dim) + " values: " + a.str("fmm"));
+    mn.assign(t.begin(), t.begin() + dim); mx.assign(t.begin() + d, t.begin() + d + dim);
+  }
+  if (a.has("im")) {
+    if (verbose) printf("Initializing from input model...\n");
+    int64_t nw = 0;
+    check(glia_hmt_mlp_file_parse(a.str("im").c_str(), nullptr, 0, &nw));
+    init.resize((size_t)nw);
+    check(glia_hmt_mlp_file_parse(a.str("im").c_str(), init.data(), nw, &nw));
+    const int64_t want = o.n1 > 0 ? (int64_t)(dim + 1) * o.n1 + (int64_t)(o.n1 + 1) * o.n2 + o.n2 + 1 : dim + 1;
+    if (nw != want) perr("Error: the input model holds " + std::to_string(nw) + " weights, rows of " + std::to_string(dim) + " columns need " + std::to_string(want));
+  }
+  glia_hmt_ctx* ctx;
+  check(glia_hmt_ctx_create(0, nullptr, &ctx));
+  glia_hmt_mlp_model* model;
+  check(glia_hmt_sshmt_train(ctx, n ? rows.data() : nullptr, n, dim, n ? labels.data() : nullptr, blocks.data(), (int)blocks.size(), &so,
+                             mn.empty() ? nullptr : mn.data(), mx.empty() ? nullptr : mx.data(), init.empty() ? nullptr : init.data(), &model));
+  int rounds = 0, stopped = 0, nSigma = 0;
+  int64_t nTrace = 0, used = 0, nPaths = 0, nUnsRows = 0;
+  check(glia_hmt_mlp_model_info(model, &rounds, nullptr, &nTrace, &stopped, &used, &nSigma));
+  check(glia_hmt_mlp_model_paths(model, &nPaths, &nUnsRows));
+  if (verbose) {
+    std::vector<glia_hmt_mlp_train_record> tr((size_t)nTrace);
+    std::vector<double> s2((size_t)nSigma), s2e((size_t)nSigma), u2((size_t)nSigma), u2e((size_t)nSigma);
+    check(glia_hmt_mlp_model_trace(model, tr.data()));
+    check(glia_hmt_mlp_model_sigmas(model, s2.data(), s2e.data()));
+    check(glia_hmt_mlp_model_sigmas_u(model, u2.data(), u2e.data()));
+    printf("Use %lld supervised samples.\n", (long long)used);
+    printf("Use %lld unsupervised samples.\n", (long long)nPaths);
+    size_t k = 0;
+    for (int i = 0; i < nSigma; ++i) {
+      printf("\tlearn-%d: su = %g (%g), ss = %g (%g)\n", i, std::sqrt(u2[i]), std::sqrt(u2e[i]), std::sqrt(s2[i]), std::sqrt(s2e[i]));
+      for (; k < tr.size() && tr[k].round == i; ++k)
+        printf("\tgd: %-6d fx = %-12g |x| = %-12g |g| = %-12g step = %g\n", tr[k].t, tr[k].fx, tr[k].xnorm, tr[k].gnorm, tr[k].step);
+    }
+  }
+  if (stopped) std::cerr << kTool << ": stopped in round " << rounds - 1 << ": the energy or its gradient is not finite; the weights from before that step are kept" << std::endl;
+  for (int i = 0; i < rounds && o.n_sigma_updates > 0; ++i) {
+    if (!((i + 1) % saveInterval == 0 || i == o.n_sigma_updates - 1 || (stopped && i == rounds - 1))) continue;
+    char path[4096];
+    snprintf(path, sizeof(path), pattern.c_str(), i);
+    check(glia_hmt_mlp_model_write(model, path, i));
+  }
+  glia_hmt_mlp_model_free(model);
+  glia_hmt_ctx_destroy(ctx);
+  return EXIT_SUCCESS;
+}

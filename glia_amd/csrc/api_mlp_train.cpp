@@ -1,11 +1,12 @@
 // glia_amd/csrc/api_mlp_train.cpp -- C ABI: training the MLP / logsig classifier (mlp_backward.hpp: the definition and the trainer;
-// mlp_train.hip: the device evaluator).
+// mlp_train.hip: the device evaluator), without and with the merge-path term (sshmt_paths.hpp; sshmt_train.hip).
 #include <chrono>
 #include <cstdio>
 #include <cstring>
 
 #include "api_types.hpp"
 #include "mlp_backward.hpp"
+#include "sshmt_paths.hpp"
 
 struct glia_hmt_mlp_model {
   glia::MlpTrainResult r;
@@ -19,24 +20,34 @@ struct DeviceEval : MlpTrainEval {
   int eval(const double* w, double* L, double* grad) override { return mlp_train_device_eval(st, w, L, grad); }
 };
 
-// everything both entry points check and prepare; *rc_out != 0: refused
+struct DeviceEvalU : MlpTrainEval {
+  SshmtTrainDevice* st = nullptr;
+  ~DeviceEvalU() override { sshmt_train_device_free(st); }
+  int eval(const double* w, double* L, double* grad) override { return sshmt_train_device_eval(st, w, L, grad); }
+};
+
+// everything the entry points check and prepare; *rc_out != 0: refused
 struct Prepared {
   glia_hmt_mlp_train_opts o;
   int D = 0;
   std::vector<double> X, t, w;
+  glia_hmt_sshmt_train_opts so;      // glia_hmt_sshmt_train alone, as `in`
+  SshmtInput in;
 };
 
 int prepare(const char* who, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_mlp_train_opts* opts,
-            const double* h_min, const double* h_max, const double* h_init, glia_hmt_mlp_model** out, Prepared* P) {
+            const double* h_min, const double* h_max, const double* h_init, glia_hmt_mlp_model** out, Prepared* P,
+            const glia_hmt_sshmt_train_opts* sopts = nullptr, bool with_u = false) {
   const std::string me = std::string(who) + ": ";
   if (!out || n_rows < 0 || dim < 1 || (n_rows > 0 && (!h_rows || !h_labels))) { set_error(me + "invalid argument"); return GLIA_HMT_ERR_ARG; }
   *out = nullptr;
   if ((h_min == nullptr) != (h_max == nullptr)) { set_error(me + "minima and maxima come together"); return GLIA_HMT_ERR_ARG; }
-  if (opts) P->o = *opts; else mlp_train_opts_default(&P->o);
+  if (sopts) P->so = *sopts; else sshmt_train_opts_default(&P->so);
+  if (with_u) P->o = P->so.base; else if (opts) P->o = *opts; else mlp_train_opts_default(&P->o);
   const glia_hmt_mlp_train_opts& o = P->o;
-  std::string bad = mlp_train_bad_opts(o);
+  std::string bad = with_u ? sshmt_train_bad_opts(P->so) : mlp_train_bad_opts(o);
   if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_ARG; }
-  bad = mlp_train_unsupported(o);
+  bad = mlp_train_unsupported(o, with_u);
   if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_UNSUPPORTED; }
   if (dim > kMlpTrainMaxDim) { set_error("mlp_train: rows of more than " + std::to_string(kMlpTrainMaxDim) + " columns are not supported"); return GLIA_HMT_ERR_UNSUPPORTED; }
   for (int64_t i = 0; i < n_rows * dim; ++i)
@@ -55,18 +66,59 @@ int prepare(const char* who, const double* h_rows, int64_t n_rows, int dim, cons
     for (long long p = 0; p < d; ++p) P->w[p] = mlp_init_weight(o.seed, (uint64_t)p);
   }
   mlp_train_prepare(h_rows, n_rows, dim, h_labels, h_min, h_max, o.pos_target, o.neg_target, &P->X, &P->t);
-  if (P->t.empty()) { set_error("mlp_train: no row is labelled +1 or -1"); return GLIA_HMT_ERR_ARG; }
+  if (P->t.empty() && (!with_u || !mlp_isfeq(o.ws, 0.0))) { set_error("mlp_train: no row is labelled +1 or -1"); return GLIA_HMT_ERR_ARG; }
   for (double v : P->X)
     if (!std::isfinite(v)) { set_error("mlp_train: a rescaled row holds a value that is not finite"); return GLIA_HMT_ERR_ARG; }
   return GLIA_HMT_OK;
 }
 
-int finish(Prepared& P, MlpTrainEval& ev, const double* h_min, const double* h_max, glia_hmt_mlp_model** out) {
+// the unlabelled blocks of glia_hmt_sshmt_train: checked, the rows prepared as the labelled ones are, the paths and incidence lists built
+int prepare_blocks(const glia_hmt_sshmt_block* blocks, int n_blocks, int dim, const double* h_min, const double* h_max, Prepared* P) {
+  if (n_blocks < 0 || (n_blocks > 0 && !blocks)) { set_error("sshmt_train: invalid blocks"); return GLIA_HMT_ERR_ARG; }
+  const std::string bad = sshmt_bad_lengths(P->so.max_path_length, P->so.min_path_length);
+  if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_UNSUPPORTED; }
+  SshmtInput& in = P->in;
+  in.D = dim + 1;
+  sshmt_fill_tables(P->so.merge_target, P->so.path_target, &in.tb);
+  for (int b = 0; b < n_blocks; ++b) {
+    const glia_hmt_sshmt_block& B = blocks[b];
+    const std::string me = "sshmt_train: block " + std::to_string(b);
+    if (B.n_merges < 0 || (B.n_merges > 0 && (!B.rows || !B.order))) { set_error(me + ": rows and order must both be given, one row per merge"); return GLIA_HMT_ERR_ARG; }
+    const int64_t first_bad = sshmt_check_order(B.order, B.n_merges);
+    if (first_bad >= 0) {
+      set_error(me + ": merge " + std::to_string(first_bad) + " of its order joins a region that does not exist (any more) or creates one that does");
+      return GLIA_HMT_ERR_ARG;
+    }
+    for (int64_t i = 0; i < B.n_merges * dim; ++i)
+      if (!std::isfinite(B.rows[i])) { set_error(me + ": row " + std::to_string(i / dim) + " holds a value that is not finite"); return GLIA_HMT_ERR_ARG; }
+    merge_paths(B.order, B.n_merges, P->so.max_path_length, P->so.min_path_length, in.n_rows, &in.offsets, &in.members);
+    for (int64_t r = 0; r < B.n_merges; ++r) {
+      for (int j = 0; j < dim; ++j) {
+        const double v = B.rows[(size_t)r * dim + j];
+        in.X.push_back(h_min ? mlp_rescale_den(v, h_min[j], (h_max[j] - h_min[j]) + kMlpTrainFeps) : v);
+      }
+      in.X.push_back(1.0);
+    }
+    in.n_rows += B.n_merges;
+  }
+  for (double v : in.X)
+    if (!std::isfinite(v)) { set_error("sshmt_train: a rescaled unlabelled row holds a value that is not finite"); return GLIA_HMT_ERR_ARG; }
+  sshmt_incidence(in.offsets, in.members, in.n_rows, &in.inc_off, &in.inc);
+  return GLIA_HMT_OK;
+}
+
+int finish(Prepared& P, MlpTrainEval& ev, const double* h_min, const double* h_max, glia_hmt_mlp_model** out, MlpTrainEval* ev_u = nullptr) {
   glia_hmt_mlp_model* m = new glia_hmt_mlp_model;
   MlpTrainResult& R = m->r;
   R.D = P.D; R.n1 = P.o.n1; R.n2 = P.o.n2; R.n_used = (int64_t)P.t.size();
   if (h_min) { R.mn.assign(h_min, h_min + (P.D - 1)); R.mx.assign(h_max, h_max + (P.D - 1)); }
-  if (int rc = mlp_train_run(P.o, R.n_used, P.w, ev, &R)) { delete m; return rc; }
+  MlpTrainUns U;
+  if (ev_u) {
+    U.ev = ev_u; U.n_paths = P.in.n_paths(); U.n_rows = P.in.n_rows; U.wu = P.o.wu; U.sigma_u = P.so.sigma_u; U.min_sigma2 = P.o.min_sigma2;
+    U.update_sigma_u = P.o.update_sigma_u;
+  }
+  R.n_paths = P.in.n_paths(); R.n_uns_rows = P.in.n_rows;
+  if (int rc = mlp_train_run(P.o, R.n_used, P.w, ev, &R, ev_u ? &U : nullptr)) { delete m; return rc; }
   if (R.round_w.empty()) R.round_w.push_back(P.w);
   *out = m;
   return GLIA_HMT_OK;
@@ -115,6 +167,96 @@ int glia_hmt_mlp_train(glia_hmt_ctx* c, const double* h_rows, int64_t n_rows, in
     mlp_train_device_timing(ev.st, &c->mlt);
   }
   return rc;
+}
+
+void glia_hmt_sshmt_train_opts_default(glia_hmt_sshmt_train_opts* opts) {
+  if (opts) sshmt_train_opts_default(opts);
+}
+
+int glia_hmt_sshmt_train_host(const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_sshmt_block* blocks,
+                              int n_blocks, const glia_hmt_sshmt_train_opts* opts, const double* h_min, const double* h_max,
+                              const double* h_init, glia_hmt_mlp_model** out) {
+  Prepared P;
+  if (int rc = prepare("sshmt_train_host", h_rows, n_rows, dim, h_labels, nullptr, h_min, h_max, h_init, out, &P, opts, true)) return rc;
+  if (int rc = prepare_blocks(blocks, n_blocks, dim, h_min, h_max, &P)) return rc;
+  MlpTrainHostEval ev;
+  ev.D = P.D; ev.n1 = P.o.n1; ev.n2 = P.o.n2; ev.X = P.X.data(); ev.t = P.t.data(); ev.n = (int64_t)P.t.size();
+  SshmtHostEval eu;
+  eu.n1 = P.o.n1; eu.n2 = P.o.n2; eu.in = &P.in;
+  return finish(P, ev, h_min, h_max, out, &eu);
+}
+
+int glia_hmt_sshmt_train(glia_hmt_ctx* c, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels,
+                         const glia_hmt_sshmt_block* blocks, int n_blocks, const glia_hmt_sshmt_train_opts* opts, const double* h_min,
+                         const double* h_max, const double* h_init, glia_hmt_mlp_model** out) {
+  if (!c) return glia_hmt_sshmt_train_host(h_rows, n_rows, dim, h_labels, blocks, n_blocks, opts, h_min, h_max, h_init, out);
+  const auto t0 = std::chrono::steady_clock::now();
+  Prepared P;
+  if (int rc = prepare("sshmt_train", h_rows, n_rows, dim, h_labels, nullptr, h_min, h_max, h_init, out, &P, opts, true)) return rc;
+  if (int rc = prepare_blocks(blocks, n_blocks, dim, h_min, h_max, &P)) return rc;
+  GLIA_HIP_TRY(hipSetDevice(c->device));
+  c->sst = glia_hmt_sshmt_train_timing();
+  // an evaluator exists only for a term that is on: the trainer asks no other
+  DeviceEval ev;
+  if (!P.t.empty() && !mlp_isfeq(P.o.ws, 0.0))
+    if (int rc = mlp_train_device_create(P.X.data(), P.t.data(), (long long)P.t.size(), P.D, P.o.n1, P.o.n2, c->libm.exp_variant, c->stream, &ev.st))
+      return rc;
+  DeviceEvalU eu;
+  if (P.in.n_paths() > 0 && !mlp_isfeq(P.o.wu, 0.0))
+    if (int rc = sshmt_train_device_create(P.in, P.o.n1, P.o.n2, c->libm.exp_variant, c->stream, &eu.st)) return rc;
+  const int rc = finish(P, ev, h_min, h_max, out, &eu);
+  if (rc == GLIA_HMT_OK) {
+    for (const glia_hmt_mlp_train_record& r : (*out)->r.trace) c->sst.sup.iterations += r.kind == 0;
+    c->sst.sup.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (ev.st) mlp_train_device_timing(ev.st, &c->sst.sup);
+    if (eu.st) sshmt_train_device_timing(eu.st, &c->sst);
+    c->sst.n_paths = P.in.n_paths(); c->sst.n_uns_rows = P.in.n_rows;
+  }
+  return rc;
+}
+
+int glia_hmt_merge_paths(const uint32_t* h_order, int64_t n_merges, int max_len, int min_len, int64_t* n_paths, int64_t* n_members,
+                         int64_t* offsets, int64_t* members) {
+  if (n_merges < 0 || (n_merges > 0 && !h_order) || !n_paths || !n_members || (offsets == nullptr) != (members == nullptr)) {
+    set_error("merge_paths: invalid argument");
+    return GLIA_HMT_ERR_ARG;
+  }
+  const std::string bad = sshmt_bad_lengths(max_len, min_len);
+  if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_UNSUPPORTED; }
+  const int64_t first_bad = sshmt_check_order(h_order, n_merges);
+  if (first_bad >= 0) {
+    set_error("merge_paths: merge " + std::to_string(first_bad) + " joins a region that does not exist (any more) or creates one that does");
+    return GLIA_HMT_ERR_ARG;
+  }
+  std::vector<int64_t> off, mem;
+  merge_paths(h_order, n_merges, max_len, min_len, 0, &off, &mem);
+  if (offsets) {
+    if (*n_paths != (int64_t)off.size() - 1 || *n_members != (int64_t)mem.size()) { set_error("merge_paths: the sizes are not those of the first call"); return GLIA_HMT_ERR_ARG; }
+    std::copy(off.begin(), off.end(), offsets);
+    std::copy(mem.begin(), mem.end(), members);
+  }
+  *n_paths = (int64_t)off.size() - 1; *n_members = (int64_t)mem.size();
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_mlp_model_sigmas_u(const glia_hmt_mlp_model* m, double* h_sigma2, double* h_sigma2_eval) {
+  if (!m) { set_error("mlp_model_sigmas_u: NULL model"); return GLIA_HMT_ERR_ARG; }
+  if (h_sigma2) std::copy(m->r.sigma_u2.begin(), m->r.sigma_u2.end(), h_sigma2);
+  if (h_sigma2_eval) std::copy(m->r.sigma_u2_eval.begin(), m->r.sigma_u2_eval.end(), h_sigma2_eval);
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_mlp_model_paths(const glia_hmt_mlp_model* m, int64_t* n_paths, int64_t* n_uns_rows) {
+  if (!m) { set_error("mlp_model_paths: NULL model"); return GLIA_HMT_ERR_ARG; }
+  if (n_paths) *n_paths = m->r.n_paths;
+  if (n_uns_rows) *n_uns_rows = m->r.n_uns_rows;
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_last_sshmt_train_timing(const glia_hmt_ctx* c, glia_hmt_sshmt_train_timing* out) {
+  if (!c || !out) { set_error("last_sshmt_train_timing: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  *out = c->sst;
+  return GLIA_HMT_OK;
 }
 
 int glia_hmt_mlp_model_info(const glia_hmt_mlp_model* m, int* rounds, int64_t* n_weights, int64_t* n_trace, int* stopped_nonfinite,

@@ -34,4 +34,14 @@ int mlp_train_device_eval(MlpTrainDevice* st, const double* h_w, double* L, doub
 void mlp_train_device_timing(const MlpTrainDevice* st, glia_hmt_mlp_train_timing* out);      // adds the device times, sets device_bytes
 void mlp_train_device_free(MlpTrainDevice* st);
 
+// ---- the merge-path term (sshmt_train.hip; the definition: sshmt_paths.hpp) ----
+// The device evaluator of the unsupervised term: the unlabelled rows, paths and incidence lists of `in` resident for the state's
+// lifetime.  eval: L_U = sum e_p^2 and, when h_grad != NULL, grad_U = -sum_r c_r g_r.  Memory plan as above.
+struct SshmtInput;
+struct SshmtTrainDevice;
+int sshmt_train_device_create(const SshmtInput& in, int n1, int n2, int exp_variant, hipStream_t stream, SshmtTrainDevice** out);
+int sshmt_train_device_eval(SshmtTrainDevice* st, const double* h_w, double* L, double* h_grad);
+void sshmt_train_device_timing(const SshmtTrainDevice* st, glia_hmt_sshmt_train_timing* out);      // fills all but out->sup
+void sshmt_train_device_free(SshmtTrainDevice* st);
+
 }  // namespace glia

@@ -175,6 +175,15 @@ struct MlpTrainResult {
   std::vector<double> sigma2, sigma2_eval;            // after every updateSigmaS: before round 0, then after each round
   int stopped_nonfinite = 0;
   std::vector<double> mn, mx;                         // the table the rows were rescaled by (empty: none)
+  std::vector<double> sigma_u2, sigma_u2_eval;        // the unsupervised term's, after every updateSigmaU; 0.0 while it is off
+  int64_t n_paths = 0, n_uns_rows = 0;                // merge paths and unlabelled rows of the unsupervised term
+};
+// The unsupervised term of the energy (sshmt_paths.hpp): its evaluator gives L_U = sum e_p^2 and grad_U = -sum e_p grad D_p.
+struct MlpTrainUns {
+  MlpTrainEval* ev = nullptr;
+  int64_t n_paths = 0, n_rows = 0;
+  double wu = 0.0, sigma_u = 0.0, min_sigma2 = 0.0;
+  int update_sigma_u = 0;
 };
 
 inline bool mlp_isfeq(double a, double b) { return std::fabs(a - b) < kMlpTrainFeps; }
@@ -193,9 +202,10 @@ inline void mlp_train_opts_default(glia_hmt_mlp_train_opts* o) {
   o->wu = 0.0; o->update_sigma_u = 0; o->sup_batch_size = -1; o->uns_batch_size = -1; o->balance_sup_batch = 0; o->alt_su = 0;
 }
 // What this library does not train (message, or empty), then what no trainer can run (message, or empty).
-inline std::string mlp_train_unsupported(const glia_hmt_mlp_train_opts& o) {
-  if (!mlp_isfeq(o.wu, 0.0)) return "mlp_train: the unsupervised term (wu != 0; --uo, --uf, --wu) is not supported";
-  if (o.update_sigma_u) return "mlp_train: update_sigma_u (--usu) belongs to the unsupervised term, which is not supported";
+// with_u: the caller is the trainer that has the unsupervised term (sshmt_paths.hpp)
+inline std::string mlp_train_unsupported(const glia_hmt_mlp_train_opts& o, bool with_u = false) {
+  if (!with_u && !mlp_isfeq(o.wu, 0.0)) return "mlp_train: the unsupervised term (wu != 0; --uo, --uf, --wu) is not supported";
+  if (!with_u && o.update_sigma_u) return "mlp_train: update_sigma_u (--usu) belongs to the unsupervised term, which is not supported";
   if (o.sup_batch_size > 0) return "mlp_train: sup_batch_size (--bss): batch samplers are not supported";
   if (o.uns_batch_size > 0) return "mlp_train: uns_batch_size (--bsu): batch samplers are not supported";
   if (o.balance_sup_batch) return "mlp_train: balance_sup_batch (--bb): batch samplers are not supported";
@@ -204,9 +214,10 @@ inline std::string mlp_train_unsupported(const glia_hmt_mlp_train_opts& o) {
     return "mlp_train: more than " + std::to_string(kMlpTrainMaxHidden) + " units in a hidden layer are not supported";
   return std::string();
 }
-inline std::string mlp_train_bad_opts(const glia_hmt_mlp_train_opts& o) {
+inline std::string mlp_train_bad_opts(const glia_hmt_mlp_train_opts& o, bool with_u = false) {
   if (o.n1 < 0 || o.n2 < 0 || (o.n1 == 0) != (o.n2 == 0)) return "mlp_train: hidden sizes must both be positive (or both 0: the logsig model)";
-  if (mlp_isfeq(o.wr, 0.0) && mlp_isfeq(o.ws, 0.0)) return "mlp_train: wr and ws are both 0: no term of the energy is on";
+  if (with_u && mlp_isfeq(o.wr, 0.0) && mlp_isfeq(o.ws, 0.0) && mlp_isfeq(o.wu, 0.0)) return "sshmt_train: wr, wu and ws are all 0: no term of the energy is on";
+  if (!with_u && mlp_isfeq(o.wr, 0.0) && mlp_isfeq(o.ws, 0.0)) return "mlp_train: wr and ws are both 0: no term of the energy is on";
   if (!mlp_isfeq(o.ws, 0.0) && o.sigma_s == 0.0 && !o.update_sigma_s) return "mlp_train: sigma_s is 0 and update_sigma_s is off: the supervised term divides by sigma^2";
   if (o.optimizer < 1 || o.optimizer > 3) return "Error: unsupported optimizer type...";
   if (o.max_iterations < 0 || o.n_sigma_updates < 0) return "mlp_train: max_iterations and n_sigma_updates must not be negative";
@@ -217,9 +228,15 @@ inline std::string mlp_train_bad_opts(const glia_hmt_mlp_train_opts& o) {
 }
 
 // The trainer.  w: the initial weights, the final ones on return; n: labelled rows.  Returns the evaluator's code if it fails.
-inline int mlp_train_run(const glia_hmt_mlp_train_opts& o, int64_t n, std::vector<double>& w, MlpTrainEval& ev, MlpTrainResult* R) {
+// U (optional): the unsupervised term; it is off without a path (sshmt/input.hxx:120-121).  The terms enter fx and g in the order
+// regulariser, unsupervised, supervised (type/energy_function.hxx:164-230); without U not one operation differs from the supervised trainer.
+inline int mlp_train_run(const glia_hmt_mlp_train_opts& o, int64_t n, std::vector<double>& w, MlpTrainEval& ev, MlpTrainResult* R,
+                         const MlpTrainUns* U = nullptr) {
   const long long d = (long long)w.size();
   const bool use_r = !mlp_isfeq(o.wr, 0.0), use_s = !mlp_isfeq(o.ws, 0.0);
+  const bool use_u = U && U->ev && U->n_paths > 0 && !mlp_isfeq(U->wu, 0.0);
+  double sigma_u2 = U ? U->sigma_u * U->sigma_u : 0.0;
+  std::vector<double> gu(use_u ? (size_t)w.size() : 0);
   const double min_step = 1e-10, grad_tol = 1e-16, fixed_decay = 0.5, mu = 0.5, beta1 = 0.5, beta2 = 0.9, adam_eps = 1e-8;   // alg/gd.hxx:19-28,289,347-349
   double sigma2 = o.sigma_s * o.sigma_s;
   std::vector<double> g((size_t)d), gs((size_t)d), backup, om((size_t)d), ov((size_t)d);
@@ -227,13 +244,18 @@ inline int mlp_train_run(const glia_hmt_mlp_train_opts& o, int64_t n, std::vecto
 
   // type/energy_function.hxx:164-230 with alg/function.hxx:72-77,257-267
   auto energy = [&](bool want_grad, double* fx) -> int {
-    double L = 0.0;
+    double L = 0.0, Lu = 0.0;
+    if (use_u && (rc = U->ev->eval(w.data(), &Lu, want_grad ? gu.data() : nullptr))) return rc;
     if (use_s && (rc = ev.eval(w.data(), &L, want_grad ? gs.data() : nullptr))) return rc;
     double ret = 0.0;
     if (want_grad) for (long long p = 0; p < d; ++p) g[p] = 0.0;
     if (use_r) {
       ret = ret + o.wr * (mlp_sqnorm(w.data(), d) / 2.0);
       if (want_grad) for (long long p = 0; p < d; ++p) g[p] = g[p] + (mlp_isfeq(o.wr, 1.0) ? w[p] : o.wr * w[p]);
+    }
+    if (use_u) {
+      ret = ret + U->wu * ((0.5 * Lu) / sigma_u2 + ((double)U->n_paths * std::log(sigma_u2)) / 2.0);
+      if (want_grad) for (long long p = 0; p < d; ++p) { const double t = gu[p] / sigma_u2; g[p] = g[p] + (mlp_isfeq(U->wu, 1.0) ? t : U->wu * t); }
     }
     if (use_s) {
       ret = ret + o.ws * ((0.5 * L) / sigma2 + ((double)n * std::log(sigma2)) / 2.0);
@@ -256,7 +278,19 @@ inline int mlp_train_run(const glia_hmt_mlp_train_opts& o, int64_t n, std::vecto
     }
   };
   // sshmt_util.hxx:140-145,188-207: sigma^2 = max(floor, L / n) when it is updated; the evaluated value is recorded either way
-  auto update_sigma = [&]() -> int {
+  // updateSigmaU (sshmt_util.hxx:148-185), after updateSigmaS (:210-222): sigma_u^2 = max(floor, L_U / P) when it is updated, and
+  // the evaluated value is then sigma_u^2 itself either way (at the floor by the rule, above it because L_U / P is not negative)
+  auto update_sigma_u = [&]() -> int {
+    if (!use_u) { R->sigma_u2.push_back(sigma_u2); R->sigma_u2_eval.push_back(0.0); return 0; }
+    double Lu = 0.0;
+    if ((rc = U->ev->eval(w.data(), &Lu, nullptr))) return rc;
+    const double v = Lu / (double)U->n_paths;
+    if (U->update_sigma_u) sigma_u2 = mlp_max(U->min_sigma2, v);
+    R->sigma_u2.push_back(sigma_u2);
+    R->sigma_u2_eval.push_back(U->update_sigma_u ? sigma_u2 : mlp_max(0.0, v));
+    return 0;
+  };
+  auto update_sigma_s = [&]() -> int {
     if (!use_s) { R->sigma2.push_back(sigma2); R->sigma2_eval.push_back(0.0); return 0; }
     double L = 0.0;
     if ((rc = ev.eval(w.data(), &L, nullptr))) return rc;
@@ -265,6 +299,10 @@ inline int mlp_train_run(const glia_hmt_mlp_train_opts& o, int64_t n, std::vecto
     R->sigma2.push_back(sigma2);
     R->sigma2_eval.push_back(o.update_sigma_s && sigma2 != o.min_sigma2 ? sigma2 : mlp_max(0.0, v));
     return 0;
+  };
+  auto update_sigma = [&]() -> int {
+    if ((rc = update_sigma_s())) return rc;
+    return update_sigma_u();
   };
   auto record = [&](int round, int t, int kind, double fx, double xx, double gg, double step, int rollbacks) {
     glia_hmt_mlp_train_record r;

@@ -1,0 +1,239 @@
+// glia_amd/csrc/sshmt_paths.hpp -- the merge-path (unsupervised) term of train_sshmt_mlp / train_sshmt_logsig, stated
+// ONCE for the host and the device on top of mlp_backward.hpp.
+//
+// Part 1 (host + device): one path.  A path of n <= kSshmtMaxPath merges has classifier outputs f_0 .. f_{n-1}; the monotonic DNF of
+// alg/dnf.hxx:191-201,234-311 is D = 1 - prod_j F_j with F_j = T_n - c_j, c_j = prod_{i<j} f_i prod_{i>=j} (1 - f_i), j = 0 .. n, the
+// residual e = t_n - D and a_i = dD/df_i (dnf.hxx:270-309).  Every product is a chain from 1.0 in ascending index order, the sum
+// of a_i a chain from +0.0; mlp_mul / mlp_add / mlp_sub, nothing contracted.  T_n = mergeTarget^n and t_n = pathTarget^n come from two
+// tables the host fills once with its own pow (input.hxx:36-39, dnf.hxx:199): the device never calls pow.
+// Part 2 (host): merge_paths, the bounded genMergePaths of hmt/tree_build.hxx:150-180; the two-level reductions -- paths in chunks of
+// kSshmtPathChunk consecutive paths for L_U = sum e_p^2, a row's coefficient c_r the chain of q = e_p a_{p,i} over the (path, slot)
+// pairs that name it in ascending path order, rows in chunks of kMlpTrainChunk for grad_U = -sum_r c_r g_r -- and the host evaluator.
+// The order IS the result.  No parity with Eigen's last bits is possible or claimed.  Host code: -ffp-contract=off.
+#pragma once
+#include "mlp_backward.hpp"
+
+namespace glia {
+
+constexpr int kSshmtMaxPath = 8;        // members of a path <= this: mergeTarget^n leaves the doubles long before a tree's depth
+constexpr int kSshmtPathChunk = 64;     // paths of a chunk of L_U's reduction: part of the definition
+
+struct SshmtTables {                    // [n], n = 1 .. kSshmtMaxPath; [0] unused
+  double T[kSshmtMaxPath + 1], t[kSshmtMaxPath + 1];
+};
+
+// x_kj: column j of dnf.hxx:178-180's matrix, f_k left of the diagonal and 1 - f_k from the diagonal on
+GLIA_MLP_HD double sshmt_x(const double* f, const double* u, int k, int j) { return k < j ? f[k] : u[k]; }
+
+// One path: returns e = t_n - D; q [n] (or NULL) receives q_i = e * a_i.
+GLIA_MLP_HD double sshmt_path(const double* f, int n, double Tn, double tn, double* q) {
+  double u[kSshmtMaxPath], F[kSshmtMaxPath + 1];
+  for (int i = 0; i < n; ++i) u[i] = mlp_sub(1.0, f[i]);
+  double P = 1.0;
+  for (int j = 0; j <= n; ++j) {
+    double c = 1.0;
+    for (int i = 0; i < n; ++i) c = mlp_mul(c, sshmt_x(f, u, i, j));
+    F[j] = mlp_sub(Tn, c);
+    P = mlp_mul(P, F[j]);
+  }
+  const double e = mlp_sub(tn, mlp_sub(1.0, P));
+  if (!q) return e;
+  double EC[kSshmtMaxPath + 1];
+  for (int j = 0; j <= n; ++j) {
+    double c = 1.0;
+    for (int k = 0; k <= n; ++k) if (k != j) c = mlp_mul(c, F[k]);
+    EC[j] = c;
+  }
+  for (int i = 0; i < n; ++i) {
+    double a = 0.0;
+    for (int j = 0; j <= n; ++j) {
+      double m = 1.0;
+      for (int k = 0; k < n; ++k) if (k != i) m = mlp_mul(m, sshmt_x(f, u, k, j));
+      a = mlp_add(a, mlp_mul(EC[j], j <= i ? -m : m));      // dnf.hxx:306: the columns up to the diagonal change sign
+    }
+    q[i] = mlp_mul(e, a);
+  }
+  return e;
+}
+
+}  // namespace glia
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// host only from here
+#include <unordered_map>
+#include <unordered_set>
+
+#include "dense_order.hpp"
+
+namespace glia {
+
+inline std::string sshmt_bad_lengths(int max_len, int min_len) {
+  if (max_len < 0) return "merge_paths: max_path_length < 0 (paths of unbounded length) is not supported";
+  if (max_len > kSshmtMaxPath) return "merge_paths: max_path_length above " + std::to_string(kSshmtMaxPath) + " is not supported";
+  if (min_len < 1 || min_len > max_len) return "merge_paths: 1 <= min_path_length <= max_path_length does not hold";
+  return std::string();
+}
+
+// order [n][3] = (key, key, created key), validated by dense_order over its own leaves (the operands no merge creates): an operand that
+// is created later or was merged before, a created key seen before.  Returns the first bad merge or -1.
+inline int64_t sshmt_check_order(const uint32_t* order, int64_t n) {
+  std::unordered_set<uint32_t> created;
+  for (int64_t i = 0; i < n; ++i) created.insert(order[3 * i + 2]);
+  std::vector<uint32_t> leaves;
+  for (int64_t i = 0; i < n; ++i)
+    for (int s = 0; s < 2; ++s) if (!created.count(order[3 * i + s])) leaves.push_back(order[3 * i + s]);
+  std::sort(leaves.begin(), leaves.end());
+  leaves.erase(std::unique(leaves.begin(), leaves.end()), leaves.end());      // a leaf merged twice is an operand merged before
+  std::vector<uint32_t> dense;
+  const DenseOrderResult r = dense_order(leaves.data(), (int64_t)leaves.size(), order, n, &dense);
+  return r.error == kDenseOrderOk ? -1 : r.merge;
+}
+
+// hmt/tree_build.hxx:150-180.  For every merge i ascending a path starts at i and follows the merge in which the current merge's
+// created key is an operand, until it has max_len members or reaches a root; kept with exactly max_len members, or with at least
+// min_len when neither operand of merge i is a created key.  CSR: offsets [P + 1], members (merge indices + row0), bottom-up.
+inline void merge_paths(const uint32_t* order, int64_t n, int max_len, int min_len, int64_t row0, std::vector<int64_t>* offsets,
+                        std::vector<int64_t>* members) {
+  std::unordered_map<uint32_t, int64_t> child_of, created;
+  child_of.reserve((size_t)n * 4); created.reserve((size_t)n * 2);
+  for (int64_t i = 0; i < n; ++i) { child_of[order[3 * i]] = i; child_of[order[3 * i + 1]] = i; created[order[3 * i + 2]] = i; }
+  if (offsets->empty()) offsets->push_back(0);
+  int64_t path[kSshmtMaxPath];
+  for (int64_t i = 0; i < n; ++i) {
+    int len = 0;
+    path[len++] = i;
+    auto it = child_of.find(order[3 * i + 2]);
+    while (it != child_of.end() && len < max_len) {
+      path[len++] = it->second;
+      it = child_of.find(order[3 * it->second + 2]);
+    }
+    if (len == max_len || (len >= min_len && !created.count(order[3 * i]) && !created.count(order[3 * i + 1]))) {
+      for (int k = 0; k < len; ++k) members->push_back(path[k] + row0);
+      offsets->push_back((int64_t)members->size());
+    }
+  }
+}
+
+// row -> the (path, slot) pairs that name it, as indices path * kSshmtMaxPath + slot into q, ascending (so: paths ascending)
+inline void sshmt_incidence(const std::vector<int64_t>& offsets, const std::vector<int64_t>& members, int64_t n_rows,
+                            std::vector<int64_t>* inc_off, std::vector<uint32_t>* inc) {
+  const int64_t P = (int64_t)offsets.size() - 1;
+  inc_off->assign((size_t)n_rows + 1, 0);
+  for (int64_t r : members) (*inc_off)[(size_t)r + 1] += 1;
+  for (int64_t r = 0; r < n_rows; ++r) (*inc_off)[(size_t)r + 1] += (*inc_off)[(size_t)r];
+  inc->assign(members.size(), 0);
+  std::vector<int64_t> fill(inc_off->begin(), inc_off->end() - 1);
+  for (int64_t p = 0; p < P; ++p)
+    for (int64_t k = offsets[p]; k < offsets[p + 1]; ++k)
+      (*inc)[(size_t)fill[(size_t)members[k]]++] = (uint32_t)(p * kSshmtMaxPath + (k - offsets[p]));
+}
+
+inline void sshmt_fill_tables(double merge_target, double path_target, SshmtTables* tb) {
+  tb->T[0] = tb->t[0] = 1.0;
+  for (int n = 1; n <= kSshmtMaxPath; ++n) { tb->T[n] = std::pow(merge_target, n); tb->t[n] = std::pow(path_target, n); }
+}
+
+// what the evaluators share: the prepared unlabelled rows of all blocks, the paths, the incidence lists, the tables
+struct SshmtInput {
+  int D = 0;
+  int64_t n_rows = 0;
+  std::vector<double> X;                        // [n_rows][D]
+  std::vector<int64_t> offsets{0}, members;     // paths
+  std::vector<int64_t> inc_off;
+  std::vector<uint32_t> inc;
+  SshmtTables tb;
+  int64_t n_paths() const { return (int64_t)offsets.size() - 1; }
+};
+
+// the logit of a prepared row with the training header's layout (mlp_loss_grad_host's forward), then the host's sigmoid
+inline double sshmt_forward_row_host(const MlpWeights& m, const double* x, double* a, double* b) {
+  double h3;
+  if (m.n1 == 0) h3 = mlp_unit(m.w2, m.D, 1, 0, MlpRow{x});
+  else {
+    for (int k = 0; k < m.n1; ++k) a[k] = mlp_unit(m.w0, m.D, 1, k, MlpRow{x});
+    for (int k = 0; k < m.n2; ++k) b[k] = mlp_unit(m.w1, m.n1 + 1, 1, k, MlpActs{a, m.n1, 1});
+    h3 = mlp_unit(m.w2, m.n2 + 1, 1, 0, MlpActs{b, m.n2, 1});
+  }
+  return mlp_train_sigmoid(h3);
+}
+
+// L_U = sum e_p^2 and, when grad != NULL, grad_U = -sum_r c_r g_r, by the orders above.
+inline void sshmt_loss_grad_host(const double* w, int n1, int n2, const SshmtInput& in, double* L, double* grad) {
+  const int D = in.D;
+  const MlpWeights m = mlp_train_weights(w, D, n1, n2);
+  const long long d = mlp_train_n_weights(D, n1, n2);
+  const int64_t N = in.n_rows, P = in.n_paths();
+  const int C = kMlpTrainChunk;
+  std::vector<double> h1((size_t)C * (n1 + 1)), h2((size_t)C * (n2 + 1)), dh1((size_t)C * (n1 + 1)), dh2((size_t)C * (n2 + 1)), dh3(C);
+  std::vector<double> f((size_t)N), e((size_t)P), q(grad ? (size_t)P * kSshmtMaxPath : 0), c(grad ? (size_t)N : 0);
+  std::vector<uint8_t> named(grad ? (size_t)N : 0, 0);
+  for (int64_t r = 0; r < N; ++r) f[(size_t)r] = sshmt_forward_row_host(m, &in.X[(size_t)r * D], h1.data(), h2.data());
+  double Lsum = 0.0;
+  for (int64_t p0 = 0; p0 < P; p0 += kSshmtPathChunk) {
+    double Lc = 0.0;
+    for (int64_t p = p0; p < P && p < p0 + kSshmtPathChunk; ++p) {
+      const int n = (int)(in.offsets[p + 1] - in.offsets[p]);
+      double fp[kSshmtMaxPath];
+      for (int i = 0; i < n; ++i) fp[i] = f[(size_t)in.members[in.offsets[p] + i]];
+      e[(size_t)p] = sshmt_path(fp, n, in.tb.T[n], in.tb.t[n], grad ? &q[(size_t)p * kSshmtMaxPath] : nullptr);
+      Lc = mlp_add(Lc, mlp_mul(e[(size_t)p], e[(size_t)p]));
+    }
+    Lsum = mlp_add(Lsum, Lc);
+  }
+  *L = Lsum;
+  if (!grad) return;
+  for (int64_t r = 0; r < N; ++r) {
+    double acc = 0.0;
+    for (int64_t k = in.inc_off[r]; k < in.inc_off[r + 1]; ++k) {
+      if (mlp_feq0(e[in.inc[k] / kSshmtMaxPath])) continue;      // dnf's caller skips the path (alg/function.hxx:195)
+      acc = mlp_add(acc, q[in.inc[k]]);
+      named[(size_t)r] = 1;
+    }
+    c[(size_t)r] = acc;
+  }
+  for (long long p = 0; p < d; ++p) grad[p] = 0.0;
+  for (int64_t r0 = 0; r0 < N; r0 += C) {
+    const int nr = (int)(N - r0 < C ? N - r0 : C);
+    for (int r = 0; r < nr; ++r) {
+      if (!named[(size_t)(r0 + r)]) continue;
+      double *a = &h1[(size_t)r * (n1 + 1)], *b = &h2[(size_t)r * (n2 + 1)];
+      dh3[r] = mlp_dh3(sshmt_forward_row_host(m, &in.X[(size_t)(r0 + r) * D], a, b));
+      double *da = &dh1[(size_t)r * (n1 + 1)], *db = &dh2[(size_t)r * (n2 + 1)];
+      for (int k = 0; k < n2; ++k) db[k] = mlp_dh2(m, k, b[k], dh3[r]);
+      for (int j = 0; j < n1; ++j) da[j] = mlp_dh1(m, j, a[j], db, 1);
+    }
+    for (long long p = 0; p < d; ++p) {
+      double S = 0.0;
+      for (int r = 0; r < nr; ++r) {
+        if (!named[(size_t)(r0 + r)]) continue;
+        const double g = mlp_grad_elem(m, p, MlpRow{&in.X[(size_t)(r0 + r) * D]}, &h1[(size_t)r * (n1 + 1)], &h2[(size_t)r * (n2 + 1)],
+                                       &dh1[(size_t)r * (n1 + 1)], &dh2[(size_t)r * (n2 + 1)], dh3[r], 1);
+        S = mlp_sub(S, mlp_mul(g, c[(size_t)(r0 + r)]));
+      }
+      grad[p] = mlp_add(grad[p], S);
+    }
+  }
+}
+
+struct SshmtHostEval : MlpTrainEval {
+  int n1 = 0, n2 = 0;
+  const SshmtInput* in = nullptr;
+  int eval(const double* w, double* L, double* grad) override { sshmt_loss_grad_host(w, n1, n2, *in, L, grad); return 0; }
+};
+
+// glia_hmt_sshmt_train_opts_default: main_train_sshmt_mlp.cxx:20-53
+inline void sshmt_train_opts_default(glia_hmt_sshmt_train_opts* o) {
+  mlp_train_opts_default(&o->base);
+  o->sigma_u = 0.0; o->merge_target = 0.95; o->path_target = 1.0; o->max_path_length = 3; o->min_path_length = 2;
+}
+inline std::string sshmt_train_bad_opts(const glia_hmt_sshmt_train_opts& o) {
+  const std::string bad = mlp_train_bad_opts(o.base, true);
+  if (!bad.empty()) return bad;
+  if (!std::isfinite(o.base.wu) || !std::isfinite(o.sigma_u) || !std::isfinite(o.merge_target) || !std::isfinite(o.path_target))
+    return "sshmt_train: wu, sigma_u, merge_target or path_target is not finite";
+  if (!mlp_isfeq(o.base.wu, 0.0) && o.sigma_u == 0.0 && !o.base.update_sigma_u)
+    return "sshmt_train: sigma_u is 0 and update_sigma_u is off: the unsupervised term divides by sigma_u^2";
+  return std::string();
+}
+
+}  // namespace glia

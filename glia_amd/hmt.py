@@ -722,7 +722,7 @@ def mlp_predict_host(weights, n1, n2, rows, mn=None, mx=None, distributor_args=N
 
 class MLPTrainOpts(C.Structure):
     """glia_hmt_mlp_train_opts: the options of train_sshmt_mlp's supervised part (sshmt/main_train_sshmt_mlp.cxx:20-47); the fields
-    after seed ask for what is not built and are refused unless they hold their defaults"""
+    after seed are refused by train_mlp unless they hold their defaults; train_sshmt honours wu and update_sigma_u"""
     _fields_ = [("n1", C.c_int), ("n2", C.c_int), ("wr", C.c_double), ("ws", C.c_double), ("sigma_s", C.c_double), ("update_sigma_s", C.c_int),
                 ("optimizer", C.c_int), ("step", C.c_double), ("step_decay", C.c_double), ("fixed_step_decay_iterations", C.c_int),
                 ("sigma_update_step_period", C.c_int), ("max_iterations", C.c_int), ("n_sigma_updates", C.c_int), ("pos_target", C.c_double),
@@ -782,6 +782,12 @@ class MLPModel:
         _check(lib().glia_hmt_mlp_model_trace(self.h, _np(self.trace) if n_trace else None))
         self.sigma2 = np.zeros(n_sigma); self.sigma2_eval = np.zeros(n_sigma)
         _check(lib().glia_hmt_mlp_model_sigmas(self.h, _np(self.sigma2), _np(self.sigma2_eval)))
+        # the merge-path term's (train_sshmt): sigma_u^2 per sigma update (zeros while the term is off), its paths and unlabelled rows
+        self.sigma_u2 = np.zeros(n_sigma); self.sigma_u2_eval = np.zeros(n_sigma)
+        _check(lib().glia_hmt_mlp_model_sigmas_u(self.h, _np(self.sigma_u2), _np(self.sigma_u2_eval)))
+        v = (C.c_int64(), C.c_int64())
+        _check(lib().glia_hmt_mlp_model_paths(self.h, *[C.byref(x) for x in v]))
+        self.n_paths, self.n_uns_rows = (x.value for x in v)
 
     def weights(self, round=-1):
         w = np.empty(self.n_weights, np.float64)
@@ -854,6 +860,94 @@ def last_mlp_train_timing(ctx):
     t = MLPTrainTiming()
     _check(lib().glia_hmt_last_mlp_train_timing(ctx.h, C.byref(t)))
     return {k: getattr(t, k) for k, _ in MLPTrainTiming._fields_}
+
+
+class SSHMTTrainOpts(C.Structure):
+    """glia_hmt_sshmt_train_opts: MLPTrainOpts (wu and update_sigma_u honoured) and the merge-path term's own options
+    (sshmt/main_train_sshmt_mlp.cxx:41-53)"""
+    _fields_ = [("base", MLPTrainOpts), ("sigma_u", C.c_double), ("merge_target", C.c_double), ("path_target", C.c_double),
+                ("max_path_length", C.c_int), ("min_path_length", C.c_int)]
+
+
+class SSHMTBlock(C.Structure):
+    _fields_ = [("rows", C.c_void_p), ("order", C.c_void_p), ("n_merges", C.c_int64)]      # glia_hmt_sshmt_block
+
+
+class SSHMTTrainTiming(C.Structure):
+    _fields_ = [("sup", MLPTrainTiming)] + \
+               [(k, C.c_double) for k in ("ms_u_upload", "ms_u_weights", "ms_u_forward", "ms_u_paths", "ms_u_gather", "ms_u_chunk", "ms_u_fold",
+                                          "ms_u_readback")] + \
+               [(k, C.c_int64) for k in ("u_evals", "u_grad_evals", "n_paths", "n_uns_rows")] + [("u_device_bytes", C.c_uint64)]
+
+
+def merge_paths(order, max_len=3, min_len=2):
+    """glia_hmt_merge_paths: the merge paths of an order [n, 3] (hmt/tree_build.hxx:150-180, the bounded genMergePaths) as a list of
+    int64 arrays of merge indices, bottom-up, by ascending first member.  Host-only."""
+    o = np.ascontiguousarray(order, dtype=np.uint32).reshape(-1, 3)
+    n_paths, n_members = C.c_int64(0), C.c_int64(0)
+    args = (_np(o) if len(o) else None, C.c_int64(len(o)), C.c_int(max_len), C.c_int(min_len), C.byref(n_paths), C.byref(n_members))
+    _check(lib().glia_hmt_merge_paths(*args, None, None))
+    off = np.zeros(n_paths.value + 1, np.int64); mem = np.zeros(max(n_members.value, 1), np.int64)
+    _check(lib().glia_hmt_merge_paths(*args, _np(off), _np(mem)))
+    return [mem[off[i]:off[i + 1]].copy() for i in range(n_paths.value)]
+
+
+def train_sshmt(ctx, rows, labels, unlabelled=(), n1=10, n2=10, minmax=None, init=None, **opts):
+    """train_sshmt_mlp / train_sshmt_logsig with the merge-path term.  rows / labels as train_mlp takes them; both may be
+    None when ws is off.  unlabelled: [(rows_u [n_i, dim], order_u [n_i, 3]), ...], row k of a block = merge k of its order.  Options:
+    the fields of MLPTrainOpts (wu and update_sigma_u included) and sigma_u, merge_target, path_target, max_path_length,
+    min_path_length.  ctx = None runs the definition on one host thread (train_sshmt_host)."""
+    blocks = [(np.ascontiguousarray(r, dtype=np.float64), np.ascontiguousarray(o, dtype=np.uint32).reshape(-1, 3)) for r, o in unlabelled]
+    dim = blocks[0][0].shape[1] if rows is None else np.asarray(rows).shape[1]
+    rows = np.zeros((0, dim)) if rows is None else np.ascontiguousarray(rows, dtype=np.float64)
+    labels = np.zeros(0, np.int32) if labels is None else np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+    assert rows.ndim == 2 and labels.shape[0] == rows.shape[0]
+    for r, o in blocks:
+        if r.ndim != 2 or r.shape[1] != dim or r.shape[0] != o.shape[0]:
+            raise HmtError(ERR_ARG, "train_sshmt: a block needs one row of %d columns per merge" % dim)
+    o = SSHMTTrainOpts()
+    lib().glia_hmt_sshmt_train_opts_default(C.byref(o))
+    o.base.n1, o.base.n2 = n1, n2
+    for k, v in opts.items():
+        if k in dict(MLPTrainOpts._fields_):
+            setattr(o.base, k, v)
+        elif k in dict(SSHMTTrainOpts._fields_) and k != "base":
+            setattr(o, k, v)
+        else:
+            raise TypeError("train_sshmt: unknown option " + k)
+    mn = mx = None
+    if minmax is not None:
+        mn = np.ascontiguousarray(minmax[0], dtype=np.float64); mx = np.ascontiguousarray(minmax[1], dtype=np.float64)
+        if min(mn.size, mx.size) < dim:
+            raise HmtError(ERR_ARG, "train_sshmt: fewer min/max entries than columns")
+    if init is not None:
+        init = np.ascontiguousarray(init, dtype=np.float64)
+        D = dim + 1
+        if init.size != (D * n1 + (n1 + 1) * n2 + n2 + 1 if n1 else D):
+            raise HmtError(ERR_ARG, "train_sshmt: %d initial weights do not fit the model" % init.size)
+    arr = (SSHMTBlock * max(len(blocks), 1))()
+    for i, (r, od) in enumerate(blocks):
+        arr[i] = SSHMTBlock(r.ctypes.data if len(r) else None, od.ctypes.data if len(od) else None, len(od))
+    h = C.c_void_p()
+    _check(lib().glia_hmt_sshmt_train(ctx.h if ctx is not None else None, _np(rows) if len(rows) else None, C.c_int64(rows.shape[0]), C.c_int(dim),
+                                      _np(labels) if len(labels) else None, arr, C.c_int(len(blocks)), C.byref(o),
+                                      _np(mn) if mn is not None else None, _np(mx) if mx is not None else None,
+                                      _np(init) if init is not None else None, C.byref(h)))
+    return MLPModel(h, n1, n2)
+
+
+def train_sshmt_host(rows, labels, unlabelled=(), n1=10, n2=10, minmax=None, init=None, **opts):
+    """glia_hmt_sshmt_train_host: the definition of DESIGN 3.15 on one host thread; no GPU, no context"""
+    return train_sshmt(None, rows, labels, unlabelled, n1, n2, minmax, init, **opts)
+
+
+def last_sshmt_train_timing(ctx):
+    """the last train_sshmt call of the context: the supervised evaluator's fields under "sup", then the merge-path term's stages"""
+    t = SSHMTTrainTiming()
+    _check(lib().glia_hmt_last_sshmt_train_timing(ctx.h, C.byref(t)))
+    out = {k: getattr(t, k) for k, _ in SSHMTTrainTiming._fields_ if k != "sup"}
+    out["sup"] = {k: getattr(t.sup, k) for k, _ in MLPTrainTiming._fields_}
+    return out
 
 
 class TrainOpts(C.Structure):

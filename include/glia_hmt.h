@@ -400,8 +400,8 @@ int glia_hmt_last_forest_train_timing(const glia_hmt_ctx* ctx, glia_hmt_forest_t
  * (type/energy_function.hxx:164-230, alg/function.hxx:171-267), the vanilla / Adam / momentum updates with a fixed or an adaptive step
  * (alg/gd.hxx) and the sigma rule and outer loop of sshmt_util.hxx:140-207.  The arithmetic is this library's own definition
  * (glia_amd/csrc/mlp_backward.hpp): no parity with Eigen's sums, Boost's Gaussian or the OpenMP partial sums is
- * possible or claimed.  The unsupervised term, batch samplers and altSU are not built: an opts struct that asks for them is
- * GLIA_HMT_ERR_UNSUPPORTED with a message naming the field.  sigma^2 is updated only when update_sigma_s is set (the reference's tool
+ * possible or claimed.  The unsupervised term is glia_hmt_sshmt_train's, below; batch samplers and altSU are not built: an opts struct
+ * that asks for any of them here is GLIA_HMT_ERR_UNSUPPORTED with a message naming the field.  sigma^2 is updated only when update_sigma_s is set (the reference's tool
  * also updates it whenever it runs with --v 0).
  * glia_hmt_mlp_train_opts: the tool's options and defaults; min_sigma2 is the floor the tool passes (0.0); seed keys the initial
  * weights of an MLP (a logsig model starts at zeros; h_init, when given, takes precedence over both). */
@@ -419,7 +419,7 @@ typedef struct {
   double pos_target, neg_target;     /* 0.05, 0.95 */
   double min_sigma2;                 /* 0.0 */
   uint64_t seed;                     /* 0 */
-  /* not supported; anything but the defaults is refused */
+  /* glia_hmt_mlp_train refuses anything but the defaults; glia_hmt_sshmt_train honours wu and update_sigma_u and refuses the rest */
   double wu;                         /* --wu 0 */
   int update_sigma_u;                /* --usu 0 */
   int sup_batch_size, uns_batch_size;/* --bss -1, --bsu -1 */
@@ -473,6 +473,52 @@ typedef struct {
   uint64_t device_bytes;
 } glia_hmt_mlp_train_timing;
 int glia_hmt_last_mlp_train_timing(const glia_hmt_ctx* ctx, glia_hmt_mlp_train_timing* out);
+
+/* ---- training with the merge-path (unsupervised) term: train_sshmt_mlp / train_sshmt_logsig ----------------
+ * The energy of glia_hmt_mlp_train plus wu * (0.5 * L_U / sigma_u^2 + P * log(sigma_u^2) / 2) between the regulariser and the supervised
+ * term (type/energy_function.hxx:164-230).  Each block is one unlabelled volume: a merge order and its feature rows, row i = merge i
+ * (sshmt/sshmt_util.hxx:30-52).  The bounded genMergePaths (hmt/tree_build.hxx:150-180) lists P merge paths over all blocks; a path of
+ * n rows with classifier outputs f_0 .. f_{n-1} has the monotonic DNF D = 1 - prod_{j=0..n} (merge_target^n - prod_{i<j} f_i
+ * prod_{i>=j} (1 - f_i)) (alg/dnf.hxx:126-326), the residual e = path_target^n - D (sshmt/input.hxx:36-39) and L_U = sum e^2
+ * (alg/function.hxx:171-267).  sigma_u^2 = max(min_sigma2, L_U / P) under update_sigma_u, updated after sigma_s^2
+ * (sshmt_util.hxx:148-222).  Without a single path the term is off (input.hxx:120-121).  The arithmetic is this library's own
+ * definition (glia_amd/csrc/sshmt_paths.hpp).  Batch samplers and alt_su stay refused by name. */
+typedef struct { const double* rows; const uint32_t* order; int64_t n_merges; } glia_hmt_sshmt_block;  /* rows [n_merges][dim], order [n_merges][3] */
+typedef struct {
+  glia_hmt_mlp_train_opts base;          /* wu and update_sigma_u are honoured HERE; the batch fields and alt_su stay refused */
+  double sigma_u;                        /* --su 0 */
+  double merge_target, path_target;      /* 0.95, 1.0 (main_train_sshmt_mlp.cxx:41-53) */
+  int max_path_length, min_path_length;  /* 3, 2; 1 <= min <= max <= 8 */
+} glia_hmt_sshmt_train_opts;
+void glia_hmt_sshmt_train_opts_default(glia_hmt_sshmt_train_opts* opts);
+/* As glia_hmt_mlp_train, with the unlabelled blocks.  Labelled rows may be absent (n_rows == 0) when base.ws is off.  The same min/max
+ * table rescales labelled and unlabelled rows.  GLIA_HMT_ERR_ARG: a block without rows or order, an invalid order (an operand that was
+ * merged before or is created later, a created key seen before), a row that is not finite, no term on, wu on with sigma_u == 0 and no
+ * update_sigma_u.  GLIA_HMT_ERR_UNSUPPORTED: max_path_length < 0 (unbounded paths) or > 8, the batch fields, the limits of
+ * glia_hmt_mlp_train, a memory plan beyond 85 % of the free device memory.  ctx NULL: glia_hmt_sshmt_train_host. */
+int glia_hmt_sshmt_train(glia_hmt_ctx* ctx, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels,
+                         const glia_hmt_sshmt_block* blocks, int n_blocks, const glia_hmt_sshmt_train_opts* opts, const double* h_min,
+                         const double* h_max, const double* h_init, glia_hmt_mlp_model** out);
+int glia_hmt_sshmt_train_host(const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_sshmt_block* blocks,
+                              int n_blocks, const glia_hmt_sshmt_train_opts* opts, const double* h_min, const double* h_max,
+                              const double* h_init, glia_hmt_mlp_model** out);
+/* Host-only: the merge paths of one order (hmt/tree_build.hxx:150-180) as CSR.  Call with offsets == members == NULL for *n_paths and
+ * *n_members, then with offsets [n_paths + 1] and members [n_members] (merge indices, bottom-up). */
+int glia_hmt_merge_paths(const uint32_t* h_order, int64_t n_merges, int max_len, int min_len, int64_t* n_paths, int64_t* n_members,
+                         int64_t* offsets, int64_t* members);
+/* sigma_u^2 and its evaluated value after every sigma update (n_sigma entries each; 0.0 while the term is off) */
+int glia_hmt_mlp_model_sigmas_u(const glia_hmt_mlp_model* model, double* h_sigma2, double* h_sigma2_eval);
+int glia_hmt_mlp_model_paths(const glia_hmt_mlp_model* model, int64_t* n_paths, int64_t* n_uns_rows);
+/* the last glia_hmt_sshmt_train call of this context: the supervised evaluator's fields, then the unsupervised evaluator's stages */
+typedef struct {
+  glia_hmt_mlp_train_timing sup;
+  double ms_u_upload;                /* unlabelled rows, paths and incidence lists to the device */
+  double ms_u_weights, ms_u_forward, ms_u_paths, ms_u_gather, ms_u_chunk, ms_u_fold, ms_u_readback;
+  int64_t u_evals, u_grad_evals;
+  int64_t n_paths, n_uns_rows;
+  uint64_t u_device_bytes;
+} glia_hmt_sshmt_train_timing;
+int glia_hmt_last_sshmt_train_timing(const glia_hmt_ctx* ctx, glia_hmt_sshmt_train_timing* out);
 
 /* Length of one feature vector for the configuration the rag was built with (BoundaryClassificationFeats::dim,
  * hmt/bc_feat.hxx:225-230; or selectFeatures' length with --simpf). */
