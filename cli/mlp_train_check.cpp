@@ -50,7 +50,7 @@ static uint64_t run_case(const Case& c, MlpTrainResult* R) {
   MlpTrainHostEval ev;
   ev.D = D; ev.n1 = c.n1; ev.n2 = c.n2; ev.X = X.data(); ev.t = t.data(); ev.n = (int64_t)t.size();
   R->D = D; R->n1 = c.n1; R->n2 = c.n2; R->n_used = ev.n;
-  EXPECT(mlp_train_run(o, ev.n, w, ev, R) == 0);
+  EXPECT(mlp_train_run(o, ev.n, w, &ev, R) == 0);
   uint64_t h = 0xCBF29CE484222325ull;
   for (const auto& rw : R->round_w) h = fnv(h, rw.data(), sizeof(double) * rw.size());
   for (const auto& r : R->trace) { const double f[5] = {r.fx, r.xnorm, r.gnorm, r.step, r.sigma2}; h = fnv(h, f, sizeof(f)); }

@@ -90,7 +90,7 @@ static uint64_t run_case(const Case& c, MlpTrainResult* R) {
   MlpTrainUns U;
   U.ev = &eu; U.n_paths = in.n_paths(); U.n_rows = in.n_rows; U.wu = o.wu; U.sigma_u = so.sigma_u; U.min_sigma2 = o.min_sigma2; U.update_sigma_u = o.update_sigma_u;
   R->D = D; R->n1 = c.n1; R->n2 = c.n2; R->n_used = ev.n; R->n_paths = U.n_paths; R->n_uns_rows = U.n_rows;
-  EXPECT(mlp_train_run(o, ev.n, w, ev, R, &U) == 0);
+  EXPECT(mlp_train_run(o, ev.n, w, &ev, R, &U) == 0);
   uint64_t h = 0xCBF29CE484222325ull;
   for (const auto& rw : R->round_w) h = fnv(h, rw.data(), sizeof(double) * rw.size());
   for (const auto& r : R->trace) { const double f[5] = {r.fx, r.xnorm, r.gnorm, r.step, r.sigma2}; h = fnv(h, f, sizeof(f)); }

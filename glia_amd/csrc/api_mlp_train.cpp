@@ -1,5 +1,5 @@
 // glia_amd/csrc/api_mlp_train.cpp -- C ABI: training the MLP / logsig classifier (mlp_backward.hpp: the definition and the trainer;
-// mlp_train.hip: the device evaluator), without and with the merge-path term (sshmt_paths.hpp; sshmt_train.hip).
+// mlp_train.hip: the device evaluator), without and with the merge-path term (sshmt_paths.hpp; sshmt_train.hip): one path through both.
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -14,72 +14,15 @@ struct glia_hmt_mlp_model {
 
 namespace {
 
-struct DeviceEval : MlpTrainEval {
-  MlpTrainDevice* st = nullptr;
-  ~DeviceEval() override { mlp_train_device_free(st); }
-  int eval(const double* w, double* L, double* grad) override { return mlp_train_device_eval(st, w, L, grad); }
-};
-
-struct DeviceEvalU : MlpTrainEval {
-  SshmtTrainDevice* st = nullptr;
-  ~DeviceEvalU() override { sshmt_train_device_free(st); }
-  int eval(const double* w, double* L, double* grad) override { return sshmt_train_device_eval(st, w, L, grad); }
-};
-
-// everything the entry points check and prepare; *rc_out != 0: refused
-struct Prepared {
-  glia_hmt_mlp_train_opts o;
-  int D = 0;
-  std::vector<double> X, t, w;
-  glia_hmt_sshmt_train_opts so;      // glia_hmt_sshmt_train alone, as `in`
-  SshmtInput in;
-};
-
-int prepare(const char* who, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_mlp_train_opts* opts,
-            const double* h_min, const double* h_max, const double* h_init, glia_hmt_mlp_model** out, Prepared* P,
-            const glia_hmt_sshmt_train_opts* sopts = nullptr, bool with_u = false) {
-  const std::string me = std::string(who) + ": ";
-  if (!out || n_rows < 0 || dim < 1 || (n_rows > 0 && (!h_rows || !h_labels))) { set_error(me + "invalid argument"); return GLIA_HMT_ERR_ARG; }
-  *out = nullptr;
-  if ((h_min == nullptr) != (h_max == nullptr)) { set_error(me + "minima and maxima come together"); return GLIA_HMT_ERR_ARG; }
-  if (sopts) P->so = *sopts; else sshmt_train_opts_default(&P->so);
-  if (with_u) P->o = P->so.base; else if (opts) P->o = *opts; else mlp_train_opts_default(&P->o);
-  const glia_hmt_mlp_train_opts& o = P->o;
-  std::string bad = with_u ? sshmt_train_bad_opts(P->so) : mlp_train_bad_opts(o);
-  if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_ARG; }
-  bad = mlp_train_unsupported(o, with_u);
-  if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_UNSUPPORTED; }
-  if (dim > kMlpTrainMaxDim) { set_error("mlp_train: rows of more than " + std::to_string(kMlpTrainMaxDim) + " columns are not supported"); return GLIA_HMT_ERR_UNSUPPORTED; }
-  for (int64_t i = 0; i < n_rows * dim; ++i)
-    if (!std::isfinite(h_rows[i])) { set_error("mlp_train: row " + std::to_string(i / dim) + " holds a value that is not finite"); return GLIA_HMT_ERR_ARG; }
-  for (int j = 0; h_min && j < dim; ++j)
-    if (!std::isfinite(h_min[j]) || !std::isfinite(h_max[j])) { set_error("mlp_train: the min/max table holds a value that is not finite"); return GLIA_HMT_ERR_ARG; }
-  P->D = dim + 1;
-  const long long d = mlp_train_n_weights(P->D, o.n1, o.n2);
-  P->w.resize((size_t)d);
-  if (h_init) {
-    for (long long p = 0; p < d; ++p) {
-      if (!std::isfinite(h_init[p])) { set_error("mlp_train: initial weight " + std::to_string(p) + " is not finite"); return GLIA_HMT_ERR_ARG; }
-      P->w[p] = h_init[p];
-    }
-  } else if (o.n1 > 0) {
-    for (long long p = 0; p < d; ++p) P->w[p] = mlp_init_weight(o.seed, (uint64_t)p);
-  }
-  mlp_train_prepare(h_rows, n_rows, dim, h_labels, h_min, h_max, o.pos_target, o.neg_target, &P->X, &P->t);
-  if (P->t.empty() && (!with_u || !mlp_isfeq(o.ws, 0.0))) { set_error("mlp_train: no row is labelled +1 or -1"); return GLIA_HMT_ERR_ARG; }
-  for (double v : P->X)
-    if (!std::isfinite(v)) { set_error("mlp_train: a rescaled row holds a value that is not finite"); return GLIA_HMT_ERR_ARG; }
-  return GLIA_HMT_OK;
-}
-
 // the unlabelled blocks of glia_hmt_sshmt_train: checked, the rows prepared as the labelled ones are, the paths and incidence lists built
-int prepare_blocks(const glia_hmt_sshmt_block* blocks, int n_blocks, int dim, const double* h_min, const double* h_max, Prepared* P) {
+int prepare_blocks(const glia_hmt_sshmt_block* blocks, int n_blocks, int dim, const double* h_min, const double* h_max,
+                   const glia_hmt_sshmt_train_opts& so, SshmtInput* input) {
   if (n_blocks < 0 || (n_blocks > 0 && !blocks)) { set_error("sshmt_train: invalid blocks"); return GLIA_HMT_ERR_ARG; }
-  const std::string bad = sshmt_bad_lengths(P->so.max_path_length, P->so.min_path_length);
+  const std::string bad = sshmt_bad_lengths(so.max_path_length, so.min_path_length);
   if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_UNSUPPORTED; }
-  SshmtInput& in = P->in;
+  SshmtInput& in = *input;
   in.D = dim + 1;
-  sshmt_fill_tables(P->so.merge_target, P->so.path_target, &in.tb);
+  sshmt_fill_tables(so.merge_target, so.path_target, &in.tb);
   for (int b = 0; b < n_blocks; ++b) {
     const glia_hmt_sshmt_block& B = blocks[b];
     const std::string me = "sshmt_train: block " + std::to_string(b);
@@ -91,7 +34,7 @@ int prepare_blocks(const glia_hmt_sshmt_block* blocks, int n_blocks, int dim, co
     }
     for (int64_t i = 0; i < B.n_merges * dim; ++i)
       if (!std::isfinite(B.rows[i])) { set_error(me + ": row " + std::to_string(i / dim) + " holds a value that is not finite"); return GLIA_HMT_ERR_ARG; }
-    merge_paths(B.order, B.n_merges, P->so.max_path_length, P->so.min_path_length, in.n_rows, &in.offsets, &in.members);
+    merge_paths(B.order, B.n_merges, so.max_path_length, so.min_path_length, in.n_rows, &in.offsets, &in.members);
     for (int64_t r = 0; r < B.n_merges; ++r) {
       for (int j = 0; j < dim; ++j) {
         const double v = B.rows[(size_t)r * dim + j];
@@ -107,20 +50,90 @@ int prepare_blocks(const glia_hmt_sshmt_block* blocks, int n_blocks, int dim, co
   return GLIA_HMT_OK;
 }
 
-int finish(Prepared& P, MlpTrainEval& ev, const double* h_min, const double* h_max, glia_hmt_mlp_model** out, MlpTrainEval* ev_u = nullptr) {
-  glia_hmt_mlp_model* m = new glia_hmt_mlp_model;
-  MlpTrainResult& R = m->r;
-  R.D = P.D; R.n1 = P.o.n1; R.n2 = P.o.n2; R.n_used = (int64_t)P.t.size();
-  if (h_min) { R.mn.assign(h_min, h_min + (P.D - 1)); R.mx.assign(h_max, h_max + (P.D - 1)); }
-  MlpTrainUns U;
-  if (ev_u) {
-    U.ev = ev_u; U.n_paths = P.in.n_paths(); U.n_rows = P.in.n_rows; U.wu = P.o.wu; U.sigma_u = P.so.sigma_u; U.min_sigma2 = P.o.min_sigma2;
-    U.update_sigma_u = P.o.update_sigma_u;
+// One training call, whichever entry point it came through.  c == NULL: the definition on one host thread.  with_u: the caller has the
+// merge-path term (glia_hmt_sshmt_train): wu, update_sigma_u, so's own fields and the blocks count, and labelled rows may be absent
+// while ws is off.
+int train(glia_hmt_ctx* c, bool with_u, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_sshmt_block* blocks,
+          int n_blocks, const glia_hmt_sshmt_train_opts& so, const double* h_min, const double* h_max, const double* h_init,
+          glia_hmt_mlp_model** out) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const std::string me = std::string(with_u ? "sshmt_train" : "mlp_train") + (c ? ": " : "_host: ");
+  if (!out || n_rows < 0 || dim < 1 || (n_rows > 0 && (!h_rows || !h_labels))) { set_error(me + "invalid argument"); return GLIA_HMT_ERR_ARG; }
+  *out = nullptr;
+  if ((h_min == nullptr) != (h_max == nullptr)) { set_error(me + "minima and maxima come together"); return GLIA_HMT_ERR_ARG; }
+  const glia_hmt_mlp_train_opts& o = so.base;
+  std::string bad = with_u ? sshmt_train_bad_opts(so) : mlp_train_bad_opts(o);
+  if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_ARG; }
+  bad = mlp_train_unsupported(o, with_u);
+  if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_UNSUPPORTED; }
+  if (dim > kMlpTrainMaxDim) { set_error("mlp_train: rows of more than " + std::to_string(kMlpTrainMaxDim) + " columns are not supported"); return GLIA_HMT_ERR_UNSUPPORTED; }
+  for (int64_t i = 0; i < n_rows * dim; ++i)
+    if (!std::isfinite(h_rows[i])) { set_error("mlp_train: row " + std::to_string(i / dim) + " holds a value that is not finite"); return GLIA_HMT_ERR_ARG; }
+  for (int j = 0; h_min && j < dim; ++j)
+    if (!std::isfinite(h_min[j]) || !std::isfinite(h_max[j])) { set_error("mlp_train: the min/max table holds a value that is not finite"); return GLIA_HMT_ERR_ARG; }
+  const int D = dim + 1;
+  const long long d = mlp_train_n_weights(D, o.n1, o.n2);
+  std::vector<double> X, t, w((size_t)d);      // the labelled rows as the trainer sees them, their targets, the weights
+  SshmtInput in;                               // the unlabelled blocks as the path term sees them
+  if (h_init) {
+    for (long long p = 0; p < d; ++p) {
+      if (!std::isfinite(h_init[p])) { set_error("mlp_train: initial weight " + std::to_string(p) + " is not finite"); return GLIA_HMT_ERR_ARG; }
+      w[p] = h_init[p];
+    }
+  } else if (o.n1 > 0) {
+    for (long long p = 0; p < d; ++p) w[p] = mlp_init_weight(o.seed, (uint64_t)p);
   }
-  R.n_paths = P.in.n_paths(); R.n_uns_rows = P.in.n_rows;
-  if (int rc = mlp_train_run(P.o, R.n_used, P.w, ev, &R, ev_u ? &U : nullptr)) { delete m; return rc; }
-  if (R.round_w.empty()) R.round_w.push_back(P.w);
-  *out = m;
+  mlp_train_prepare(h_rows, n_rows, dim, h_labels, h_min, h_max, o.pos_target, o.neg_target, &X, &t);
+  if (t.empty() && (!with_u || !mlp_isfeq(o.ws, 0.0))) { set_error("mlp_train: no row is labelled +1 or -1"); return GLIA_HMT_ERR_ARG; }
+  for (double v : X)
+    if (!std::isfinite(v)) { set_error("mlp_train: a rescaled row holds a value that is not finite"); return GLIA_HMT_ERR_ARG; }
+  if (with_u)
+    if (int rc = prepare_blocks(blocks, n_blocks, dim, h_min, h_max, so, &in)) return rc;
+
+  // an evaluator exists only for a term that is on: the trainer asks no other (the supervised trainer has always had its own)
+  const bool on_s = !with_u || (!t.empty() && !mlp_isfeq(o.ws, 0.0)), on_u = with_u && in.n_paths() > 0 && !mlp_isfeq(o.wu, 0.0);
+  std::unique_ptr<MlpTrainEval> ev, eu;
+  // the context's record of its last call: the device evaluators add to it; a call that fails leaves it zeroed
+  glia_hmt_mlp_train_timing* tm = !c ? nullptr : with_u ? &c->sst.sup : &c->mlt;
+  auto zero_timing = [&]() {
+    if (c && with_u) c->sst = glia_hmt_sshmt_train_timing();
+    if (c && !with_u) c->mlt = glia_hmt_mlp_train_timing();
+  };
+  if (c) {
+    GLIA_HIP_TRY(hipSetDevice(c->device));
+    zero_timing();
+    if (on_s)
+      if (int rc = mlp_train_device_create(X.data(), t.data(), (long long)t.size(), D, o.n1, o.n2, c->libm.exp_variant, c->stream, tm, &ev)) { zero_timing(); return rc; }
+    if (on_u)
+      if (int rc = sshmt_train_device_create(in, o.n1, o.n2, c->libm.exp_variant, c->stream, &c->sst, &eu)) { zero_timing(); return rc; }
+  } else {
+    if (on_s) {
+      MlpTrainHostEval* h = new MlpTrainHostEval;
+      ev.reset(h);
+      h->D = D; h->n1 = o.n1; h->n2 = o.n2; h->X = X.data(); h->t = t.data(); h->n = (int64_t)t.size();
+    }
+    if (on_u) {
+      SshmtHostEval* h = new SshmtHostEval;
+      eu.reset(h);
+      h->n1 = o.n1; h->n2 = o.n2; h->in = &in;
+    }
+  }
+  std::unique_ptr<glia_hmt_mlp_model> m(new glia_hmt_mlp_model);
+  MlpTrainResult& R = m->r;
+  R.D = D; R.n1 = o.n1; R.n2 = o.n2; R.n_used = (int64_t)t.size();
+  if (h_min) { R.mn.assign(h_min, h_min + dim); R.mx.assign(h_max, h_max + dim); }
+  R.n_paths = in.n_paths(); R.n_uns_rows = in.n_rows;
+  MlpTrainUns U;
+  U.ev = eu.get(); U.n_paths = R.n_paths; U.n_rows = R.n_uns_rows; U.wu = o.wu; U.sigma_u = so.sigma_u; U.min_sigma2 = o.min_sigma2;
+  U.update_sigma_u = o.update_sigma_u;
+  if (int rc = mlp_train_run(o, R.n_used, w, ev.get(), &R, with_u ? &U : nullptr)) { zero_timing(); return rc; }
+  if (R.round_w.empty()) R.round_w.push_back(w);
+  if (c) {
+    for (const glia_hmt_mlp_train_record& r : R.trace) tm->iterations += r.kind == 0;
+    tm->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (with_u) { c->sst.n_paths = R.n_paths; c->sst.n_uns_rows = R.n_uns_rows; }
+  }
+  *out = m.release();
   return GLIA_HMT_OK;
 }
 
@@ -139,80 +152,37 @@ void glia_hmt_mlp_train_opts_default(glia_hmt_mlp_train_opts* opts) {
   if (opts) mlp_train_opts_default(opts);
 }
 
-int glia_hmt_mlp_train_host(const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_mlp_train_opts* opts,
-                            const double* h_min, const double* h_max, const double* h_init, glia_hmt_mlp_model** out) {
-  Prepared P;
-  if (int rc = prepare("mlp_train_host", h_rows, n_rows, dim, h_labels, opts, h_min, h_max, h_init, out, &P)) return rc;
-  MlpTrainHostEval ev;
-  ev.D = P.D; ev.n1 = P.o.n1; ev.n2 = P.o.n2; ev.X = P.X.data(); ev.t = P.t.data(); ev.n = (int64_t)P.t.size();
-  return finish(P, ev, h_min, h_max, out);
-}
-
 int glia_hmt_mlp_train(glia_hmt_ctx* c, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels,
                        const glia_hmt_mlp_train_opts* opts, const double* h_min, const double* h_max, const double* h_init,
                        glia_hmt_mlp_model** out) {
-  if (!c) return glia_hmt_mlp_train_host(h_rows, n_rows, dim, h_labels, opts, h_min, h_max, h_init, out);
-  const auto t0 = std::chrono::steady_clock::now();
-  Prepared P;
-  if (int rc = prepare("mlp_train", h_rows, n_rows, dim, h_labels, opts, h_min, h_max, h_init, out, &P)) return rc;
-  GLIA_HIP_TRY(hipSetDevice(c->device));
-  c->mlt = glia_hmt_mlp_train_timing();
-  DeviceEval ev;
-  if (int rc = mlp_train_device_create(P.X.data(), P.t.data(), (long long)P.t.size(), P.D, P.o.n1, P.o.n2, c->libm.exp_variant, c->stream, &ev.st))
-    return rc;
-  const int rc = finish(P, ev, h_min, h_max, out);
-  if (rc == GLIA_HMT_OK) {
-    for (const glia_hmt_mlp_train_record& r : (*out)->r.trace) c->mlt.iterations += r.kind == 0;
-    c->mlt.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    mlp_train_device_timing(ev.st, &c->mlt);
-  }
-  return rc;
+  glia_hmt_sshmt_train_opts so;
+  sshmt_train_opts_default(&so);
+  if (opts) so.base = *opts;
+  return train(c, false, h_rows, n_rows, dim, h_labels, nullptr, 0, so, h_min, h_max, h_init, out);
+}
+
+int glia_hmt_mlp_train_host(const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_mlp_train_opts* opts,
+                            const double* h_min, const double* h_max, const double* h_init, glia_hmt_mlp_model** out) {
+  return glia_hmt_mlp_train(nullptr, h_rows, n_rows, dim, h_labels, opts, h_min, h_max, h_init, out);
 }
 
 void glia_hmt_sshmt_train_opts_default(glia_hmt_sshmt_train_opts* opts) {
   if (opts) sshmt_train_opts_default(opts);
 }
 
-int glia_hmt_sshmt_train_host(const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_sshmt_block* blocks,
-                              int n_blocks, const glia_hmt_sshmt_train_opts* opts, const double* h_min, const double* h_max,
-                              const double* h_init, glia_hmt_mlp_model** out) {
-  Prepared P;
-  if (int rc = prepare("sshmt_train_host", h_rows, n_rows, dim, h_labels, nullptr, h_min, h_max, h_init, out, &P, opts, true)) return rc;
-  if (int rc = prepare_blocks(blocks, n_blocks, dim, h_min, h_max, &P)) return rc;
-  MlpTrainHostEval ev;
-  ev.D = P.D; ev.n1 = P.o.n1; ev.n2 = P.o.n2; ev.X = P.X.data(); ev.t = P.t.data(); ev.n = (int64_t)P.t.size();
-  SshmtHostEval eu;
-  eu.n1 = P.o.n1; eu.n2 = P.o.n2; eu.in = &P.in;
-  return finish(P, ev, h_min, h_max, out, &eu);
-}
-
 int glia_hmt_sshmt_train(glia_hmt_ctx* c, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels,
                          const glia_hmt_sshmt_block* blocks, int n_blocks, const glia_hmt_sshmt_train_opts* opts, const double* h_min,
                          const double* h_max, const double* h_init, glia_hmt_mlp_model** out) {
-  if (!c) return glia_hmt_sshmt_train_host(h_rows, n_rows, dim, h_labels, blocks, n_blocks, opts, h_min, h_max, h_init, out);
-  const auto t0 = std::chrono::steady_clock::now();
-  Prepared P;
-  if (int rc = prepare("sshmt_train", h_rows, n_rows, dim, h_labels, nullptr, h_min, h_max, h_init, out, &P, opts, true)) return rc;
-  if (int rc = prepare_blocks(blocks, n_blocks, dim, h_min, h_max, &P)) return rc;
-  GLIA_HIP_TRY(hipSetDevice(c->device));
-  c->sst = glia_hmt_sshmt_train_timing();
-  // an evaluator exists only for a term that is on: the trainer asks no other
-  DeviceEval ev;
-  if (!P.t.empty() && !mlp_isfeq(P.o.ws, 0.0))
-    if (int rc = mlp_train_device_create(P.X.data(), P.t.data(), (long long)P.t.size(), P.D, P.o.n1, P.o.n2, c->libm.exp_variant, c->stream, &ev.st))
-      return rc;
-  DeviceEvalU eu;
-  if (P.in.n_paths() > 0 && !mlp_isfeq(P.o.wu, 0.0))
-    if (int rc = sshmt_train_device_create(P.in, P.o.n1, P.o.n2, c->libm.exp_variant, c->stream, &eu.st)) return rc;
-  const int rc = finish(P, ev, h_min, h_max, out, &eu);
-  if (rc == GLIA_HMT_OK) {
-    for (const glia_hmt_mlp_train_record& r : (*out)->r.trace) c->sst.sup.iterations += r.kind == 0;
-    c->sst.sup.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (ev.st) mlp_train_device_timing(ev.st, &c->sst.sup);
-    if (eu.st) sshmt_train_device_timing(eu.st, &c->sst);
-    c->sst.n_paths = P.in.n_paths(); c->sst.n_uns_rows = P.in.n_rows;
-  }
-  return rc;
+  glia_hmt_sshmt_train_opts so;
+  sshmt_train_opts_default(&so);
+  if (opts) so = *opts;
+  return train(c, true, h_rows, n_rows, dim, h_labels, blocks, n_blocks, so, h_min, h_max, h_init, out);
+}
+
+int glia_hmt_sshmt_train_host(const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_sshmt_block* blocks,
+                              int n_blocks, const glia_hmt_sshmt_train_opts* opts, const double* h_min, const double* h_max,
+                              const double* h_init, glia_hmt_mlp_model** out) {
+  return glia_hmt_sshmt_train(nullptr, h_rows, n_rows, dim, h_labels, blocks, n_blocks, opts, h_min, h_max, h_init, out);
 }
 
 int glia_hmt_merge_paths(const uint32_t* h_order, int64_t n_merges, int max_len, int min_len, int64_t* n_paths, int64_t* n_members,

@@ -109,50 +109,71 @@ namespace glia {
 
 inline double mlp_train_sigmoid(double h3) { return 1.0 / (1.0 + std::exp(-h3)); }      // the host's exp (mlp_model.hpp: mlp_sigmoid)
 
-// L = sum e_i^2 and, when grad != NULL, grad = -sum g_i e_i over prepared rows X [n][D] with targets t [n], by the two-level order.
-inline void mlp_loss_grad_host(const double* w, int D, int n1, int n2, const double* X, const double* t, int64_t n, double* L, double* grad) {
-  const MlpWeights m = mlp_train_weights(w, D, n1, n2);
+// The forward pass of one prepared row x [D]: the pre-activations to a [n1] and b [n2] (logsig: untouched); returns f by the host's sigmoid.
+inline double mlp_forward_row_host(const MlpWeights& m, const double* x, double* a, double* b) {
+  double h3;
+  if (m.n1 == 0) h3 = mlp_unit(m.w2, m.D, 1, 0, MlpRow{x});
+  else {
+    for (int k = 0; k < m.n1; ++k) a[k] = mlp_unit(m.w0, m.D, 1, k, MlpRow{x});
+    for (int k = 0; k < m.n2; ++k) b[k] = mlp_unit(m.w1, m.n1 + 1, 1, k, MlpActs{a, m.n1, 1});
+    h3 = mlp_unit(m.w2, m.n2 + 1, 1, 0, MlpActs{b, m.n2, 1});
+  }
+  return mlp_train_sigmoid(h3);
+}
+
+// The reduction both terms of the energy end in, by the two-level order: grad = -sum_r c_r g_r over prepared rows X [n][D].  Every
+// row r ascending runs the forward pass and asks term(r, f_r, &c_r) for its coefficient; false: the row is skipped.  grad == NULL:
+// the forward pass and the term's questions alone.
+template <class Term>
+inline void mlp_chunk_grad_host(const MlpWeights& m, const double* X, int64_t n, Term term, double* grad) {
+  const int C = kMlpTrainChunk, D = m.D, n1 = m.n1, n2 = m.n2;
   const long long d = mlp_train_n_weights(D, n1, n2);
-  const int C = kMlpTrainChunk;
-  std::vector<double> h1((size_t)C * (n1 + 1)), h2((size_t)C * (n2 + 1)), dh1((size_t)C * (n1 + 1)), dh2((size_t)C * (n2 + 1)), dh3(C), e(C);
-  double Lsum = 0.0;
+  std::vector<double> h1((size_t)C * (n1 + 1)), h2((size_t)C * (n2 + 1)), dh1((size_t)C * (n1 + 1)), dh2((size_t)C * (n2 + 1)), dh3(C), c(C);
+  std::vector<uint8_t> used(C);
   if (grad) for (long long p = 0; p < d; ++p) grad[p] = 0.0;
   for (int64_t r0 = 0; r0 < n; r0 += C) {
     const int nr = (int)(n - r0 < C ? n - r0 : C);
-    double Lc = 0.0;
     for (int r = 0; r < nr; ++r) {
-      const MlpRow x{X + (size_t)(r0 + r) * D};
       double *a = &h1[(size_t)r * (n1 + 1)], *b = &h2[(size_t)r * (n2 + 1)];
-      double h3;
-      if (n1 == 0) h3 = mlp_unit(m.w2, D, 1, 0, x);
-      else {
-        for (int k = 0; k < n1; ++k) a[k] = mlp_unit(m.w0, D, 1, k, x);
-        for (int k = 0; k < n2; ++k) b[k] = mlp_unit(m.w1, n1 + 1, 1, k, MlpActs{a, n1, 1});
-        h3 = mlp_unit(m.w2, n2 + 1, 1, 0, MlpActs{b, n2, 1});
-      }
-      const double f = mlp_train_sigmoid(h3);
-      e[r] = mlp_sub(t[r0 + r], f);
-      Lc = mlp_add(Lc, mlp_mul(e[r], e[r]));
-      if (!grad) continue;
+      const double f = mlp_forward_row_host(m, X + (size_t)(r0 + r) * D, a, b);
+      used[r] = term(r0 + r, f, &c[r]) && grad;
+      if (!used[r]) continue;
       dh3[r] = mlp_dh3(f);
       double *da = &dh1[(size_t)r * (n1 + 1)], *db = &dh2[(size_t)r * (n2 + 1)];
       for (int k = 0; k < n2; ++k) db[k] = mlp_dh2(m, k, b[k], dh3[r]);
       for (int j = 0; j < n1; ++j) da[j] = mlp_dh1(m, j, a[j], db, 1);
     }
-    Lsum = mlp_add(Lsum, Lc);
     if (!grad) continue;
     for (long long p = 0; p < d; ++p) {
       double S = 0.0;
       for (int r = 0; r < nr; ++r) {
-        if (mlp_feq0(e[r])) continue;
+        if (!used[r]) continue;
         const double g = mlp_grad_elem(m, p, MlpRow{X + (size_t)(r0 + r) * D}, &h1[(size_t)r * (n1 + 1)], &h2[(size_t)r * (n2 + 1)],
                                        &dh1[(size_t)r * (n1 + 1)], &dh2[(size_t)r * (n2 + 1)], dh3[r], 1);
-        S = mlp_sub(S, mlp_mul(g, e[r]));
+        S = mlp_sub(S, mlp_mul(g, c[r]));
       }
       grad[p] = mlp_add(grad[p], S);
     }
   }
-  *L = Lsum;
+}
+
+// sum v_i^2 over chunks of `chunk` consecutive entries: the chunk sums from +0.0 in order, their sum from +0.0 in chunk order
+inline double mlp_chunk_sqsum_host(const double* v, int64_t n, int chunk) {
+  double L = 0.0;
+  for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+    double Lc = 0.0;
+    for (int64_t i = i0; i < n && i < i0 + chunk; ++i) Lc = mlp_add(Lc, mlp_mul(v[i], v[i]));
+    L = mlp_add(L, Lc);
+  }
+  return L;
+}
+
+// The supervised term: c_r = e_r = t_r - f_r, a row with |e_r| < FEPS skipped; L = sum e_r^2 by row chunks.  grad == NULL: L alone.
+inline void mlp_loss_grad_host(const double* w, int D, int n1, int n2, const double* X, const double* t, int64_t n, double* L, double* grad) {
+  std::vector<double> e((size_t)n);
+  mlp_chunk_grad_host(mlp_train_weights(w, D, n1, n2), X, n,
+                      [&](int64_t r, double f, double* c) { *c = e[(size_t)r] = mlp_sub(t[r], f); return !mlp_feq0(*c); }, grad);
+  *L = mlp_chunk_sqsum_host(e.data(), n, kMlpTrainChunk);
 }
 
 // Whoever computes L and grad for the trainer; grad == NULL: L alone.  Returns a GLIA_HMT_* code.
@@ -227,10 +248,11 @@ inline std::string mlp_train_bad_opts(const glia_hmt_mlp_train_opts& o, bool wit
   return std::string();
 }
 
-// The trainer.  w: the initial weights, the final ones on return; n: labelled rows.  Returns the evaluator's code if it fails.
+// The trainer.  w: the initial weights, the final ones on return; n: labelled rows; ev: the supervised term's evaluator (asked, and so
+// needed, only while ws is on).  Returns the evaluator's code if it fails.
 // U (optional): the unsupervised term; it is off without a path (sshmt/input.hxx:120-121).  The terms enter fx and g in the order
 // regulariser, unsupervised, supervised (type/energy_function.hxx:164-230); without U not one operation differs from the supervised trainer.
-inline int mlp_train_run(const glia_hmt_mlp_train_opts& o, int64_t n, std::vector<double>& w, MlpTrainEval& ev, MlpTrainResult* R,
+inline int mlp_train_run(const glia_hmt_mlp_train_opts& o, int64_t n, std::vector<double>& w, MlpTrainEval* ev, MlpTrainResult* R,
                          const MlpTrainUns* U = nullptr) {
   const long long d = (long long)w.size();
   const bool use_r = !mlp_isfeq(o.wr, 0.0), use_s = !mlp_isfeq(o.ws, 0.0);
@@ -246,7 +268,7 @@ inline int mlp_train_run(const glia_hmt_mlp_train_opts& o, int64_t n, std::vecto
   auto energy = [&](bool want_grad, double* fx) -> int {
     double L = 0.0, Lu = 0.0;
     if (use_u && (rc = U->ev->eval(w.data(), &Lu, want_grad ? gu.data() : nullptr))) return rc;
-    if (use_s && (rc = ev.eval(w.data(), &L, want_grad ? gs.data() : nullptr))) return rc;
+    if (use_s && (rc = ev->eval(w.data(), &L, want_grad ? gs.data() : nullptr))) return rc;
     double ret = 0.0;
     if (want_grad) for (long long p = 0; p < d; ++p) g[p] = 0.0;
     if (use_r) {
@@ -293,7 +315,7 @@ inline int mlp_train_run(const glia_hmt_mlp_train_opts& o, int64_t n, std::vecto
   auto update_sigma_s = [&]() -> int {
     if (!use_s) { R->sigma2.push_back(sigma2); R->sigma2_eval.push_back(0.0); return 0; }
     double L = 0.0;
-    if ((rc = ev.eval(w.data(), &L, nullptr))) return rc;
+    if ((rc = ev->eval(w.data(), &L, nullptr))) return rc;
     const double v = L / (double)n;
     if (o.update_sigma_s) sigma2 = mlp_max(o.min_sigma2, v);
     R->sigma2.push_back(sigma2);

@@ -145,42 +145,20 @@ struct SshmtInput {
   int64_t n_paths() const { return (int64_t)offsets.size() - 1; }
 };
 
-// the logit of a prepared row with the training header's layout (mlp_loss_grad_host's forward), then the host's sigmoid
-inline double sshmt_forward_row_host(const MlpWeights& m, const double* x, double* a, double* b) {
-  double h3;
-  if (m.n1 == 0) h3 = mlp_unit(m.w2, m.D, 1, 0, MlpRow{x});
-  else {
-    for (int k = 0; k < m.n1; ++k) a[k] = mlp_unit(m.w0, m.D, 1, k, MlpRow{x});
-    for (int k = 0; k < m.n2; ++k) b[k] = mlp_unit(m.w1, m.n1 + 1, 1, k, MlpActs{a, m.n1, 1});
-    h3 = mlp_unit(m.w2, m.n2 + 1, 1, 0, MlpActs{b, m.n2, 1});
-  }
-  return mlp_train_sigmoid(h3);
-}
-
 // L_U = sum e_p^2 and, when grad != NULL, grad_U = -sum_r c_r g_r, by the orders above.
 inline void sshmt_loss_grad_host(const double* w, int n1, int n2, const SshmtInput& in, double* L, double* grad) {
-  const int D = in.D;
-  const MlpWeights m = mlp_train_weights(w, D, n1, n2);
-  const long long d = mlp_train_n_weights(D, n1, n2);
+  const MlpWeights m = mlp_train_weights(w, in.D, n1, n2);
   const int64_t N = in.n_rows, P = in.n_paths();
-  const int C = kMlpTrainChunk;
-  std::vector<double> h1((size_t)C * (n1 + 1)), h2((size_t)C * (n2 + 1)), dh1((size_t)C * (n1 + 1)), dh2((size_t)C * (n2 + 1)), dh3(C);
   std::vector<double> f((size_t)N), e((size_t)P), q(grad ? (size_t)P * kSshmtMaxPath : 0), c(grad ? (size_t)N : 0);
   std::vector<uint8_t> named(grad ? (size_t)N : 0, 0);
-  for (int64_t r = 0; r < N; ++r) f[(size_t)r] = sshmt_forward_row_host(m, &in.X[(size_t)r * D], h1.data(), h2.data());
-  double Lsum = 0.0;
-  for (int64_t p0 = 0; p0 < P; p0 += kSshmtPathChunk) {
-    double Lc = 0.0;
-    for (int64_t p = p0; p < P && p < p0 + kSshmtPathChunk; ++p) {
-      const int n = (int)(in.offsets[p + 1] - in.offsets[p]);
-      double fp[kSshmtMaxPath];
-      for (int i = 0; i < n; ++i) fp[i] = f[(size_t)in.members[in.offsets[p] + i]];
-      e[(size_t)p] = sshmt_path(fp, n, in.tb.T[n], in.tb.t[n], grad ? &q[(size_t)p * kSshmtMaxPath] : nullptr);
-      Lc = mlp_add(Lc, mlp_mul(e[(size_t)p], e[(size_t)p]));
-    }
-    Lsum = mlp_add(Lsum, Lc);
+  mlp_chunk_grad_host(m, in.X.data(), N, [&](int64_t r, double fr, double*) { f[(size_t)r] = fr; return false; }, nullptr);
+  for (int64_t p = 0; p < P; ++p) {
+    const int n = (int)(in.offsets[p + 1] - in.offsets[p]);
+    double fp[kSshmtMaxPath];
+    for (int i = 0; i < n; ++i) fp[i] = f[(size_t)in.members[in.offsets[p] + i]];
+    e[(size_t)p] = sshmt_path(fp, n, in.tb.T[n], in.tb.t[n], grad ? &q[(size_t)p * kSshmtMaxPath] : nullptr);
   }
-  *L = Lsum;
+  *L = mlp_chunk_sqsum_host(e.data(), P, kSshmtPathChunk);
   if (!grad) return;
   for (int64_t r = 0; r < N; ++r) {
     double acc = 0.0;
@@ -191,28 +169,7 @@ inline void sshmt_loss_grad_host(const double* w, int n1, int n2, const SshmtInp
     }
     c[(size_t)r] = acc;
   }
-  for (long long p = 0; p < d; ++p) grad[p] = 0.0;
-  for (int64_t r0 = 0; r0 < N; r0 += C) {
-    const int nr = (int)(N - r0 < C ? N - r0 : C);
-    for (int r = 0; r < nr; ++r) {
-      if (!named[(size_t)(r0 + r)]) continue;
-      double *a = &h1[(size_t)r * (n1 + 1)], *b = &h2[(size_t)r * (n2 + 1)];
-      dh3[r] = mlp_dh3(sshmt_forward_row_host(m, &in.X[(size_t)(r0 + r) * D], a, b));
-      double *da = &dh1[(size_t)r * (n1 + 1)], *db = &dh2[(size_t)r * (n2 + 1)];
-      for (int k = 0; k < n2; ++k) db[k] = mlp_dh2(m, k, b[k], dh3[r]);
-      for (int j = 0; j < n1; ++j) da[j] = mlp_dh1(m, j, a[j], db, 1);
-    }
-    for (long long p = 0; p < d; ++p) {
-      double S = 0.0;
-      for (int r = 0; r < nr; ++r) {
-        if (!named[(size_t)(r0 + r)]) continue;
-        const double g = mlp_grad_elem(m, p, MlpRow{&in.X[(size_t)(r0 + r) * D]}, &h1[(size_t)r * (n1 + 1)], &h2[(size_t)r * (n2 + 1)],
-                                       &dh1[(size_t)r * (n1 + 1)], &dh2[(size_t)r * (n2 + 1)], dh3[r], 1);
-        S = mlp_sub(S, mlp_mul(g, c[(size_t)(r0 + r)]));
-      }
-      grad[p] = mlp_add(grad[p], S);
-    }
-  }
+  mlp_chunk_grad_host(m, in.X.data(), N, [&](int64_t r, double, double* cr) { *cr = c[(size_t)r]; return named[(size_t)r] != 0; }, grad);
 }
 
 struct SshmtHostEval : MlpTrainEval {

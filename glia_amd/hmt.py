@@ -818,6 +818,33 @@ class MLPModel:
             pass
 
 
+def _train_args(who, o, n1, n2, dim, minmax, init, opts):
+    """What train_mlp and train_sshmt marshal alike.  o: MLPTrainOpts or SSHMTTrainOpts holding the defaults; receives n1, n2 and opts.
+    Returns the trailing (options, minima, maxima, initial weights, model handle) arguments of the call, the handle, and the arrays
+    the pointers look into."""
+    base = getattr(o, "base", o)
+    base.n1, base.n2 = n1, n2
+    for k, v in opts.items():
+        if k in dict(MLPTrainOpts._fields_):
+            setattr(base, k, v)
+        elif o is not base and k in dict(SSHMTTrainOpts._fields_) and k != "base":
+            setattr(o, k, v)
+        else:
+            raise TypeError(who + ": unknown option " + k)
+    mn = mx = None
+    if minmax is not None:
+        mn = np.ascontiguousarray(minmax[0], dtype=np.float64); mx = np.ascontiguousarray(minmax[1], dtype=np.float64)
+        if min(mn.size, mx.size) < dim:
+            raise HmtError(ERR_ARG, who + ": fewer min/max entries than columns")
+    if init is not None:
+        init = np.ascontiguousarray(init, dtype=np.float64)
+        D = dim + 1
+        if init.size != (D * n1 + (n1 + 1) * n2 + n2 + 1 if n1 else D):
+            raise HmtError(ERR_ARG, who + ": %d initial weights do not fit the model" % init.size)
+    h = C.c_void_p()
+    return (C.byref(o), _np(mn), _np(mx), _np(init), C.byref(h)), h, (mn, mx, init)
+
+
 def train_mlp(ctx, rows, labels, n1=10, n2=10, minmax=None, init=None, **opts):
     """train_sshmt_mlp / train_sshmt_logsig without the unsupervised term: rows [n, dim] float64, labels [n] (+1 / -1; any
     other label drops the row), n1 = n2 = 0 for logsig, minmax = (minima, maxima) to rescale rows by, init = initial weights.  Options:
@@ -829,25 +856,9 @@ def train_mlp(ctx, rows, labels, n1=10, n2=10, minmax=None, init=None, **opts):
     assert rows.ndim == 2 and labels.shape[0] == rows.shape[0]
     o = MLPTrainOpts()
     lib().glia_hmt_mlp_train_opts_default(C.byref(o))
-    o.n1, o.n2 = n1, n2
-    for k, v in opts.items():
-        if k not in dict(MLPTrainOpts._fields_):
-            raise TypeError("train_mlp: unknown option " + k)
-        setattr(o, k, v)
-    mn = mx = None
-    if minmax is not None:
-        mn = np.ascontiguousarray(minmax[0], dtype=np.float64); mx = np.ascontiguousarray(minmax[1], dtype=np.float64)
-        if min(mn.size, mx.size) < rows.shape[1]:
-            raise HmtError(ERR_ARG, "train_mlp: fewer min/max entries than columns")
-    if init is not None:
-        init = np.ascontiguousarray(init, dtype=np.float64)
-        D = rows.shape[1] + 1
-        if init.size != (D * n1 + (n1 + 1) * n2 + n2 + 1 if n1 else D):
-            raise HmtError(ERR_ARG, "train_mlp: %d initial weights do not fit the model" % init.size)
-    h = C.c_void_p()
+    args, h, keep = _train_args("train_mlp", o, n1, n2, rows.shape[1], minmax, init, opts)
     _check(lib().glia_hmt_mlp_train(ctx.h if ctx is not None else None, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(labels),
-                                    C.byref(o), _np(mn) if mn is not None else None, _np(mx) if mx is not None else None,
-                                    _np(init) if init is not None else None, C.byref(h)))
+                                    *args))
     return MLPModel(h, n1, n2)
 
 
@@ -907,32 +918,12 @@ def train_sshmt(ctx, rows, labels, unlabelled=(), n1=10, n2=10, minmax=None, ini
             raise HmtError(ERR_ARG, "train_sshmt: a block needs one row of %d columns per merge" % dim)
     o = SSHMTTrainOpts()
     lib().glia_hmt_sshmt_train_opts_default(C.byref(o))
-    o.base.n1, o.base.n2 = n1, n2
-    for k, v in opts.items():
-        if k in dict(MLPTrainOpts._fields_):
-            setattr(o.base, k, v)
-        elif k in dict(SSHMTTrainOpts._fields_) and k != "base":
-            setattr(o, k, v)
-        else:
-            raise TypeError("train_sshmt: unknown option " + k)
-    mn = mx = None
-    if minmax is not None:
-        mn = np.ascontiguousarray(minmax[0], dtype=np.float64); mx = np.ascontiguousarray(minmax[1], dtype=np.float64)
-        if min(mn.size, mx.size) < dim:
-            raise HmtError(ERR_ARG, "train_sshmt: fewer min/max entries than columns")
-    if init is not None:
-        init = np.ascontiguousarray(init, dtype=np.float64)
-        D = dim + 1
-        if init.size != (D * n1 + (n1 + 1) * n2 + n2 + 1 if n1 else D):
-            raise HmtError(ERR_ARG, "train_sshmt: %d initial weights do not fit the model" % init.size)
+    args, h, keep = _train_args("train_sshmt", o, n1, n2, dim, minmax, init, opts)
     arr = (SSHMTBlock * max(len(blocks), 1))()
     for i, (r, od) in enumerate(blocks):
         arr[i] = SSHMTBlock(r.ctypes.data if len(r) else None, od.ctypes.data if len(od) else None, len(od))
-    h = C.c_void_p()
     _check(lib().glia_hmt_sshmt_train(ctx.h if ctx is not None else None, _np(rows) if len(rows) else None, C.c_int64(rows.shape[0]), C.c_int(dim),
-                                      _np(labels) if len(labels) else None, arr, C.c_int(len(blocks)), C.byref(o),
-                                      _np(mn) if mn is not None else None, _np(mx) if mx is not None else None,
-                                      _np(init) if init is not None else None, C.byref(h)))
+                                      _np(labels) if len(labels) else None, arr, C.c_int(len(blocks)), *args))
     return MLPModel(h, n1, n2)
 
 

@@ -88,6 +88,27 @@ def cases():
 
 CASES = cases()
 IDS = [name for name, _ in CASES]
+
+
+def _no_term_cases():
+    """train_sshmt given no unlabelled block and wu = 0 must be train_mlp byte for byte (one routine runs both): 65 rows are a chunk and
+    a row, 3 + 17 units the kernel's <32> instantiation; Adam with the adaptive rule asks for L alone as well as for the gradient."""
+    rows, labels = _data(65, 5, 3)
+    adaptive_adam = dict(BASE, optimizer=2, step_decay=0.5, n_sigma_updates=2)
+    return [_case("mlp_3_17_n65_d5_adam_adaptive", rows, labels, 3, 17, **dict(adaptive_adam, seed=11)),
+            _case("logsig_n65_d5_adam_adaptive", rows, labels, 0, 0, init=np.linspace(-0.3, 0.3, 6), **adaptive_adam)]
+
+
+NO_TERM_CASES = _no_term_cases()
+
+
+def assert_identical_models(a, b):
+    """the weights of every round, the trace and sigma2: the same bytes"""
+    assert a.rounds == b.rounds and a.stopped_nonfinite == b.stopped_nonfinite
+    for r in range(a.rounds):
+        assert a.weights(r).tobytes() == b.weights(r).tobytes(), "weights after round %d differ" % r
+    assert len(a.trace) > 0 and a.trace.tobytes() == b.trace.tobytes()
+    assert a.sigma2.tobytes() == b.sigma2.tobytes() and a.sigma2_eval.tobytes() == b.sigma2_eval.tobytes()
 _REF = {}
 
 

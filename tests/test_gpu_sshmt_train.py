@@ -64,6 +64,21 @@ def test_two_calls_return_identical_bytes_and_timing_is_reported(ctx):
 
 
 @pytest.mark.gpu
+def test_no_block_and_no_wu_is_the_supervised_trainer_byte_for_byte(ctx):
+    """train_sshmt(ctx, ...) without blocks and train_mlp(ctx, ...) through the device entry points: 65 rows, 3 + 17 units -- the chunk
+    kernel's <32> instantiation across a chunk boundary"""
+    from glia_amd import hmt
+    kw = MK.NO_TERM_CASES[0][1]
+    assert (kw["rows"].shape[0], kw["n1"], kw["n2"]) == (65, 3, 17)
+    a = hmt.train_mlp(ctx, kw["rows"], kw["labels"], kw["n1"], kw["n2"], kw["minmax"], kw["init"], **kw["opts"])
+    b = hmt.train_sshmt(ctx, kw["rows"], kw["labels"], (), kw["n1"], kw["n2"], kw["minmax"], kw["init"], **dict(kw["opts"], wu=0.0))
+    assert a.rounds == 2 and int((a.trace["kind"] == 0).sum()) > 0
+    MK.assert_identical_models(a, b)
+    assert b.n_paths == 0 and (b.sigma_u2 == 0.0).all()
+    assert hmt.Context.internal_errors() == 0
+
+
+@pytest.mark.gpu
 def test_refusals_reach_the_device_entry_point_too(ctx):
     from glia_amd import hmt
     kw = K.CASES[K.IDS.index("wu_one")][1]

@@ -220,6 +220,17 @@ def test_without_the_term_the_supervised_trainer_is_unchanged(name):
     assert a.n_paths == 0 and a.n_uns_rows == 0 and (a.sigma_u2 == 0.0).all()
 
 
+@pytest.mark.parametrize("name,kw", MK.NO_TERM_CASES, ids=[n for n, _ in MK.NO_TERM_CASES])
+def test_no_block_and_no_wu_is_the_supervised_trainer_byte_for_byte(name, kw):
+    """mlp_backward.hpp: "without U not one operation differs from the supervised trainer" -- both entry points run one routine"""
+    hmt = _hmt()
+    a = hmt.train_mlp_host(kw["rows"], kw["labels"], kw["n1"], kw["n2"], kw["minmax"], kw["init"], **kw["opts"])
+    b = hmt.train_sshmt_host(kw["rows"], kw["labels"], (), kw["n1"], kw["n2"], kw["minmax"], kw["init"], **dict(kw["opts"], wu=0.0))
+    assert a.rounds == 2 and a.n_used_rows == 65 and int((a.trace["kind"] == 0).sum()) > 0
+    MK.assert_identical_models(a, b)
+    assert b.n_paths == 0 and (b.sigma_u2 == 0.0).all()
+
+
 def test_defaults():
     hmt = _hmt()
     import ctypes as C
