@@ -10,6 +10,7 @@ tests/test_gpu_wide_linkages.py holds the device to this file where it cannot.
     order, sal = generate(labels, image)                 # what merge_order_bc(FeatureStubClassifier(31)) has to return
     step = check(labels, image, order, sal)              # first step that breaks a rule, or -1
     st = stats(labels, image)                            # per merge: neighbour counts, list lengths, new edges, fragile pairs
+    step, n, alive = chain_at_pop(labels, image, order, key)   # the fragile chain of the edge that merges leaf `key` away
 
 Rules, each with the place in the reference (glia/code/...) it restates:
   leaf pairs      _featdef.leaf_lists: the directed pair (own label, first differing valid neighbour) of every boundary voxel.
@@ -139,6 +140,14 @@ class Replay:
         sel = ((ra == r) != (rb == r)) & self.fragile
         return np.bincount(np.where(ra == r, rb, ra)[sel], minlength=self.nreg)
 
+    def fragile_chain(self, x, y):
+        """(the fragile pairs between regions x and y -- what the device chains on their record --, how many of them are on the shared
+        boundary now: those whose target leaf has an alive pair left)"""
+        ra, rb = self.reg[self.pa], self.reg[self.pb]
+        sel = self.fragile & (((ra == x) & (rb == y)) | ((ra == y) & (rb == x)))
+        own = np.bincount(self.pa[~(self.has_rev & (ra == rb))], minlength=self.L)
+        return int(sel.sum()), int((sel & (own[self.pb] > 0)).sum())
+
     def _saliency(self, s, n):
         mean = np.zeros(len(s), np.float64)                     # ImageRealFeats::generate: nothing is touched for an empty list
         np.divide(s, n, out=mean, where=n > 0)
@@ -246,6 +255,18 @@ def check(labels, image, order, saliencies, mask=None, F=None, explain=False, le
     if rp.top() is not None:
         return out(len(order), "the order ends with edges left in the table")
     return out(-1, "")
+
+
+def chain_at_pop(labels, image, order, key, mask=None, leaves=None):
+    """(the step of `order` that merges the region with label `key` away, the fragile pairs between the two merged regions at that
+    step, how many of them are alive): how long and how dead the chain is that the popped edge was scored with"""
+    rp = Replay(labels, image, mask, leaves=leaves)
+    for i, (a, b, _) in enumerate(np.asarray(order).tolist()):
+        r0, r1 = rp.rid(a), rp.rid(b)
+        if key in (a, b):
+            return (i,) + rp.fragile_chain(r0, r1)
+        rp.merge(r0, r1)
+    return None
 
 
 def stats(labels, image, mask=None, F=None, order=None, leaves=None):

@@ -19,6 +19,18 @@ kernel's rule -- a region's list is created with one entry per region it touches
 when a neighbour is merged away its entry is reused in place for the new region, or dies when the neighbour touched both merged
 regions -- are `total` itself, and have to be kMargin below a class's upper edge.  The new table edges are a lower bound of newcount.
 
+Two more caps have images of their own (tests/_hub_cases.py; small instances of both are held to the oracle in
+tests/test_loop_definition.py):
+    the fragile comb (2202 regions)   one record, hub-Y, with a chain of 1100 fragile leaf entries of which half are dead when its edge
+        pops.  A helper's last wave walks the chains of a chunk's (record, channel) pairs into ONE LDS work list of kFragCap = 4096
+        entries: with four channels 4400 entries, two batches (the full list, the entry that opens the next batch, the accumulators
+        carried over); with one channel a long chain inside one batch.  Under the stub scorer the loop's own workgroup walks the
+        chain serially.  ysplit = 2: two records with chains of 550.
+    the touching comb (16 606 regions, 410 merges)   `total` falls by one per merge from 16 607 to 16 198, across kJobMax = 16 384:
+        the first 223 contractions are too large for a helper job and are scored by the loop's own workgroup, the others go to the
+        helpers -- one run that changes the route; every contraction has more than 16 000 list entries and new records.
+test_fragile_chains_and_job_sizes_are_reached proves these sizes from the replay.
+
 The other linkages are compared with the oracle directly (0.5 s and 3 s of oracle time at 1801 regions).  Everything is Q8, every
 comparison bit for bit."""
 import os
@@ -30,10 +42,14 @@ import pytest
 import _featdef
 import _loopdef
 import _rf
-from _hub_cases import CLASSES, hub_image, kMargin, thin_hub_image, width_classes
+from _hub_cases import CLASSES, fragile_comb_image, hub_image, kMargin, thin_hub_image, touching_comb_image, width_classes
 
 STUB = 11 + 4 * 3 + 7 + 1          # x0.b0.mean
 kCap, kLdsCap4 = 96, 2252          # W.cap's limit; kWsBytes / (8 + 8 K) at K = 4
+kFragCap, kHelpChunk, kJobMax = 4096, 8, 16384      # greedy_bc.hip: work-list entries per batch; records per helper round; records per job
+kCombN, kCombY = 1100, 2           # fragile comb: cells (chain entries of hub-Y), Y's label
+
+
 def _narrow_hub(grid):
     """hub_image(None, grid) with the hub's own pixels pressed into [0.25, 0.75): on random Q8 values the extremes of a boundary of
     thousands of pixels are 0 and 255/256 from either side, so a contraction that took the neighbours' extremes for the hub's, or lost
@@ -43,7 +59,9 @@ def _narrow_hub(grid):
 
 
 IMAGES = {"hub": lambda: hub_image(None), "hub4": lambda: hub_image(4), "hub36": lambda: hub_image(None, grid=36), "hub36n": lambda: _narrow_hub(36),
-          "thin30": lambda: thin_hub_image(30), "thin30_4": lambda: thin_hub_image(30, 4)}
+          "thin30": lambda: thin_hub_image(30), "thin30_4": lambda: thin_hub_image(30, 4),
+          "comb": lambda: fragile_comb_image(kCombN), "comb2": lambda: fragile_comb_image(kCombN, ysplit=2),
+          "tcomb": lambda: touching_comb_image(41, 10, 40, 39)}
 BC_CLASSES = ("several rounds, one pass", "two or three passes", "global marks", "beyond ldsCap (K = 4)")
 _cpu, _dev = {}, {}
 
@@ -98,6 +116,49 @@ def test_width_classes_are_hit(name, forest):
         assert h >= 20, (cls, h)
     if name == "hub4" or forest:      # exact ties: the insertion order decides most of the order
         assert len(np.unique(s)) * 2 < len(o)
+
+
+def _pop_of(name, forest, y=kCombY):
+    """(step, chain entries, alive ones) of the edge that merges Y away in the reference order"""
+    key = ("pop", name, forest, y)
+    if key not in _cpu:
+        lab, pb = _image(name)
+        _cpu[key] = _loopdef.chain_at_pop(lab, pb, _reference(name, forest)[0], y, leaves=_cpu["leaves", name])
+    return _cpu[key]
+
+
+@pytest.mark.parametrize("name,forest", [("comb", False), ("comb", True), ("comb2", True), ("tcomb", False), ("tcomb", True)])
+def test_fragile_chains_and_job_sizes_are_reached(name, forest):
+    """what the replay proves about the images of the two caps.  A chain's entries are the fragile pairs on one record, dead or alive
+    (stats()["fragile"]): a helper's lane walks all of them, once per channel, and aliveness is decided from the list."""
+    o, s, st, _ = _reference(name, forest)
+    lab, _ = _image(name)
+    which = "%s, %s" % (name, "stump forest" if forest else "stub")
+    if name == "tcomb":
+        total = st["len0"] + st["len1"]
+        above, below = total > kJobMax, total <= kJobMax - kMargin
+        print("%s: %d merges of %d regions, total %d .. %d: %d merges above kJobMax, %d at least kMargin below; fewest new records %d"
+              % (which, len(o), len(np.unique(lab)), int(total.max()), int(total.min()), int(above.sum()), int(below.sum()), int(st["new_records"].min())))
+        assert len(o) == 410 and above.sum() >= 100 and below.sum() >= 100
+        assert above[:int(above.sum())].all() and below[-int(below.sum()):].all(), "one order, the large ones first"
+        assert st["new_records"].min() > 16000 and st["new_edges"].max() <= 409
+        return
+    assert len(o) == len(np.unique(lab)) - 1
+    K = 4
+    two = st["fragile"] * K > kFragCap + kHelpChunk * 4        # the other records of the chunk add entries to the list too
+    inside = (st["fragile"] > 256) & (st["fragile"] + kHelpChunk <= kFragCap)        # K = 1
+    pops = [_pop_of(name, forest, y) for y in ((2, 3) if name == "comb2" else (kCombY,))]
+    print("%s: largest fragile count on one record %d; %d merges with more than (kFragCap + 32) / 4 = 1032; hub-Y pops at %s, distinct saliencies %d"
+          % (which, int(st["fragile"].max()), int(two.sum()),
+             ", ".join("step %d with %d of %d entries alive" % (p[0], p[2], p[1]) for p in pops), len(np.unique(s))))
+    if name == "comb":
+        step, n, alive = pops[0]
+        assert two.sum() >= 20 and inside.sum() >= 20
+        assert n == kCombN > 1024 and n * K > kFragCap + kHelpChunk * 4
+        assert n <= 4 * alive <= 3 * n, "a quarter to three quarters of the chain alive at the pop"
+        assert two[step - 1], "the record that pops was scored with the long chain"
+    else:
+        assert all(p[1] == kCombN // 2 and 0 < p[2] < p[1] for p in pops)
 
 
 @pytest.fixture(scope="module")
@@ -343,6 +404,145 @@ def test_stub_loop_on_the_thin_hub_image(ctx, name):
     assert _rows_are(f, o, rm.bc_feat, int(lab.max())) == _rows_are(f, o, rm.bc_feat_batch, int(lab.max()))
     rm.close()
     assert hmt.Context.internal_errors() == before == 0
+
+
+HELPERS = [None, 5, 0]            # the default (one per compute unit left), a few, none: the loop's own workgroup walks trees and chains
+
+
+def _forest_run(ctx, name, four, helpers, routes):
+    """the stump forest on `name`: order and saliencies are the replay's, s == clf.predict(f), the popped rows are the rows of
+    `routes` (attribute names of the map)"""
+    from glia_amd import hmt
+    lab, pb = _image(name)
+    ref = _reference(name, forest=True)
+    clf = _stump_forest(ctx, pb)
+    before = hmt.Context.internal_errors()
+    rm = _rm(ctx, name, four)
+    with hmt.options(**({} if helpers is None else dict(GLIA_HMT_HELPERS=helpers))):
+        o, s, f = rm.merge_order_bc(clf, want_feats=True)
+    assert _loopdef.check(lab, pb, o, s, F=ref[3], explain=True, leaves=_cpu["leaves", name]) == (-1, "")
+    assert _same((o, s), ref)
+    assert (_bits(s) == _bits(clf.predict(f))).all()
+    assert (_bits(s) == _bits(ref[3](f[:, STUB]))).all()
+    assert len({_rows_are(f, o, getattr(rm, r), int(lab.max())) for r in routes}) == 1
+    rm.close()
+    clf.close()
+    assert hmt.Context.internal_errors() == before == 0
+
+
+def _stub_run_checked(ctx, name, four, routes, **env):
+    from glia_amd import hmt
+    lab, _ = _image(name)
+    ref = _reference(name)
+    before = hmt.Context.internal_errors()
+    with hmt.options(**env):
+        rm = _rm(ctx, name, four)
+        o, s, f = rm.merge_order_bc(hmt.FeatureStubClassifier(ctx, STUB), want_feats=True)
+    assert _check(name, o, s) == (-1, "")
+    assert _same((o, s), ref)
+    assert (_bits(1.0 - f[:, STUB]) == _bits(s)).all()
+    assert len({_rows_are(f, o, getattr(rm, r), int(lab.max())) for r in routes}) == 1
+    rm.close()
+    assert hmt.Context.internal_errors() == before == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,helpers", [("comb", h) for h in HELPERS] + [("comb2", None)])
+def test_stump_forest_on_a_fragile_chain_of_two_batches(ctx, name, helpers):
+    """four channels: the 1100 entries of hub-Y are walked by four lanes into a list of 4096 -- the list fills, the wave goes round a
+    second time with the accumulators carried over, and more than a third of the entries are dead when the edge pops (comb2: two
+    chains of 550).  Of a helper's accumulators the saliency sees the count and the sum of one channel (the others:
+    test_every_accumulator_of_a_chain_of_two_batches); the popped rows are the work of the loop's own workgroup, which walks the
+    chain one lane per channel -- as it does for every record when there are no helpers."""
+    step, n, alive = _pop_of(name, True)
+    assert n * 4 > kFragCap + kHelpChunk * 4 or name == "comb2"
+    assert 0 < alive < n
+    _forest_run(ctx, name, True, helpers, ("bc_feat", "bc_feat_batch"))
+
+
+def _mixed_forest(ctx, pb, rows, nrandom):
+    """the 255 stumps on x0.b0.mean, which shape the order (the X_i first, hub-Y among the V_i), and `nrandom` trees of depth 7 over
+    ALL columns of `rows`"""
+    thr = _stumps(pb)
+    rnd = _rf.random_forest(np.random.default_rng(63), nrandom, 7, rows)
+    n, m = len(thr), rnd["xbestsplit"].shape[1]
+    stumps = {k: np.zeros((n,) + v.shape[1:], v.dtype) for k, v in rnd.items() if k not in ("ndbigtree", "orig_labels")}
+    stumps["xbestsplit"][:, 0] = thr
+    stumps["treemap"][:, 0] = (2, 3)
+    stumps["nodestatus"][:, 0], stumps["nodestatus"][:, 1:3] = 1, -1
+    stumps["bestvar"][:, 0] = STUB + 1
+    stumps["nodeclass"][:, 1], stumps["nodeclass"][:, 2] = 1, 2
+    forest = {k: np.concatenate([v, rnd[k]]) for k, v in stumps.items()}
+    forest["ndbigtree"] = np.concatenate([np.full(n, 3, np.int32), rnd["ndbigtree"]])
+    forest["orig_labels"] = rnd["orig_labels"]
+    assert m >= 3
+    return _load(ctx, forest)
+
+
+@pytest.mark.gpu
+def test_every_accumulator_of_a_chain_of_two_batches(ctx):
+    """The stump forest reads ONE column, the mean of one channel's sums; and the popped rows are no witness of a helper's work: the
+    loop's own workgroup makes the row of the edge it pops, walking the chain itself.  So the helpers' histogram, threshold, extreme
+    and square accumulators of the four channels are seen by nothing above.  Here 48 trees over all columns vote beside the stumps.
+    No replay knows their votes; the witness is clf.predict() of the popped rows: the saliency hub-Y pops with is the helpers' vote
+    on their vector, from a work list of two batches, the row is the loop's own serial walk of the same chain.  That hub-Y was
+    scored on more than 1032 entries, and popped part dead, is read off the returned order.  (A run without helpers would be a
+    witness of every re-scoring on the way to the pop, through the order, but takes 12 s: the serial walk is slow.)"""
+    from glia_amd import hmt
+    lab, pb = _image("comb")
+    before = hmt.Context.internal_errors()
+    rm = _rm(ctx, "comb", four=True)
+    clf = _mixed_forest(ctx, pb, rm.bc_feat_batch(_reference("comb", forest=True)[0]), 48)
+    o, s, f = rm.merge_order_bc(clf, want_feats=True)
+    st = _loopdef.stats(lab, pb, order=o, leaves=_cpu["leaves", "comb"])
+    step, n, alive = _loopdef.chain_at_pop(lab, pb, o, kCombY, leaves=_cpu["leaves", "comb"])
+    two = st["fragile"] * 4 > kFragCap + kHelpChunk * 4
+    print("mixed forest: hub-Y pops at step %d with %d of %d entries alive; %d merges with more than 1032 fragile entries on one record; "
+          "distinct saliencies %d" % (step, alive, n, int(two.sum()), len(np.unique(s))))
+    assert len(o) == 2 * kCombN + 1 and n * 4 > kFragCap + kHelpChunk * 4 and two[step - 1] and two.sum() >= 20
+    assert 0 < alive < n
+    assert (_bits(s) == _bits(clf.predict(f))).all()
+    votes = s * (255 + 48) - 255 * _reference("comb", forest=True)[3](f[:, STUB])
+    assert np.abs(votes - np.round(votes)).max() < 1e-9 and len(np.unique(np.round(votes))) > 8, "the random trees take part"
+    _rows_are(f, o, rm.bc_feat_batch, int(lab.max()))
+    rm.close()
+    clf.close()
+    assert hmt.Context.internal_errors() == before == 0
+
+
+@pytest.mark.gpu
+def test_stub_loop_on_a_fragile_chain(ctx):
+    """the loop's own workgroup: one lane per (record, channel) walks the 1100 entries serially"""
+    _stub_run_checked(ctx, "comb", True, ("bc_feat", "bc_feat_batch"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("helpers", HELPERS + ["stub", "stub, smallest capacities"])
+def test_fragile_chain_inside_one_batch(ctx, helpers):
+    """one channel: 1100 entries of 4096.  The stub's serial walk takes a quarter of the four-channel one's time here, so this is where
+    it runs once more with GLIA_HMT_MINCAP=1 (the arrays grow, and the kernel is launched again, while the chain is being built)"""
+    if isinstance(helpers, str):
+        _stub_run_checked(ctx, "comb", False, ("bc_feat", "bc_feat_batch"), **(dict(GLIA_HMT_MINCAP=1) if "smallest" in helpers else {}))
+    else:
+        _forest_run(ctx, "comb", False, helpers, ("bc_feat", "bc_feat_batch"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("helpers", HELPERS)
+def test_stump_forest_across_job_max(ctx, helpers):
+    """the touching comb: 223 contractions of more than kJobMax list entries scored by the loop's own workgroup, then 187 helper jobs of
+    16 000 rows (of which the table edges, at most 409, are scored) -- the job sequence, the vote slots and the rows start in the
+    middle of a run"""
+    st = _reference("tcomb", forest=True)[2]
+    total = st["len0"] + st["len1"]
+    assert (total > kJobMax).sum() >= 100 and (total <= kJobMax - kMargin).sum() >= 100
+    _forest_run(ctx, "tcomb", False, helpers, ("bc_feat_batch",))
+
+
+@pytest.mark.gpu
+def test_stub_loop_on_the_touching_comb(ctx):
+    """contractions of 16 000 list entries on the global mark arrays, 16 000 new records each"""
+    _stub_run_checked(ctx, "tcomb", False, ("bc_feat_batch",))
 
 
 # ---- the other linkages, against the oracle ----------------------------------------------------------------------------------------

@@ -10,7 +10,7 @@ import pytest
 
 import _featdef
 import _loopdef
-from _hub_cases import hub_image, thin_hub_image
+from _hub_cases import fragile_comb_image, hub_image, thin_hub_image, touching_comb_image
 
 STUB = 11 + 4 * 3 + 7 + 1          # x0.b0.mean: mean of the boundary image over the shared boundary
 
@@ -35,6 +35,8 @@ def _const():
 CASES = {
     "hub8": lambda: hub_image(None, 8), "hub10": lambda: hub_image(None, 10), "hub8_4levels": lambda: hub_image(4, 8),
     "hub8_constant": _const, "thin_hub8": lambda: thin_hub_image(8),
+    "fragile_comb40": lambda: fragile_comb_image(40), "fragile_comb36_split3": lambda: fragile_comb_image(36, ysplit=3),
+    "touching_comb3x4": lambda: touching_comb_image(3, 4, 5, 4),
     "synth64x64_S4": lambda: _synth((64, 64), 4), "synth96x96_S8": lambda: _synth((96, 96), 8), "synth48x40_S4": lambda: _synth((48, 40), 4),
     "synth72x72_S4": lambda: _synth((72, 72), 4), "synth24x24x24_S6": lambda: _synth((24, 24, 24), 6), "masked48x40_S4": _masked,
 }
@@ -80,13 +82,37 @@ def test_the_cases_are_what_they_are_meant_to_be():
     assert len(np.unique(lab)) == 129 and len(o) == 64
     st = _loopdef.stats(lab, pb, order=o)
     assert (st["live0"] + st["live1"] > st["tab0"] + st["tab1"]).all() and st["fragile"].max() >= 1
+    # the fragile comb: every Y -> X_i is fragile and nothing else is; the hub takes the 40 X_i first, and W'-Y pops between the V_i,
+    # on a chain of 40 of which a quarter to three quarters are alive.  Split in three: each part pops on a chain of 12, part dead
+    lab, pb, _, o, s = _case("fragile_comb40")
+    rp = _loopdef.Replay(lab, pb)
+    assert len(np.unique(lab)) == 82 and len(o) == 81 and rp.fragile.sum() == 40
+    assert {rp.pair_keys[i] for i in np.flatnonzero(rp.fragile)} == {(2, 3 + 2 * i) for i in range(40)}
+    assert set(o[:40, 0].tolist()) | set(o[:40, 1].tolist()) >= {3 + 2 * i for i in range(40)}, "the X_i go first"
+    step, n, alive = _loopdef.chain_at_pop(lab, pb, o, 2)
+    print("fragile_comb40: W'-Y pops at step %d of %d, %d of its %d fragile pairs alive" % (step, len(o), alive, n))
+    assert n == 40 and 10 <= alive <= 30 and step == 40 + (n - alive)
+    assert _loopdef.stats(lab, pb, order=o)["fragile"].max() == 40
+    lab, pb, _, o, s = _case("fragile_comb36_split3")
+    assert len(np.unique(lab)) == 76 and len(o) == 75
+    for y in (2, 3, 4):
+        step, n, alive = _loopdef.chain_at_pop(lab, pb, o, y)
+        print("fragile_comb36_split3: part %d pops at step %d, %d of %d alive" % (y, step, alive, n))
+        assert n == 12 and 0 < alive < 12
+    # the touching comb: 12 merges (hub <-> L) among 67 regions, the hub touches every tooth: total = regions + 1 - step
+    lab, pb, _, o, _ = _case("touching_comb3x4")
+    st = _loopdef.stats(lab, pb, order=o)
+    assert len(np.unique(lab)) == 67 and len(o) == 12
+    assert (st["len0"] + st["len1"] == 68 - np.arange(12)).all() and (st["new_records"] == 65 - np.arange(12)).all()
+    assert st["fragile"].max() == 1 and (st["new_edges"] == 11 - np.arange(12)).all()
     # compact supervoxels: regions touch that are no table neighbours (the restriction to the table matters)
     lab, pb, _, o, _ = _case("synth64x64_S4")
     st = _loopdef.stats(lab, pb, order=o)
     assert (st["new_records"] > st["new_edges"]).any()
 
 
-@pytest.mark.parametrize("name", ["hub8_4levels", "thin_hub8", "synth48x40_S4", "synth24x24x24_S6", "masked48x40_S4"])
+@pytest.mark.parametrize("name", ["hub8_4levels", "thin_hub8", "synth48x40_S4", "synth24x24x24_S6", "masked48x40_S4", "fragile_comb40",
+                                  "fragile_comb36_split3"])
 def test_flat_shared_boundary_rule_equals_get_boundary(name):
     """'alive pairs between the two regions whose target leaf has an alive pair left' against boundaryWith on TRegion objects, for the
     merged pair of every step and for the new region with (a sample of) the regions that touch it"""
@@ -99,7 +125,7 @@ def test_flat_shared_boundary_rule_equals_get_boundary(name):
         assert rp.boundary_pairs(r0, r1) == set(_featdef.get_boundary(g.regions[a], g.regions[b]))
         r2 = rp.merge(r0, r1)
         _, touching = _loopdef._others(rp.t_lo, rp.t_hi, r2)
-        every = name == "thin_hub8" and i % 8 == 0
+        every = name == "thin_hub8" and i % 8 == 0 or name.startswith("fragile_comb") and i % 4 == 0
         for rs in touching.tolist() if every else touching.tolist()[:4]:
             got = rp.boundary_pairs(r2, rs)
             assert got == set(_featdef.get_boundary(g.regions[c], g.regions[rp.key(rs)]))
@@ -120,7 +146,8 @@ def _independent(o, i):
     return o[i, 2] not in o[i + 1, :2]
 
 
-@pytest.mark.parametrize("name", ["hub8", "thin_hub8", "synth72x72_S4", "synth24x24x24_S6", "masked48x40_S4"])
+@pytest.mark.parametrize("name", ["hub8", "thin_hub8", "synth72x72_S4", "synth24x24x24_S6", "masked48x40_S4", "fragile_comb40",
+                                  "fragile_comb36_split3", "touching_comb3x4"])
 def test_check_names_the_step_of_a_spoiled_order(name):
     lab, pb, mask, o, s = _case(name)
     n = len(o)
