@@ -182,8 +182,18 @@ void glia_hmt_train_opts_default(glia_hmt_train_opts* o) {
   o->max_depth = d.max_depth; o->seed = d.seed;
 }
 
+void glia_hmt_oob_opts_default(glia_hmt_oob_opts* o) {
+  if (!o) return;
+  o->oob = 0; o->importance = 0;
+}
+
 int glia_hmt_forest_train(glia_hmt_ctx* c, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_train_opts* opts,
                           glia_hmt_forest_model** out) {
+  return glia_hmt_forest_train_oob(c, h_rows, n_rows, dim, h_labels, opts, nullptr, out);
+}
+
+int glia_hmt_forest_train_oob(glia_hmt_ctx* c, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_train_opts* opts,
+                              const glia_hmt_oob_opts* oob_opts, glia_hmt_forest_model** out) {
   if (!c || !out) { set_error("forest_train: NULL context or output"); return GLIA_HMT_ERR_ARG; }
   if ((n_rows > 0 && dim > 0 && !h_rows) || (n_rows > 0 && !h_labels)) { set_error("forest_train: NULL rows or labels"); return GLIA_HMT_ERR_ARG; }
   TrainOptions o;
@@ -196,7 +206,9 @@ int glia_hmt_forest_train(glia_hmt_ctx* c, const double* h_rows, int64_t n_rows,
   if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_ARG; }
   GLIA_HIP_TRY(hipSetDevice(c->device));
   glia_hmt_forest_model* m = new glia_hmt_forest_model;
-  const int rc = forest_train_device(h_rows, n_rows, dim, plan, o, c->stream, &m->m, &c->trt);
+  OobOptions oo;
+  if (oob_opts) { oo.oob = oob_opts->oob ? 1 : 0; oo.importance = oob_opts->importance ? 1 : 0; }
+  const int rc = forest_train_device(h_rows, n_rows, dim, plan, o, c->stream, &m->m, &c->trt, &oo, &c->obt);
   if (rc) { delete m; return rc; }
   *out = m;
   return GLIA_HMT_OK;
@@ -241,6 +253,48 @@ int glia_hmt_forest_model_arrays(const glia_hmt_forest_model* m, double* xbestsp
   return GLIA_HMT_OK;
 }
 
+int glia_hmt_forest_model_oob_sizes(const glia_hmt_forest_model* m, int64_t* n_rows, int* dim, int* has_oob, int* has_importance) {
+  if (!m) { set_error("forest_model_oob_sizes: NULL model"); return GLIA_HMT_ERR_ARG; }
+  if (!m->m.has_oob() && !m->m.has_importance()) { set_error("forest_model_oob_sizes: the model holds no out-of-bag arrays"); return GLIA_HMT_ERR_ARG; }
+  if (n_rows) *n_rows = m->m.oob_rows;
+  if (dim) *dim = m->m.oob_dim;
+  if (has_oob) *has_oob = m->m.has_oob() ? 1 : 0;
+  if (has_importance) *has_importance = m->m.has_importance() ? 1 : 0;
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_forest_model_oob_arrays(const glia_hmt_forest_model* m, int* outcl, int* counttr, int* votes, int* oob_times, double* errtr,
+                                     int64_t* err_wrong, int64_t* err_seen, double* importance, double* importanceSD) {
+  if (!m) { set_error("forest_model_oob_arrays: NULL model"); return GLIA_HMT_ERR_ARG; }
+  const ForestModel& f = m->m;
+  if (!f.has_oob() && !f.has_importance()) { set_error("forest_model_oob_arrays: the model holds no out-of-bag arrays"); return GLIA_HMT_ERR_ARG; }
+  auto put = [](auto* dst, const auto& v) { if (dst && !v.empty()) memcpy(dst, v.data(), sizeof(v[0]) * v.size()); };
+  static_assert(sizeof(long long) == sizeof(int64_t), "err_wrong / err_seen are copied as they are");
+  put(outcl, f.outcl); put(counttr, f.counttr); put(votes, f.votes); put(oob_times, f.oob_times); put(errtr, f.errtr);
+  put(err_wrong, f.err_wrong); put(err_seen, f.err_seen); put(importance, f.importance); put(importanceSD, f.importanceSD);
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_forest_model_set_oob(glia_hmt_forest_model* m, int64_t n_rows, int dim, const int* outcl, const int* counttr, const int* votes,
+                                  const int* oob_times, const double* errtr, const double* importance, const double* importanceSD) {
+  if (!m || n_rows < 1 || n_rows >= (1ll << 28) || dim < 1 || (!outcl && !importance) || (outcl && (!counttr || !votes || !oob_times || !errtr)) ||
+      (importance && !importanceSD)) {
+    set_error("forest_model_set_oob: invalid argument");
+    return GLIA_HMT_ERR_ARG;
+  }
+  ForestModel& f = m->m;
+  const size_t N = (size_t)n_rows, nc = (size_t)f.nclass, D = (size_t)dim;
+  f.oob_rows = n_rows; f.oob_dim = dim;
+  f.outcl.clear(); f.counttr.clear(); f.votes.clear(); f.oob_times.clear(); f.errtr.clear(); f.err_wrong.clear(); f.err_seen.clear();
+  f.importance.clear(); f.importanceSD.clear();
+  if (outcl) {
+    f.outcl.assign(outcl, outcl + N); f.counttr.assign(counttr, counttr + nc * N); f.votes.assign(votes, votes + nc * N);
+    f.oob_times.assign(oob_times, oob_times + N); f.errtr.assign(errtr, errtr + (size_t)f.ntree * (nc + 1));
+  }
+  if (importance) { f.importance.assign(importance, importance + D * (nc + 2)); f.importanceSD.assign(importanceSD, importanceSD + D * (nc + 1)); }
+  return GLIA_HMT_OK;
+}
+
 int glia_hmt_forest_model_write(const glia_hmt_forest_model* m, const char* path) {
   if (!m || !path) { set_error("forest_model_write: NULL argument"); return GLIA_HMT_ERR_ARG; }
   const std::string bad = write_forest_model(m->m, path);
@@ -268,6 +322,12 @@ int glia_hmt_forest_from_model(glia_hmt_ctx* c, const glia_hmt_forest_model* m, 
 int glia_hmt_last_forest_train_timing(const glia_hmt_ctx* c, glia_hmt_forest_train_timing* out) {
   if (!c || !out) { set_error("last_forest_train_timing: NULL argument"); return GLIA_HMT_ERR_ARG; }
   *out = c->trt;
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_last_forest_oob_timing(const glia_hmt_ctx* c, glia_hmt_forest_oob_timing* out) {
+  if (!c || !out) { set_error("last_forest_oob_timing: NULL argument"); return GLIA_HMT_ERR_ARG; }
+  *out = c->obt;
   return GLIA_HMT_OK;
 }
 

@@ -24,6 +24,7 @@ struct glia_hmt_ctx {
   double transform_ms = 0;
   glia_hmt_eval_timing evt = {0, 0, 0};   // the last glia_hmt_label_overlap / glia_hmt_eval call
   glia_hmt_forest_train_timing trt = {};  // the last glia_hmt_forest_train call
+  glia_hmt_forest_oob_timing obt = {};    // its out-of-bag passes (glia_hmt_forest_train_oob)
   glia_hmt_mlp_train_timing mlt = {};     // the last glia_hmt_mlp_train call
   glia_hmt_sshmt_train_timing sst = {};   // the last glia_hmt_sshmt_train call
   int tz = kTZ;                  // tile depth of the accumulation pass; halved when the LDS tables of a pass overflowed a lot

@@ -25,6 +25,17 @@ struct ForestModel {
   std::vector<int> ndbigtree;       // [ntree]
   std::vector<double> classwt, cutoff;               // [nclass]
   std::vector<int> orig_labels, new_labels;          // [nclass]
+  // Optional: what the trainer learned on rows its trees did not see (the slots of ml/rf/ml_rf.h:131-156, shaped as
+  // ml/rf/ml_rf_train.cxx:728-784 leaves them).  oob_rows == 0: none; importance.empty(): no importance.
+  int64_t oob_rows = 0;             // N
+  int oob_dim = 0;                  // D
+  std::vector<int> outcl, oob_times;                 // [N]: 1-based class of the most out-of-bag votes (0: never out of bag), their number
+  std::vector<int> counttr, votes;                   // [nclass][N] and the same counts as [N][nclass]
+  std::vector<double> errtr;                         // [ntree][nclass + 1]: error over trees 0..t, all rows and per class
+  std::vector<long long> err_wrong, err_seen;        // [ntree][nclass + 1]: the integers errtr divides (not in the file)
+  std::vector<double> importance, importanceSD;      // [D][nclass + 2], [D][nclass + 1]
+  bool has_oob() const { return oob_rows > 0 && !outcl.empty(); }
+  bool has_importance() const { return oob_rows > 0 && !importance.empty(); }
 };
 
 struct TrainOptions {
@@ -104,7 +115,8 @@ constexpr size_t kHeaderBytes = 520;
 // offsets of the int n[2] pairs / scalars inside the struct dump (x86-64, libstdc++; forest.cpp reads the same ones)
 constexpr size_t O_NRNODES = 128, O_NTREE = 132, O_N_XBEST = 144, O_N_CLASSWT = 160, O_N_CUTOFF = 176, O_N_TREEMAP = 192,
                  O_N_NODESTATUS = 208, O_N_NODECLASS = 224, O_N_BESTVAR = 240, O_N_NDBIGTREE = 256, O_MTRY = 264, O_N_ORIG = 280,
-                 O_N_NEW = 296, O_NCLASS = 304;
+                 O_N_NEW = 296, O_NCLASS = 304, O_N_OUTCL = 320, O_N_COUNTTR = 352, O_N_IMPORTANCE = 416, O_N_IMPORTANCESD = 432,
+                 O_N_ERRTR = 448, O_N_VOTES = 496, O_N_OOB_TIMES = 512;
 // writeArray (ml_rf_model.cxx:20-46) for an array kept dense: a flag byte in front of arrays longer than 128 elements
 template <typename T> bool array(FILE* f, const T* a, size_t n) {
   if (n == 0) return true;
@@ -127,6 +139,16 @@ inline std::string model_check(const ForestModel& m) {
       m.bestvar.size() != nn || m.ndbigtree.size() != (size_t)m.ntree || m.classwt.size() != (size_t)m.nclass ||
       m.cutoff.size() != (size_t)m.nclass || m.orig_labels.size() != (size_t)m.nclass || m.new_labels.size() != (size_t)m.nclass)
     return "forest_model: inconsistent array sizes";
+  const size_t N = (size_t)m.oob_rows, nc = (size_t)m.nclass, D = (size_t)m.oob_dim;
+  if (m.oob_rows < 0 || m.oob_rows >= (1ll << 28) || m.oob_dim < 0) return "forest_model: inconsistent out-of-bag sizes";
+  if (m.has_oob() && (m.outcl.size() != N || m.oob_times.size() != N || m.counttr.size() != nc * N || m.votes.size() != nc * N ||
+                      m.errtr.size() != (size_t)m.ntree * (nc + 1)))
+    return "forest_model: inconsistent out-of-bag array sizes";
+  if (!m.has_oob() && !(m.outcl.empty() && m.oob_times.empty() && m.counttr.empty() && m.votes.empty() && m.errtr.empty()))
+    return "forest_model: inconsistent out-of-bag array sizes";
+  if (!m.importance.empty() && (m.oob_rows <= 0 || D == 0 || m.importance.size() != D * (nc + 2) || m.importanceSD.size() != D * (nc + 1)))
+    return "forest_model: inconsistent importance array sizes";
+  if (m.importance.empty() && !m.importanceSD.empty()) return "forest_model: inconsistent importance array sizes";
   return std::string();
 }
 
@@ -143,6 +165,13 @@ inline std::string write_forest_model(const ForestModel& m, const char* path) {
   n2(O_N_TREEMAP, m.nrnodes, 2 * m.ntree); n2(O_N_NODESTATUS, m.nrnodes, m.ntree); n2(O_N_NODECLASS, m.nrnodes, m.ntree);
   n2(O_N_BESTVAR, m.nrnodes, m.ntree); n2(O_N_NDBIGTREE, m.ntree, 1); n2(O_N_ORIG, m.nclass, 1); n2(O_N_NEW, m.nclass, 1);
   n1(O_NRNODES, m.nrnodes); n1(O_NTREE, m.ntree); n1(O_MTRY, m.mtry); n1(O_NCLASS, m.nclass);
+  // the out-of-bag slots, n[2] as ml_rf_train.cxx:728-784 sets them: a transposed array is {columns, rows} of classRF's, errtr and votes
+  // keep {rows, columns}; the slots between them (outclts, proximities, localImp, errts, inbag) stay empty
+  const int N = (int)m.oob_rows;
+  if (m.has_oob()) {
+    n2(O_N_OUTCL, N, 1); n2(O_N_COUNTTR, m.nclass, N); n2(O_N_ERRTR, m.ntree, m.nclass + 1); n2(O_N_VOTES, N, m.nclass); n2(O_N_OOB_TIMES, N, 1);
+  }
+  if (m.has_importance()) { n2(O_N_IMPORTANCE, m.oob_dim, m.nclass + 2); n2(O_N_IMPORTANCESD, m.oob_dim, m.nclass + 1); }
   FILE* f = fopen(path, "wb");
   if (!f) return std::string("Error: cannot create file ") + path;
   const size_t n0 = (size_t)m.nrnodes, nt = (size_t)m.ntree, nn = n0 * nt;
@@ -158,6 +187,10 @@ inline std::string write_forest_model(const ForestModel& m, const char* path) {
   ok = ok && fwrite(&m.mtry, 4, 1, f) == 1;
   ok = ok && array(f, m.orig_labels.data(), m.orig_labels.size()) && array(f, m.new_labels.data(), m.new_labels.size());
   ok = ok && fwrite(&m.nclass, 4, 1, f) == 1;
+  if (m.has_oob()) ok = ok && array(f, m.outcl.data(), m.outcl.size()) && array(f, m.counttr.data(), m.counttr.size());      // ml_rf_model.cxx:428-432
+  if (m.has_importance()) ok = ok && array(f, m.importance.data(), m.importance.size()) && array(f, m.importanceSD.data(), m.importanceSD.size());   // :439-442
+  if (m.has_oob()) ok = ok && array(f, m.errtr.data(), m.errtr.size()) && array(f, m.votes.data(), m.votes.size()) &&       // :443-448
+                        array(f, m.oob_times.data(), m.oob_times.size());
   ok = (fclose(f) == 0) && ok;
   return ok ? std::string() : std::string("Error: cannot write file ") + path;
 }

@@ -21,6 +21,8 @@
 //   k_partition  one thread per row: the winning segment IS the node's rows in split order, so the stable partition is a copy in that
 //                order; the daughters' class counts are integer atomic adds (summed per wave first where a wave is inside one daughter)
 // and one 8-byte read-back: nodes and rows of the next level.
+// When the call asks for the out-of-bag error or the importances, the passes of forest_oob.hip run on every batch after
+// its last level, on the rows, the bootstrap counts and the trees this file still holds on the device; they change nothing here.
 #include <chrono>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -360,10 +362,13 @@ __global__ void __launch_bounds__(256) k_partition(TrainDev d, const NodeRec* no
 }  // namespace
 
 int forest_train_device(const double* h_x, int64_t N, int D, const TrainPlan& plan, const TrainOptions& opts, hipStream_t stream, ForestModel* out,
-                        glia_hmt_forest_train_timing* tm) {
+                        glia_hmt_forest_train_timing* tm, const OobOptions* oob, glia_hmt_forest_oob_timing* otm) {
   const auto wall0 = std::chrono::steady_clock::now();
   const bool trace = option("GLIA_HMT_TRACE");
   memset(tm, 0, sizeof(*tm));
+  if (otm) memset(otm, 0, sizeof(*otm));
+  const OobOptions oo = oob ? *oob : OobOptions();
+  const bool with_oob = oo.oob || oo.importance;
   const int mtry = plan.mtry, nclass = plan.nclass, ntree = opts.ntree;
   const uint64_t per_tree = (uint64_t)std::min<int64_t>(plan.sampsize, N);      // distinct in-bag rows of a tree, at most
   const uint64_t cap = 2 * per_tree - 1;                                         // nodes of a tree, at most
@@ -376,6 +381,7 @@ int forest_train_device(const double* h_x, int64_t N, int D, const TrainPlan& pl
     b += S * (4 + 4 + 4 + 8 + 4 + 2 * 8 + 2 * 4);                                // vars, segments, results, keys x 2, positions x 2
     b += S * 8;                                                                  // rocPRIM's scratch (bounded below once it is known)
     b += T * (cap * 20 + 4);                                                     // the trees
+    b += OobPass::bytes(oo, (uint64_t)N, (uint64_t)D, (uint64_t)nclass, T, cap, (uint64_t)ntree);   // the out-of-bag passes (forest_oob.hip)
     return b;
   };
   size_t free_b = 0, total_b = 0;
@@ -449,6 +455,8 @@ int forest_train_device(const double* h_x, int64_t N, int D, const TrainPlan& pl
   std::vector<std::vector<int>> t_left((size_t)ntree), t_var((size_t)ntree), t_class((size_t)ntree);
   std::vector<std::vector<double>> t_split((size_t)ntree);
   std::vector<int> ndbig((size_t)ntree, 0);
+  OobPass oob_pass;
+  if (with_oob && (rc = oob_pass.init(oo, N, D, plan, opts, T, cap, stream, otm))) return rc;
   auto blocks = [](unsigned long long n) { return (unsigned)((n + 255) / 256); };
 
   for (int tree0 = 0; tree0 < ntree; tree0 += (int)T) {
@@ -542,6 +550,12 @@ int forest_train_device(const double* h_x, int64_t N, int D, const TrainPlan& pl
     GLIA_HIP_TRY(hipEventRecord(ev.ev[1], stream));
     GLIA_HIP_TRY(hipStreamSynchronize(stream));
     tm->ms_download += ev.ms(0, 1);
+    if (with_oob) {
+      OobBatch ob;
+      ob.X = dX; ob.ycls = dY; ob.cnt = d.cnt; ob.pos = d.pos; ob.o_left = d.o_left; ob.o_var = d.o_var; ob.o_class = d.o_class; ob.ndbig = d.ndbig;
+      ob.o_split = d.o_split; ob.tree0 = tree0; ob.T = Tb;
+      if ((rc = oob_pass.run(ob, &t_left[tree0], &t_var[tree0]))) return rc;
+    }
     if (trace)
       fprintf(stderr, "[trace] forest_train: trees %d..%d of %d done, %lld levels so far; ms: bootstrap %.2f prepare %.2f gather %.2f sort %.2f scan %.2f split %.2f partition %.2f download %.2f\n",
               tree0, tree0 + Tb - 1, ntree, (long long)tm->levels, tm->ms_bootstrap, tm->ms_prepare, tm->ms_gather, tm->ms_sort, tm->ms_scan, tm->ms_split,
@@ -569,6 +583,7 @@ int forest_train_device(const double* h_x, int64_t N, int D, const TrainPlan& pl
   m.orig_labels = plan.orig_labels;
   m.new_labels.resize(nclass);
   for (int k = 0; k < nclass; ++k) m.new_labels[k] = k + 1;
+  if (with_oob && (rc = oob_pass.finish(&m))) return rc;
   tm->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
   if (trace)
     fprintf(stderr, "[trace] forest_train: %d trees (%lld in flight, %lld batches), %lld levels, %lld launches, %.1f MiB planned, %.2f ms in all (upload %.2f)\n", ntree,

@@ -953,6 +953,16 @@ class ForestTrainTiming(C.Structure):
                [(k, C.c_int64) for k in ("levels", "launches", "batches", "trees_in_flight", "nodes")] + [("device_bytes", C.c_uint64)]
 
 
+class OobOpts(C.Structure):
+    """glia_hmt_oob_opts"""
+    _fields_ = [("oob", C.c_int), ("importance", C.c_int)]
+
+
+class ForestOobTiming(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("ms_walk", "ms_tally", "ms_importance")] + \
+               [(k, C.c_int64) for k in ("oob_rows", "walks_nominal", "walks_done")] + [("device_bytes", C.c_uint64)]
+
+
 class ForestModel:
     """A trained forest on the host (glia_hmt_forest_model): every array of the GLIA model file."""
     _TREE = (("xbestsplit", np.float64, 1), ("treemap", np.int32, 2), ("nodestatus", np.int32, 1), ("nodeclass", np.int32, 1),
@@ -994,6 +1004,32 @@ class ForestModel:
         out["mtry"] = s["mtry"]
         return out
 
+    def oob(self):
+        """dict of the out-of-bag arrays of a model trained with oob=True and / or importance=True, shaped as the model file
+        holds them: outcl [N], counttr [nclass, N], votes [N, nclass], oob_times [N], errtr [ntree, nclass + 1] with the integers it
+        divides (err_wrong, err_seen); importance [D, nclass + 2], importanceSD [D, nclass + 1].  HmtError when the model has none."""
+        n, d, has_oob, has_imp = C.c_int64(), C.c_int(), C.c_int(), C.c_int()
+        _check(lib().glia_hmt_forest_model_oob_sizes(self.h, C.byref(n), C.byref(d), C.byref(has_oob), C.byref(has_imp)))
+        s = self.sizes()
+        N, D, nc, nt = n.value, d.value, s["nclass"], s["ntree"]
+        out = {}
+        if has_oob.value:
+            out.update(outcl=np.zeros(N, np.int32), counttr=np.zeros((nc, N), np.int32), votes=np.zeros((N, nc), np.int32),
+                       oob_times=np.zeros(N, np.int32), errtr=np.zeros((nt, nc + 1)), err_wrong=np.zeros((nt, nc + 1), np.int64),
+                       err_seen=np.zeros((nt, nc + 1), np.int64))
+        if has_imp.value:
+            out.update(importance=np.zeros((D, nc + 2)), importanceSD=np.zeros((D, nc + 1)))
+        order = ("outcl", "counttr", "votes", "oob_times", "errtr", "err_wrong", "err_seen", "importance", "importanceSD")
+        _check(lib().glia_hmt_forest_model_oob_arrays(self.h, *[_np(out[k]) if k in out else None for k in order]))
+        return out
+
+    def set_oob(self, n_rows, dim, arrays):
+        """host-only: gives the model out-of-bag arrays from a dict shaped like oob()'s (glia_hmt_forest_model_set_oob)"""
+        order = (("outcl", np.int32), ("counttr", np.int32), ("votes", np.int32), ("oob_times", np.int32), ("errtr", np.float64),
+                 ("importance", np.float64), ("importanceSD", np.float64))
+        keep = [np.ascontiguousarray(arrays[k], dtype=t) if k in arrays else None for k, t in order]
+        _check(lib().glia_hmt_forest_model_set_oob(self.h, C.c_int64(n_rows), C.c_int(dim), *[_np(x) for x in keep]))
+
     def write(self, path):
         _check(lib().glia_hmt_forest_model_write(self.h, str(path).encode()))
 
@@ -1017,9 +1053,10 @@ class ForestModel:
             pass
 
 
-def train_forest(ctx, rows, labels, **opts):
+def train_forest(ctx, rows, labels, oob=False, importance=False, **opts):
     """train_rf (ml/rf/main_train_rf.cxx): grows the forest on the device by the rule of DESIGN 3.12.  rows [n, dim] float64, labels [n]
-    integers; options ntree, mtry, sample_ratio, nodesize, balance, max_depth, seed (defaults: glia_hmt_train_opts_default)."""
+    integers; options ntree, mtry, sample_ratio, nodesize, balance, max_depth, seed (defaults: glia_hmt_train_opts_default).  oob /
+    importance: also the out-of-bag error and the variable importances (ForestModel.oob()); the trees are the same."""
     rows = np.ascontiguousarray(rows, dtype=np.float64)
     labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
     assert rows.ndim == 2 and labels.shape[0] == rows.shape[0]
@@ -1030,7 +1067,12 @@ def train_forest(ctx, rows, labels, **opts):
             raise TypeError("train_forest: unknown option " + k)
         setattr(o, k, v)
     h = C.c_void_p()
-    _check(lib().glia_hmt_forest_train(ctx.h, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(labels), C.byref(o), C.byref(h)))
+    if oob or importance:
+        oo = OobOpts(1 if oob else 0, 1 if importance else 0)
+        _check(lib().glia_hmt_forest_train_oob(ctx.h, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(labels), C.byref(o),
+                                               C.byref(oo), C.byref(h)))
+    else:
+        _check(lib().glia_hmt_forest_train(ctx.h, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(labels), C.byref(o), C.byref(h)))
     return ForestModel(ctx, h)
 
 
@@ -1038,6 +1080,13 @@ def last_forest_train_timing(ctx):
     t = ForestTrainTiming()
     _check(lib().glia_hmt_last_forest_train_timing(ctx.h, C.byref(t)))
     return {k: getattr(t, k) for k, _ in ForestTrainTiming._fields_}
+
+
+def last_forest_oob_timing(ctx):
+    """the out-of-bag passes of the last train_forest call (all zero when it asked for neither)"""
+    t = ForestOobTiming()
+    _check(lib().glia_hmt_last_forest_oob_timing(ctx.h, C.byref(t)))
+    return {k: getattr(t, k) for k, _ in ForestOobTiming._fields_}
 
 
 class Slab(C.Structure):

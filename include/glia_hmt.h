@@ -393,6 +393,46 @@ typedef struct {
   uint64_t device_bytes;     /* device memory planned for the call */
 } glia_hmt_forest_train_timing;
 int glia_hmt_last_forest_train_timing(const glia_hmt_ctx* ctx, glia_hmt_forest_train_timing* out);
+/* Out-of-bag error and variable importance: classRF's outputs errtr, outcl, counttr, votes, oob_times, importance and importanceSD
+ * (sized at ml/rf/ml_rf_train.cxx:112-159, kept in the model at ml/rf/ml_rf.h:131-156).  As with the trees, the values are this
+ * library's own deterministic definition; classRF's sources are not in the reference tree and no parity is claimed.
+ * oob: the votes of the trees a row is outside the bag of, and the error per tree; importance: mean decrease in accuracy under a
+ * permutation of the out-of-bag rows, per class and overall, its standard error, and the mean decrease in Gini (the doImportance
+ * switch of ml/rf/ml_rf_train.cxx:112-130).  Both 0: exactly glia_hmt_forest_train. */
+typedef struct {
+  int oob;                /* 0 */
+  int importance;         /* 0 */
+} glia_hmt_oob_opts;
+void glia_hmt_oob_opts_default(glia_hmt_oob_opts* opts);
+/* glia_hmt_forest_train with the out-of-bag passes after every batch of trees; oob_opts NULL = neither.  The model's trees are those of
+ * glia_hmt_forest_train with the same train_opts (rf_old::train, ml/rf/ml_rf_train.cxx:234). */
+int glia_hmt_forest_train_oob(glia_hmt_ctx* ctx, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels,
+                              const glia_hmt_train_opts* train_opts, const glia_hmt_oob_opts* oob_opts, glia_hmt_forest_model** out);
+/* The sizes the out-of-bag arrays are shaped by (ml/rf/ml_rf_train.cxx:728-784): rows and columns of the training call, and which of
+ * the two groups the model holds.  GLIA_HMT_ERR_ARG when it holds neither.  Any pointer may be NULL. */
+int glia_hmt_forest_model_oob_sizes(const glia_hmt_forest_model* model, int64_t* n_rows, int* dim, int* has_oob, int* has_importance);
+/* Copies the arrays (ml/rf/ml_rf.h:131-156): outcl [n_rows] (1-based class, 0 = never out of bag), counttr [nclass][n_rows], votes
+ * [n_rows][nclass], oob_times [n_rows], errtr [ntree][nclass + 1] with the integers it divides err_wrong, err_seen [ntree][nclass + 1]
+ * (not part of rf_old::Model), importance [dim][nclass + 2] (per class, all, Gini), importanceSD [dim][nclass + 1].  Any pointer may be
+ * NULL; a group the model does not hold is left untouched.  GLIA_HMT_ERR_ARG when it holds neither. */
+int glia_hmt_forest_model_oob_arrays(const glia_hmt_forest_model* model, int* outcl, int* counttr, int* votes, int* oob_times, double* errtr,
+                                     int64_t* err_wrong, int64_t* err_seen, double* importance, double* importanceSD);
+/* Host-only (tests, converters): gives a model its out-of-bag arrays, shaped as above (the slots of ml/rf/ml_rf.h:131-156).  The group
+ * outcl / counttr / votes / oob_times / errtr is set when outcl is not NULL (then all five are needed), importance / importanceSD when
+ * importance is not NULL; err_wrong / err_seen are left empty.  Replaces what the model held. */
+int glia_hmt_forest_model_set_oob(glia_hmt_forest_model* model, int64_t n_rows, int dim, const int* outcl, const int* counttr, const int* votes,
+                                  const int* oob_times, const double* errtr, const double* importance, const double* importanceSD);
+/* the out-of-bag passes of the last glia_hmt_forest_train_oob call of this context (device times from events; all zero after a call
+ * with neither option): the walk of the out-of-bag rows (with the node table and the leaves' in-bag counts), the tally of votes and
+ * errors, the permuted walks of the importance.  walks_nominal = sum over trees of out-of-bag rows x columns, walks_done = the walks
+ * made after the rule that a variable a row's path never tests needs none (replaces classRF's own timing, none in the reference). */
+typedef struct {
+  double ms_walk, ms_tally, ms_importance;
+  int64_t oob_rows;          /* out-of-bag rows over all trees */
+  int64_t walks_nominal, walks_done;
+  uint64_t device_bytes;     /* device memory the passes add to the plan */
+} glia_hmt_forest_oob_timing;
+int glia_hmt_last_forest_oob_timing(const glia_hmt_ctx* ctx, glia_hmt_forest_oob_timing* out);
 
 /* ---- training the MLP / logsig classifier --------------------------------------------------------------
  * Replaces the supervised part of train_sshmt_mlp / train_sshmt_logsig (sshmt/main_train_sshmt_mlp.cxx:96-168): the energy
