@@ -870,27 +870,35 @@ __device__ __forceinline__ void stage_regions(const BcState& st, const ScoreWs& 
 // entries -- four to six DEPENDENT loads.  One lane per (record, channel) doing both is ~4 k cycles per entry; at 1024^3 a job nearly
 // always holds a record with 4 .. 15 entries (+15 .. 60 k cycles on the answer the loop waits for), and a few thousand records late
 // in the run hold hundreds to thousands (millions of cycles each: profiles/r04z_bc1024_fragile.txt).  A helper's LAST WAVE therefore
-// owns the shared sets: lane i only WALKS the list of (record, channel) pair i (one load per entry), appending to ONE work list in
-// LDS; then the wave's 64 lanes take the list's entries, decide aliveness and add the statistics to the pair's accumulator with LDS
-// atomics; long lists go round in batches of kFragCap.  All of it inside one wave -- no workgroup barrier -- while the other waves
-// scan the neighbour lists.  The helpers' copy of the mark table's LDS (never used by a helper) holds the lists.
+// owns the shared sets, in three steps per batch of kFragCap entries, all of it inside one wave -- no workgroup barrier -- while
+// the other waves scan the neighbour lists:
+//   walk   lane i WALKS the list of (record, channel) pair i (one load per entry), appending to ONE work list in LDS.  The wave
+//          walks in step: in round t the lanes that still have an entry take consecutive slots in lane order (a ballot, no atomic),
+//          so a lane's slots are a function of the lanes' entry counts alone;
+//   test   the wave's 64 lanes take the list's entries, decide aliveness, note it in the slot's tag, and add the ORDER-FREE
+//          statistics (counts, thresholds, histogram, extremes) to the pair's accumulator with LDS atomics;
+//   fold   the rounds of the walk are gone through again from the counts: lane i meets its own slots in chain order and adds the
+//          f64 sum and sq of the alive ones onto its running (A + sh), one by one.  That is the ONE ASSOCIATION of these sums
+//          ("One association"): ((A + sh) + e1) + e2 ..., the alive entries in chain order, as score_chunk<false> and
+//          shared_boundary() add them -- floating-point sums through atomics would depend on the route and on the hardware's order.
+//          The running sums stay in registers across batches.
+// The helpers' copy of the mark table's LDS (never used by a helper) holds the lists.
 constexpr uint32_t kFragCap = 4096;        // work-list entries per batch
 constexpr uint32_t kFragItems = kHelpChunk * kMaxChannels;
-struct FragAcc { uint32_t n, thr[GLIA_HMT_MAX_THRESH], mn_ord, mx_ord; double sum, sq; uint32_t hist[GLIA_HMT_MAX_BINS]; };
-static_assert(sizeof(FragAcc) == sizeof(EStats), "same fields, extremes as ordered integers");
-struct FragWs { FragAcc* acc; uint32_t* ids; unsigned char* tag; uint32_t* total; };
-static_assert(kFragItems * sizeof(FragAcc) + kFragCap * 5u + 16u <= kMarkBytes, "fits the mark table's LDS");
+constexpr uint32_t kFragAlive = 0x80u;     // in a slot's tag, beside the pair's lane (< 64)
+struct FragAcc { uint32_t n, thr[GLIA_HMT_MAX_THRESH], mn_ord, mx_ord; uint32_t hist[GLIA_HMT_MAX_BINS]; };      // EStats without sum and sq, extremes as ordered integers
+struct FragWs { FragAcc* acc; uint32_t* ids; unsigned char* tag; };
+static_assert(kFragItems * sizeof(FragAcc) + kFragCap * 5u <= kMarkBytes, "fits the mark table's LDS");
 static_assert(kFragItems <= 64u, "one lane per (record, channel) pair");
 __device__ __forceinline__ FragWs frag_ws(unsigned char* pool) {
   FragWs f;
   f.acc = reinterpret_cast<FragAcc*>(pool + kWsBytes);
   f.ids = reinterpret_cast<uint32_t*>(f.acc + kFragItems);
-  f.total = f.ids + kFragCap;
-  f.tag = reinterpret_cast<unsigned char*>(f.total + 4);
+  f.tag = reinterpret_cast<unsigned char*>(f.ids + kFragCap);
   return f;
 }
 __device__ __forceinline__ void frag_clear(FragAcc& a) {
-  a.n = 0; a.mn_ord = 0xFFFFFFFFu; a.mx_ord = 0u; a.sum = 0.0; a.sq = 0.0;
+  a.n = 0; a.mn_ord = 0xFFFFFFFFu; a.mx_ord = 0u;
   for (int i = 0; i < GLIA_HMT_MAX_THRESH; ++i) a.thr[i] = 0;
   for (int i = 0; i < GLIA_HMT_MAX_BINS; ++i) a.hist[i] = 0;
 }
@@ -1024,42 +1032,70 @@ __device__ __forceinline__ bool score_chunk(const BcState& st, BcShared& s, cons
     const FragWs F = frag_ws(s.pool);
     const uint32_t lane = (uint32_t)tid & 63u, items = n * (uint32_t)K;
     const bool mine = lane < items && W.hdr[lane / (uint32_t)K].on != 0u;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const EStats* le_stats = chan_of(st, (int)(lane % (uint32_t)K)).le_stats;
     uint32_t f = mine ? W.hdr[lane / (uint32_t)K].fhead : kNone;
+    double fsum = 0.0, fsq = 0.0;                             // (A + sh), then the alive entries one by one: estats_add's order
+    if (mine) { const RecIn& in = W.in[lane]; fsum = in.A.sum + in.sh.sum; fsq = in.A.sq + in.sh.sq; }      // (W.in is indexed [record * K + channel], as the pairs are)
     for (;;) {
-      while (f != kNone) {
-        const uint32_t pos = atomicAdd(F.total, 1u);
-        if (pos >= kFragCap) break;                       // the list is full: this entry opens the next batch
-        F.ids[pos] = f; F.tag[pos] = (unsigned char)lane;
-        f = ldm<AG>(&st.le_next[f]);
+      // walk: round by round, the lanes with an entry left take the next slots in lane order
+      uint32_t tot = 0u, cnt = 0u;
+      for (;;) {
+        const unsigned long long m = __ballot(f != kNone);
+        if (m == 0ull || tot >= kFragCap) break;              // (a full list: the entries left open the next batch)
+        const uint32_t pos = tot + (uint32_t)__popcll(m & below);
+        if (f != kNone && pos < kFragCap) { F.ids[pos] = f; F.tag[pos] = (unsigned char)lane; f = ldm<AG>(&st.le_next[f]); ++cnt; }
+        tot += (uint32_t)__popcll(m);
       }
-      wave_lds_fence();
-      const uint32_t tot = *F.total < kFragCap ? *F.total : kFragCap;
+      tot = tot < kFragCap ? tot : kFragCap;
       const bool more = __ballot(f != kNone) != 0ull;
+      wave_lds_fence();
+      // test
       for (uint32_t k = lane; k < tot; k += 64u) {
         const uint32_t e = F.ids[k], q = F.tag[k];
         if (!leaf_alive<AG>(st, st.le_dst[e])) continue;
+        F.tag[k] = (unsigned char)(q | kFragAlive);
         const EStats es = chan_of(st, (int)(q % (uint32_t)K)).le_stats[e];
         FragAcc& a = F.acc[q];
         atomicAdd(&a.n, es.n);
 #pragma unroll
         for (int i = 0; i < GLIA_HMT_MAX_THRESH; ++i) if (es.thr[i]) atomicAdd(&a.thr[i], es.thr[i]);
         atomicMin(&a.mn_ord, float_ord(es.mn)); atomicMax(&a.mx_ord, float_ord(es.mx));
-        atomicAdd(&a.sum, es.sum); atomicAdd(&a.sq, es.sq);
 #pragma unroll
         for (int i = 0; i < GLIA_HMT_MAX_BINS; ++i) if (es.hist[i]) atomicAdd(&a.hist[i], es.hist[i]);
       }
       wave_lds_fence();
-      if (lane == 0u) *F.total = 0u;
+      // fold: the walk's rounds again -- in round t the lanes with cnt > t hold the slots from `base` on, in lane order (a lane that
+      // found the list full had the highest ranks of its round, so the ranks of the others are what they were).  Four rounds' loads
+      // are in flight together.
+      for (uint32_t t0 = 0u, base = 0u; ; t0 += 4u) {
+        if (__ballot(t0 < cnt) == 0ull) break;
+        double vs[4], vq[4];
+        bool live[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const bool have = t0 + (uint32_t)u < cnt;
+          const unsigned long long m = __ballot(have);
+          const uint32_t pos = base + (uint32_t)__popcll(m & below);
+          base += (uint32_t)__popcll(m);
+          live[u] = have && (F.tag[have ? pos : 0u] & kFragAlive) != 0u;
+          vs[u] = 0.0; vq[u] = 0.0;
+          if (live[u]) { const EStats* es = &le_stats[F.ids[pos]]; vs[u] = es->sum; vq[u] = es->sq; }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) if (live[u]) { fsum += vs[u]; fsq += vq[u]; }
+      }
       wave_lds_fence();
       if (!more) break;
     }
     if (mine) {
-      RecIn& in = W.in[lane];                              // (W.in is indexed [record * K + channel], as the pairs are)
+      RecIn& in = W.in[lane];
       EStats sh = in.A;
       estats_add(sh, in.sh);
+      sh.sum = fsum; sh.sq = fsq;
       FragAcc& a = F.acc[lane];
       if (a.n) {
-        sh.n += a.n; sh.sum += a.sum; sh.sq += a.sq;
+        sh.n += a.n;
         sh.mn = fminf(sh.mn, ord_float(a.mn_ord)); sh.mx = fmaxf(sh.mx, ord_float(a.mx_ord));
         for (int i = 0; i < GLIA_HMT_MAX_THRESH; ++i) sh.thr[i] += a.thr[i];
         for (int i = 0; i < GLIA_HMT_MAX_BINS; ++i) sh.hist[i] += a.hist[i];
@@ -1237,7 +1273,6 @@ __device__ __forceinline__ void bc_helper_loop(const BcState& st, BcShared& s) {
   const uint32_t cap = W.cap;
   if (tid == 0) s.nlog = (uint32_t)feat::log_slots(st.cfg, s.logpos);
   if ((uint32_t)tid < kFragItems) frag_clear(frag_ws(s.pool).acc[tid]);
-  if (tid == 0) *frag_ws(s.pool).total = 0u;
   for (int i = tid; i < glibc::kLog2TabWords; i += kBcThreads) s.log2tab[i] = i < 18 ? glibc::kLog2Head[i] : i < 18 + 128 ? glibc::kLog2Tab[i - 18] : glibc::kLog2Tab2[i - 18 - 128];
   uint32_t last = 0;
   for (;;) {

@@ -12,6 +12,8 @@ pixels beside and above / below a right half point at it without an answer.  Onl
 the right halves' entries are the ones whose membership in a shared boundary depends on the state of the merge forest.
 
 fragile_comb_image(n): one record whose shared boundary holds n fragile leaf pairs, half of them dead when its edge pops.
+fragile_comb_image_f32(n): the same labels under float32 values (the Q8 values plus a jitter below half a Q8 step), whose f64 sums of
+squares depend on the order of the additions.
 touching_comb_image(gy, gx, m, m2): a thin hub whose hub touches every region, so that a contraction has as many list entries as the
 image has regions while only gy gx regions ever merge.  Their docstrings go through the contacts.
 
@@ -117,6 +119,21 @@ def fragile_comb_image(n, ysplit=1, ycol=(170, 192), seed=20251021):
         q8[c - 1:c + 1, 6] = 179
     assert len(np.unique(lab)) == 2 * n + 1 + ysplit
     return lab, (q8 / 256.0).astype(np.float32)
+
+
+def fragile_comb_image_f32(n, ysplit=1, ycol=(170, 192), seed=20251021, jitter_seed=1, width=2.0 ** -9):
+    """fragile_comb_image's labels, and every pixel its Q8 value plus a seeded jitter in [0, width), width <= 2^-9, drawn with more
+    bits than a float has and rounded once: a float32 with a full 24-bit mantissa.  A pixel stays inside its Q8 step [q, q + 1/256),
+    so every value band of fragile_comb_image's docstring is kept -- column 5 beside the cells stays in [ycol) / 256 within [0.5, 0.75)
+    -- and with them the shape of the order.  What changes is the arithmetic: the values of [0.5, 1) are multiples of 2^-24, whose
+    plain sums are still exact in double, but a square needs 48 bits and the sum of a few dozen squares more than 53; the values
+    below 2^-2 (the W | X contacts) have finer steps, and their plain sums are inexact too."""
+    assert 0.0 < width <= 2.0 ** -9
+    lab, q8 = fragile_comb_image(n, ysplit, ycol, seed)
+    jitter = np.random.default_rng(jitter_seed).random(q8.shape) * width
+    pb = (q8.astype(np.float64) + jitter).astype(np.float32)
+    assert (np.floor(pb.astype(np.float64) * 256.0) == q8.astype(np.float64) * 256.0).all(), "a pixel left its Q8 step"
+    return lab, pb
 
 
 def touching_comb_image(gy, gx, m, m2=None, levels=None):

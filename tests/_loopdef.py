@@ -11,6 +11,7 @@ tests/test_gpu_wide_linkages.py holds the device to this file where it cannot.
     step = check(labels, image, order, sal)              # first step that breaks a rule, or -1
     st = stats(labels, image)                            # per merge: neighbour counts, list lengths, new edges, fragile pairs
     step, n, alive = chain_at_pop(labels, image, order, key)   # the fragile chain of the edge that merges leaf `key` away
+    step, pairs, alive = chain_entries_at_pop(labels, image, order, key)   # ... its entries in the device's chain order
 
 Rules, each with the place in the reference (glia/code/...) it restates:
   leaf pairs      _featdef.leaf_lists: the directed pair (own label, first differing valid neighbour) of every boundary voxel.
@@ -266,6 +267,40 @@ def chain_at_pop(labels, image, order, key, mask=None, leaves=None):
         if key in (a, b):
             return (i,) + rp.fragile_chain(r0, r1)
         rp.merge(r0, r1)
+    return None
+
+
+def chain_entries_at_pop(labels, image, order, key, mask=None, leaves=None):
+    """(the step of `order` that merges the region with label `key` away, the fragile pairs (a, b) -- leaf labels -- between the two
+    merged regions in the order of the device's chain, whether each is alive).  The chain's order is structural: a record of two
+    leaves starts with its one fragile pair (a leaf pair has at most one non-mutual direction); when r0 < r1 become r2, a neighbour's
+    record with r2 takes the chain of its record with r0 followed by that of its record with r1 (greedy_bc.hip, "the fragile-entry
+    chains of the parents, concatenated in (r0 side, r1 side) order").  No float goes into it."""
+    rp = Replay(labels, image, mask, leaves=leaves)
+    chains = {}                                   # region -> {other region -> list of pair indices}, the same list from both sides
+    for i in np.flatnonzero(rp.fragile).tolist():
+        a, b = int(rp.pa[i]), int(rp.pb[i])
+        lst = [i]
+        chains.setdefault(a, {})[b] = lst
+        chains.setdefault(b, {})[a] = lst
+    for step, (a, b, _) in enumerate(np.asarray(order).tolist()):
+        r0, r1 = rp.rid(a), rp.rid(b)
+        if key in (a, b):
+            entries = chains.get(r0, {}).get(r1, [])
+            ra, rb = rp.reg[rp.pa], rp.reg[rp.pb]
+            own = np.bincount(rp.pa[~(rp.has_rev & (ra == rb))], minlength=rp.L)
+            return step, [rp.pair_keys[i] for i in entries], [bool(own[rp.pb[i]] > 0) for i in entries]
+        r2 = rp.merge(r0, r1)
+        new = {}
+        for side, partner in ((r0, r1), (r1, r0)):
+            for other, lst in chains.pop(side, {}).items():
+                if other != partner:
+                    new[other] = new[other] + lst if other in new else lst
+                    del chains[other][side]
+        for other, lst in new.items():
+            chains[other][r2] = lst
+        if new:
+            chains[r2] = new
     return None
 
 

@@ -105,6 +105,54 @@ def test_random_forest_matches_oracle(ctx, shape, S, G, ntree, depth):
         assert (o2 == o_ref).all() and (s2 == s_ref).all(), env
 
 
+def _forest_at_observed_values(rng, ntree, depth, rows):
+    """_rf.random_forest with every split moved ONTO an observed value of its column (the largest one not above the midpoint it was
+    drawn at): a record whose column differs from another route's in the last bit goes down the other branch"""
+    import _rf
+    forest = _rf.random_forest(rng, ntree, depth, rows)
+    cols = [np.unique(rows[:, v]) for v in range(rows.shape[1])]
+    for t, k in zip(*np.nonzero(forest["nodestatus"] == 1)):
+        col = cols[forest["bestvar"][t, k] - 1]
+        forest["xbestsplit"][t, k] = col[max(int(np.searchsorted(col, forest["xbestsplit"][t, k], side="right")) - 1, 0)]
+    return forest
+
+
+def test_no_setting_changes_a_result_on_a_float32_volume(ctx):
+    """include/glia_hmt.h: "No setting changes a result."  On Q8 volumes every f64 sum is exact and no order of additions can show;
+    here the volume is synth's variant=1 (float32 values, inexact sums) and the forest's splits sit AT values the columns take in a
+    stub run, so a last-bit difference between two routes is a different vote.  One map object (the RAG pass has a documented
+    run-to-run freedom in the last bit of inexact sums): order, saliencies and popped rows are byte-identical under every helper
+    count, both other kernel instances and the smallest capacities, and the saliencies are the forest's values of the returned
+    rows.  Nothing is compared with the oracle (test_stub_scorer_matches_oracle does that, within 1e-5)."""
+    from glia_amd import hmt
+    from oracle import pyoracle as O
+    import _rf
+    labels, pb = O.synth((33, 30, 40), 5, 20, variant=1)
+    assert np.unique(np.round(pb.astype(np.float64) * 256) - pb.astype(np.float64) * 256).size > 100, "not a Q8 volume"
+    before = hmt.Context.internal_errors()
+    rm = _gpu_rm(ctx, labels, pb, bins=16)
+    _, _, f0 = rm.merge_order_bc(hmt.FeatureStubClassifier(ctx, 11 + 4 * 3 + 7 + 1), want_feats=True)
+    forest = _forest_at_observed_values(np.random.default_rng(33), 63, 8, f0)
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "model.bin")
+        _rf.write_model(path, forest)
+        clf = hmt.RandomForest(ctx, path, predict_label=-1)
+    o, s, f = rm.merge_order_bc(clf, want_feats=True)
+    assert len(o) == len(np.unique(labels)) - 1 and len(np.unique(s)) > 8
+    assert (s.view(np.uint64) == clf.predict(f).view(np.uint64)).all()
+    for env in (dict(GLIA_HMT_HELPERS=0), dict(GLIA_HMT_HELPERS=5), dict(GLIA_HMT_BC_NOCOMMON=1), dict(GLIA_HMT_BC_GENERIC=1),
+                dict(GLIA_HMT_MINCAP=1)):
+        with hmt.options(**env):
+            o2, s2, f2 = rm.merge_order_bc(clf, want_feats=True)
+            p2 = clf.predict(f2)
+        assert o2.shape == o.shape and (o2 == o).all() and (s2.view(np.uint64) == s.view(np.uint64)).all(), env
+        assert _feat_bits(f2, f), env
+        assert (s2.view(np.uint64) == p2.view(np.uint64)).all(), env
+    rm.close()
+    clf.close()
+    assert hmt.Context.internal_errors() == before == 0
+
+
 @pytest.mark.parametrize("shape,S,G,ntrees", [((32, 32, 32), 8, 16, (31, 31, 31)), ((40, 36, 28), 6, 12, (15, 63, 7)), ((64, 64), 4, 16, (7, 7, 31))])
 def test_ensemble_random_forest_matches_oracle(ctx, shape, S, G, ntrees):
     """alg::EnsembleRandomForest + opt::ThresholdModelDistributor(dim0, dim1, threshold) (alg/rf.hxx:63-98,

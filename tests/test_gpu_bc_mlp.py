@@ -1,5 +1,5 @@
 """The MLP as the classifier of the merge loop (glia_hmt_merge_order_bc_mlp, merge_order_bc --bct 2; glia_amd/csrc/greedy_bc.hip:
-classify_serial for the initial edges, mlp_chunk per round).  All images are Q8.
+classify_serial for the initial edges, mlp_chunk per round).  All images are Q8 but one: the float32 volume at the end of part 3, where the loop is compared with itself.
 
 1. One-column models (tests/_bc_mlp_cases.py): the probability is a function F(mean of the shared boundary) alone, so the second
    author tests/_loopdef.py gives the expected order and saliencies, ties included -- on the hub image, whose contractions cross W.cap
@@ -330,6 +330,36 @@ def test_identities_on_a_synth_volume(ctx, model):
     if model == "ensemble":
         picked = np.unique(_mlpdef.pick(_mlpdef.prepare(f, m["mn"], m["mx"]), m["dist"])).tolist()
         assert picked == [0, 1, 2], picked
+    rm.close()
+    clf.close()
+    assert hmt.Context.internal_errors() == before == 0
+
+
+@pytest.mark.gpu
+def test_no_setting_changes_a_result_on_a_float32_volume(ctx):
+    """The one image here that is not Q8: synth's variant=1 volume of tests/test_gpu_bc.py (float32 values, inexact f64 sums, 16
+    bins).  On ONE map object (the RAG pass may differ from run to run in the last bit of an inexact sum) order, saliencies and
+    popped rows are byte-identical under the tier switches and the smallest capacities, and the saliencies are the host predictor's
+    values of the returned rows.  The MLP loop has no helper workgroups: every record is scored by the loop's own workgroup."""
+    import torch
+    from glia_amd import hmt
+    from oracle import pyoracle as O
+    labels, pb = O.synth((33, 30, 40), 5, 20, variant=1)
+    assert np.unique(np.round(pb.astype(np.float64) * 256) - pb.astype(np.float64) * 256).size > 100, "not a Q8 volume"
+    d_lab, d_pb = torch.from_numpy(labels.view(np.int32)).cuda(), torch.from_numpy(pb).cuda()
+    before = hmt.Context.internal_errors()
+    rm = hmt.RegionMap(ctx, d_lab, pb=d_pb, cfg=hmt.make_config(d_pb, rb=[(d_pb, 16, 0.0, 1.0)]))
+    names = _featdef.column_names(3, 3, [16], [], [16])
+    assert len(names) == rm.feat_dim()
+    _, _, stub_f = rm.merge_order_bc(hmt.FeatureStubClassifier(ctx, names.index("x0.b0.mean")), want_feats=True)
+    clf = _mlp(ctx, _dense_models(rm.feat_dim(), stub_f)["10+10 minmax"])
+    o, s, f = rm.merge_order_bc(clf, want_feats=True)
+    assert len(o) == len(np.unique(labels)) - 1 and len(np.unique(s)) > 8
+    assert (_bits(s) == _bits(clf.predict_host(f))).all()
+    for env in (dict(GLIA_HMT_BC_NOCOMMON=1), dict(GLIA_HMT_BC_GENERIC=1), dict(GLIA_HMT_MINCAP=1)):
+        with hmt.options(**env):
+            o2, s2, f2 = rm.merge_order_bc(clf, want_feats=True)
+        assert o2.tobytes() == o.tobytes() and s2.tobytes() == s.tobytes() and f2.tobytes() == f.tobytes(), env
     rm.close()
     clf.close()
     assert hmt.Context.internal_errors() == before == 0

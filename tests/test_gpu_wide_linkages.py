@@ -32,7 +32,8 @@ tests/test_loop_definition.py):
 test_fragile_chains_and_job_sizes_are_reached proves these sizes from the replay.
 
 The other linkages are compared with the oracle directly (0.5 s and 3 s of oracle time at 1801 regions).  Everything is Q8, every
-comparison bit for bit."""
+comparison bit for bit -- but for comb32, the fragile comb with a float32 jitter, on which the loop is compared with itself under
+every setting and with clf.predict of its own rows (the section "one association" below), bit for bit as well."""
 import os
 import tempfile
 
@@ -42,7 +43,7 @@ import pytest
 import _featdef
 import _loopdef
 import _rf
-from _hub_cases import CLASSES, fragile_comb_image, hub_image, kMargin, thin_hub_image, touching_comb_image, width_classes
+from _hub_cases import CLASSES, fragile_comb_image, fragile_comb_image_f32, hub_image, kMargin, thin_hub_image, touching_comb_image, width_classes
 
 STUB = 11 + 4 * 3 + 7 + 1          # x0.b0.mean
 kCap, kLdsCap4 = 96, 2252          # W.cap's limit; kWsBytes / (8 + 8 K) at K = 4
@@ -60,7 +61,7 @@ def _narrow_hub(grid):
 
 IMAGES = {"hub": lambda: hub_image(None), "hub4": lambda: hub_image(4), "hub36": lambda: hub_image(None, grid=36), "hub36n": lambda: _narrow_hub(36),
           "thin30": lambda: thin_hub_image(30), "thin30_4": lambda: thin_hub_image(30, 4),
-          "comb": lambda: fragile_comb_image(kCombN), "comb2": lambda: fragile_comb_image(kCombN, ysplit=2),
+          "comb": lambda: fragile_comb_image(kCombN), "comb32": lambda: fragile_comb_image_f32(kCombN), "comb2": lambda: fragile_comb_image(kCombN, ysplit=2),
           "tcomb": lambda: touching_comb_image(41, 10, 40, 39)}
 BC_CLASSES = ("several rounds, one pass", "two or three passes", "global marks", "beyond ldsCap (K = 4)")
 _cpu, _dev = {}, {}
@@ -245,6 +246,19 @@ def _stump_forest(ctx, pb):
     forest["bestvar"][:, 0] = STUB + 1
     forest["nodeclass"][:, 1], forest["nodeclass"][:, 2] = 1, 2
     return _load(ctx, forest)
+
+
+def _stump_arrays(stumps):
+    """forest arrays of one stump per (column, threshold, votes_on_le): it votes for the predicted label (-1) on x[column] <= threshold,
+    or on x[column] > threshold.  [(STUB, t, True) for t in _stumps(pb)] is _stump_forest's."""
+    n = len(stumps)
+    forest = dict(xbestsplit=np.zeros((n, 3)), treemap=np.zeros((n, 3, 2), np.int32), nodestatus=np.full((n, 3), -1, np.int32),
+                  nodeclass=np.zeros((n, 3), np.int32), bestvar=np.zeros((n, 3), np.int32), ndbigtree=np.full(n, 3, np.int32),
+                  orig_labels=np.array([-1, 1], np.int32))
+    for i, (col, thr, le) in enumerate(stumps):
+        forest["xbestsplit"][i, 0], forest["treemap"][i, 0], forest["nodestatus"][i, 0], forest["bestvar"][i, 0] = thr, (2, 3), 1, col + 1
+        forest["nodeclass"][i, 1:] = (1, 2) if le else (2, 1)
+    return forest
 
 
 def _load(ctx, forest):
@@ -543,6 +557,197 @@ def test_stump_forest_across_job_max(ctx, helpers):
 def test_stub_loop_on_the_touching_comb(ctx):
     """contractions of 16 000 list entries on the global mark arrays, 16 000 new records each"""
     _stub_run_checked(ctx, "tcomb", False, ("bc_feat_batch",))
+
+
+# ---- one association of the fragile entries' sums, on a float32 image ---------------------------------------------------------------
+# include/glia_hmt.h: "No setting changes a result."  On Q8 images every f64 sum is exact and no order of additions can show.  comb32
+# is the fragile comb with a float32 jitter (_hub_cases.fragile_comb_image_f32): hub-Y pops on a chain of 1100 entries, half alive,
+# whose squares do not add exactly.  The loop's own workgroup folds the alive entries one by one onto the mutual entries' sums; the
+# rule (DESIGN.md, "One association") is that a helper does the same.  A vote is an integer, so a last-bit difference shows only if
+# a split sits on it: four stumps are put AROUND the value the loop's own row holds for hub-Y's pop (_witness_stumps).
+kBand = 64                         # ulps on either side of the value inside which a different association is seen
+WITNESS_ENVS = [dict(), dict(GLIA_HMT_HELPERS=5), dict(GLIA_HMT_BC_NOCOMMON=1), dict(GLIA_HMT_BC_GENERIC=1), dict(GLIA_HMT_MINCAP=1)]
+
+
+def _ulps(v, d):
+    """the double d ulps above (below) the positive double v"""
+    return float((np.array([v], np.float64).view(np.int64) + d).view(np.float64)[0])
+
+
+def _witness_stumps(v, col, k=kBand):
+    """four stumps on column col that vote 2 everywhere, and 3 within k ulps of v but not AT v: x <= pred(v), x > v - (k + 1) ulp,
+    x > v, x <= v + k ulp.  Added to a forest F0 they make F1 = a monotone map of F0's votes (v0 -> (v0 + 2) / (n + 4)) for every
+    record that is not within k ulps of v, ties kept."""
+    assert v > 0.0
+    return [(col, _ulps(v, -1), True), (col, _ulps(v, -(k + 1)), False), (col, v, False), (col, _ulps(v, k), True)]
+
+
+def _comb32_folds(order):
+    """From the image alone and the chain order _loopdef reports for hub-Y's pop in `order`: (step, alive entries, dead entries,
+    sq folded serially, sq folded apart, sum folded serially, sum folded apart, pixels on the shared boundary).  An entry is the
+    pair Y -> X_i, two pixels of column 5; its sq is p1 * p1 then an FMA of p2 * p2 -- both squares are exact in f64 (24 x 24 bits), so
+    one rounding, the same in either order of the pixels.  The base is the record's mutual part: W -> Y, pixel (0, 4), and Y -> W,
+    pixel (0, 5) (two terms: commutative); hub-Y has no other non-mutual entries.  Serially: ((base + e1) + e2) + ...;
+    apart: base + (((+0.0 + e1) + e2) + ...)."""
+    lab, pb = _image("comb32")
+    step, pairs, alive = _loopdef.chain_entries_at_pop(lab, pb, order, kCombY, leaves=_cpu["leaves", "comb32"])
+    p = pb.astype(np.float64)
+    base_sq, base_sum = p[0, 4] * p[0, 4] + p[0, 5] * p[0, 5], p[0, 4] + p[0, 5]
+    ser_sq, ser_sum, apart_sq, apart_sum = base_sq, base_sum, np.float64(0.0), np.float64(0.0)
+    for (a, b), live in zip(pairs, alive):
+        assert a == kCombY and b >= 3 and (b - 3) % 2 == 0, "a chain entry is a pair Y -> X_i"
+        r = b - 2                                                    # X_i = 3 + 2 i lies in the rows 1 + 2 i and 2 + 2 i
+        assert lab[r, 4] == b and lab[r, 5] == lab[r + 1, 5] == kCombY
+        if live:
+            e_sq, e_sum = p[r, 5] * p[r, 5] + p[r + 1, 5] * p[r + 1, 5], p[r, 5] + p[r + 1, 5]
+            ser_sq, ser_sum, apart_sq, apart_sum = ser_sq + e_sq, ser_sum + e_sum, apart_sq + e_sq, apart_sum + e_sum
+    n_alive = int(np.sum(alive))
+    return step, n_alive, len(alive) - n_alive, float(ser_sq), float(base_sq + apart_sq), float(ser_sum), float(base_sum + apart_sum), 2 + 2 * n_alive
+
+
+def _std_of(sq, total, n):
+    """bc_features.hpp: mean = sum / n, stddev = sqrt(sq / n - mean * mean) (no contraction)"""
+    mean = np.float64(total) / n
+    return float(np.sqrt(np.float64(sq) / n - mean * mean))
+
+
+def _assert_two_associations(order, where):
+    """the condition on the INPUT under which the witness can see anything"""
+    step, n_alive, n_dead, ser_sq, apart_sq, ser_sum, apart_sum, n = _comb32_folds(order)
+    d = int(np.float64(_std_of(apart_sq, apart_sum, n)).view(np.int64) - np.float64(_std_of(ser_sq, ser_sum, n)).view(np.int64))
+    print("comb32, %s: hub-Y pops at step %d with %d entries alive and %d dead; sq folded serially %r, apart %r; the standard "
+          "deviations of the two are %d ulps apart" % (where, step, n_alive, n_dead, ser_sq, apart_sq, d))
+    assert n_alive >= 64 and n_dead >= 1
+    assert ser_sq != apart_sq, "both associations give the same sum of squares: the image is no witness"
+    assert ser_sum == apart_sum, "the plain sums were expected exact (see test_comb32_has_two_associations)"
+    return step, d
+
+
+def test_comb32_has_two_associations():
+    """No GPU: on the replayed order (the stump forest reads the mean alone, and comb32's plain sums along column 5 are exact) the
+    sum of squares of hub-Y's alive entries differs between the two associations, by so little that the standard deviations stay
+    within kBand ulps -- and do differ.  The plain SUM cannot be a witness on this image: the band of column 5 lies in [0.5, 0.75),
+    whose float32 values are multiples of 2^-24, and 2202 of them add exactly in 53 bits whatever the jitter's seed; so only the
+    column derived from sq, x0.b0.std, is witnessed."""
+    step, d = _assert_two_associations(_reference("comb32", forest=True)[0], "replayed order")
+    assert 0 < abs(d) <= kBand, "the two standard deviations must differ, and by no more than the band the stumps span"
+
+
+@pytest.fixture(scope="module")
+def wit(ctx):
+    """one map object for the runs A, B and C: the RAG pass may differ from run to run in the last bit of an inexact sum"""
+    w = dict(rm=_rm(ctx, "comb32"))
+    yield w
+    for k in ("F0", "F1"):
+        if k in w:
+            w[k].close()
+    w["rm"].close()
+
+
+def _run(w, clf, **env):
+    from glia_amd import hmt
+    with hmt.options(**env):
+        return w["rm"].merge_order_bc(w[clf], want_feats=True)
+
+
+def _wit_a(ctx, w):
+    """run A: F0 = the 255 stumps on x0.b0.mean, no helpers -- every record and the popped rows by the loop's own workgroup"""
+    if "A" not in w:
+        _, pb = _image("comb32")
+        w["stumps"] = [(STUB, t, True) for t in _stumps(pb)]
+        w["F0"] = _load(ctx, _stump_arrays(w["stumps"]))
+        w["A"] = _run(w, "F0", GLIA_HMT_HELPERS=0)
+    return w["A"]
+
+
+def _wit_proof(w, order):
+    """the CPU-side conditions on run A's order, replayed once; returns the step at which hub-Y pops"""
+    if "proof" not in w:
+        w["proof"] = _assert_two_associations(order, "run A")[0]
+    return w["proof"]
+
+
+def _wit_b(ctx, w):
+    """run B: F1 = F0 + the witness stumps around x0.b0.std of the row hub-Y popped with in run A, no helpers"""
+    if "B" not in w:
+        o, s, f = _wit_a(ctx, w)
+        w["step"] = _wit_proof(w, o)
+        w["F1"] = _load(ctx, _stump_arrays(w["stumps"] + _witness_stumps(float(f[w["step"], STUB + 1]), STUB + 1)))
+        w["B"] = _run(w, "F1", GLIA_HMT_HELPERS=0)
+    return w["B"]
+
+
+@pytest.mark.gpu
+def test_float32_comb_run_a(ctx, wit):
+    """the CPU-side conditions on the order the device returned: at least 64 entries of hub-Y's chain alive and one dead at the pop,
+    and the two associations of their squares differ"""
+    from glia_amd import hmt
+    before = hmt.Context.internal_errors()
+    o, s, f = _wit_a(ctx, wit)
+    lab, _ = _image("comb32")
+    assert len(o) == len(np.unique(lab)) - 1 and _featdef.column_names(2, 3, [8], [], [8])[STUB + 1] == "x0.b0.std"
+    assert (_bits(s) == _bits(wit["F0"].predict(f))).all()
+    _wit_proof(wit, o)
+    assert hmt.Context.internal_errors() == before == 0
+
+
+@pytest.mark.gpu
+def test_float32_comb_run_b(ctx, wit):
+    """the witness stumps change nothing where every record goes one route: run A's order, hub-Y at the same step with the same row"""
+    from glia_amd import hmt
+    before = hmt.Context.internal_errors()
+    (oa, sa, fa), (o, s, f) = _wit_a(ctx, wit), _wit_b(ctx, wit)
+    step = wit["step"]
+    assert o.shape == oa.shape and (o == oa).all(), "another record fell into the band: shrink kBand or move the seed"
+    assert (_bits(s) == _bits(wit["F1"].predict(f))).all()
+    assert kCombY in o[step, :2].tolist() and (_bits(f[step]) == _bits(fa[step])).all()
+    assert round(s[step] * 259) == round(sa[step] * 255) + 2, "hub-Y pops AT the value: two of the four stumps vote"
+    assert hmt.Context.internal_errors() == before == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env", WITNESS_ENVS, ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()) or "default")
+def test_float32_comb_under_every_setting(ctx, wit, env):
+    """runs C: F1 under the default helpers, five helpers, the other two kernel instances and the smallest capacities -- (order,
+    saliencies) byte-identical to run B's, saliencies = the forest's values of the returned rows.  The saliency hub-Y pops with is
+    a helper's vote on ITS vector; the row is the loop's own."""
+    from glia_amd import hmt
+    before = hmt.Context.internal_errors()
+    ob, sb, _ = _wit_b(ctx, wit)
+    o, s, f = _run(wit, "F1", **env)
+    step = wit["step"]
+    print("comb32, %s: hub-Y pops at step %d with %r (run B: %r)" % (env, step, float(s[step]) if len(s) > step else None, float(sb[step])))
+    assert _same((o, s), (ob, sb)), env
+    assert (_bits(s) == _bits(wit["F1"].predict(f))).all(), env
+    assert hmt.Context.internal_errors() == before == 0
+
+
+@pytest.mark.gpu
+def test_float32_comb_of_two_batches(ctx):
+    """four channels, default helpers: the chain goes through two kFragCap batches and the fold is carried across them.  The serial
+    walk without helpers takes 12 s here, so the value comes from a run with helpers: the popped row is the loop's own walk either
+    way.  F0's run gives hub-Y's row; F1 has the witness stumps around x0.b0.std and x0.b3.std (both channels read comb32; the
+    other two images are exact); its order is F0's and its saliencies are the forest's values of its rows."""
+    from glia_amd import hmt
+    lab, pb = _image("comb32")
+    names = _featdef.column_names(2, 3, [8], [], [8, 8, 8, 4])
+    cols = [names.index("x0.b0.std"), names.index("x0.b3.std")]
+    before = hmt.Context.internal_errors()
+    rm = _rm(ctx, "comb32", four=True)
+    stumps = [(STUB, t, True) for t in _stumps(pb)]
+    f0 = _load(ctx, _stump_arrays(stumps))
+    oa, sa, fa = rm.merge_order_bc(f0, want_feats=True)
+    step, pairs, alive = _loopdef.chain_entries_at_pop(lab, pb, oa, kCombY, leaves=_cpu["leaves", "comb32"])
+    assert len(pairs) * 4 > kFragCap + kHelpChunk * 4 and sum(alive) >= 64 and not all(alive)
+    f1 = _load(ctx, _stump_arrays(stumps + [t for c in cols for t in _witness_stumps(float(fa[step, c]), c)]))
+    o, s, f = rm.merge_order_bc(f1, want_feats=True)
+    assert o.shape == oa.shape and (o == oa).all()
+    assert (_bits(f[step]) == _bits(fa[step])).all()
+    assert (_bits(s) == _bits(f1.predict(f))).all()
+    rm.close()
+    f0.close()
+    f1.close()
+    assert hmt.Context.internal_errors() == before == 0
 
 
 # ---- the other linkages, against the oracle ----------------------------------------------------------------------------------------
