@@ -8,10 +8,14 @@
 // rescales the rows inside, as pred_mlp --fmm does (the reference expects normalize_sample to have run).  --omp is a printf pattern
 // taking the round index; a model is written every --si rounds and after the last.  --v 1 (the default) prints the reference's "gd:"
 // and "learn-" lines from the trace.  train_mlp and train_logsig are not named train_sshmt_*: they train without the semi-supervised
-// term -- --uo, --uf, a non-zero --wu, --bsu, --bss > 0, --bb 1 and --usu 1 end with a message naming the flag and exit status 1.
+// term -- --uo, --uf, a non-zero --wu, --bsu and --usu 1 end with a message naming the flag and exit status 1.
 // train_sshmt_*: --uo / --uf come in equal numbers: file k of --uf holds one row per merge of file k of --uo (bc_feat's output for that
-// order).  --sl / --sf may be left out when --ws is 0.  Mini-batches are not built: --bsu > 0, --bss > 0, --bb 1 and --te / --tb other
-// than 1 end with a message naming the flag and exit status 1.
+// order).  --sl / --sf may be left out when --ws is 0.
+// Mini-batches are an opt-in: with --bseed S the reference's --bss B (batches of labelled rows), --bb 1 (balanced by
+// class), --bsu B (train_sshmt_*: batches of merge paths), --te E (epochs per iteration, 1) and --tb N (batches per iteration when
+// --te is 0, 1) are honoured, with THIS library's sampler: its permutations are a function of S, not the reference's rand() sequence.
+// Without --bseed, --bsu > 0, --bss > 0, --bb 1 and (train_sshmt_*) --te / --tb other than 1 end with a message naming the flag and
+// exit status 1.
 #include <climits>
 
 #include "common.hpp"
@@ -41,30 +45,32 @@ int main(int argc, char* argv[]) {
 #ifdef GLIA_TRAIN_SSHMT
                             "[--wr <w>] [--wu <w>] [--ws <w>] [--su <sigma>] [--ss <sigma>] [--usu <0|1>] [--uss <0|1>] [--topt <1|2|3>] [--lr <step>] "
                             "[--lrd <decay>] [--lrdi <n>] [--lrds <n>] [--tw <iterations>] [--ts <rounds>] [--si <n>] --omp <pattern> [--v <0|1>] "
-                            "[--seed <s>] [--fmm <minmax>]\n"
-                            "  (flags as sshmt/main_train_sshmt_mlp.cxx:171-236; not supported: --bsu --bss --bb, --te / --tb other than 1)\n";
+                            "[--seed <s>] [--fmm <minmax>] [--bseed <S> [--bss <B>] [--bb <0|1>] [--bsu <B>] [--te <epochs>] [--tb <batches>]]\n"
+                            "  (flags as sshmt/main_train_sshmt_mlp.cxx:171-236; --bsu --bss --bb, --te / --tb other than 1 need --bseed: this tool's own sampler)\n";
 #else
                             "[--wr <w>] [--ws <w>] [--ss <sigma>] [--uss <0|1>] [--topt <1|2|3>] [--lr <step>] [--lrd <decay>] [--lrdi <n>] "
                             "[--lrds <n>] [--tw <iterations>] [--ts <rounds>] [--si <n>] --omp <pattern> [--v <0|1>] [--seed <s>] [--fmm <minmax>]\n"
-                            "  (flags as sshmt/main_train_sshmt_mlp.cxx:171-236; not supported: --uo --uf --wu --bsu --bss --bb --usu)\n";
+                            "  [--bseed <S> [--bss <B>] [--bb <0|1>] [--te <epochs>] [--tb <batches>]]\n"
+                            "  (flags as sshmt/main_train_sshmt_mlp.cxx:171-236; not supported: --uo --uf --wu --bsu --usu; --bss --bb need --bseed: this tool's own sampler)\n";
 #endif
   Args a = parse(argc, argv, {}, {"sl", "sf", "im", "nn1", "nn2", "wr", "ws", "ss", "uss", "topt", "lr", "lrd", "lrdi", "lrds", "tw", "ts", "si", "omp", "v",
-                                  "seed", "fmm", "uo", "uf", "wu", "su", "usu", "bsu", "bss", "bb", "te", "tb"}, usage);
+                                  "seed", "fmm", "uo", "uf", "wu", "su", "usu", "bsu", "bss", "bb", "te", "tb", "bseed"}, usage);
+  const bool batches = a.has("bseed");      // the opt-in to this library's sampler
   auto refuse = [&](const char* flag, const char* what) { perr(std::string("Error: ") + kTool + ": --" + flag + " is not supported (" + what + ")"); };
 #ifdef GLIA_TRAIN_SSHMT
-  if (a.has("bsu") && atoi(a.str("bsu", "-1").c_str()) > 0) refuse("bsu", "batch samplers");
-  if (a.has("bss") && atoi(a.str("bss", "-1").c_str()) > 0) refuse("bss", "batch samplers");
-  if (flagOf(a, "bb")) refuse("bb", "batch samplers");
-  if (a.has("te") && atoi(a.str("te", "1").c_str()) != 1) refuse("te", "batch samplers");
-  if (a.has("tb") && atoi(a.str("tb", "1").c_str()) != 1) refuse("tb", "batch samplers");
+  if (!batches && a.has("bsu") && atoi(a.str("bsu", "-1").c_str()) > 0) refuse("bsu", "batch samplers");
+  if (!batches && a.has("bss") && atoi(a.str("bss", "-1").c_str()) > 0) refuse("bss", "batch samplers");
+  if (!batches && flagOf(a, "bb")) refuse("bb", "batch samplers");
+  if (!batches && a.has("te") && atoi(a.str("te", "1").c_str()) != 1) refuse("te", "batch samplers");
+  if (!batches && a.has("tb") && atoi(a.str("tb", "1").c_str()) != 1) refuse("tb", "batch samplers");
   for (const char* req : {"omp"})
 #else
   if (a.has("uo")) refuse("uo", "the unsupervised term");
   if (a.has("uf")) refuse("uf", "the unsupervised term");
   if (a.has("wu") && std::fabs(atof(a.str("wu", "0").c_str())) >= 2.22e-16) refuse("wu", "the unsupervised term");
   if (a.has("bsu")) refuse("bsu", "batch samplers");
-  if (a.has("bss") && atoi(a.str("bss", "-1").c_str()) > 0) refuse("bss", "batch samplers");
-  if (flagOf(a, "bb")) refuse("bb", "batch samplers");
+  if (!batches && a.has("bss") && atoi(a.str("bss", "-1").c_str()) > 0) refuse("bss", "batch samplers");
+  if (!batches && flagOf(a, "bb")) refuse("bb", "batch samplers");
   if (flagOf(a, "usu")) refuse("usu", "the unsupervised term");
   for (const char* req : {"sl", "sf", "omp"})
 #endif
@@ -88,6 +94,16 @@ int main(int argc, char* argv[]) {
   o.fixed_step_decay_iterations = atoi(a.str("lrdi", "-1").c_str()); o.sigma_update_step_period = atoi(a.str("lrds", "-1").c_str());
   o.max_iterations = atoi(a.str("tw", "0").c_str()); o.n_sigma_updates = atoi(a.str("ts", "0").c_str());
   o.seed = strtoull(a.str("seed", "0").c_str(), nullptr, 0);
+  glia_hmt_batch_opts bo;
+  glia_hmt_batch_opts_default(&bo);
+  if (batches) {
+    bo.seed = strtoull(a.str("bseed").c_str(), nullptr, 0);
+    bo.epochs_per_iteration = atoi(a.str("te", "1").c_str()); bo.batches_per_iteration = atoi(a.str("tb", "1").c_str());
+    o.sup_batch_size = atoi(a.str("bss", "-1").c_str()); o.balance_sup_batch = flagOf(a, "bb");
+#ifdef GLIA_TRAIN_SSHMT
+    o.uns_batch_size = atoi(a.str("bsu", "-1").c_str());
+#endif
+  }
   const int saveInterval = a.has("si") ? atoi(a.str("si").c_str()) : INT_MAX;
   const bool verbose = a.has("v") ? flagOf(a, "v") : true;
   const std::string pattern = a.str("omp");
@@ -159,10 +175,15 @@ int main(int argc, char* argv[]) {
   glia_hmt_mlp_model* model;
   const double *pmn = mn.empty() ? nullptr : mn.data(), *pmx = mx.empty() ? nullptr : mx.data(), *pinit = init.empty() ? nullptr : init.data();
 #ifdef GLIA_TRAIN_SSHMT
-  check(glia_hmt_sshmt_train(ctx, n ? rows.data() : nullptr, n, dim, n ? labels.data() : nullptr, blocks.data(), (int)blocks.size(), &so, pmn, pmx,
-                             pinit, &model));
+  if (batches)
+    check(glia_hmt_sshmt_train_batches(ctx, n ? rows.data() : nullptr, n, dim, n ? labels.data() : nullptr, blocks.data(), (int)blocks.size(), &so, &bo,
+                                       pmn, pmx, pinit, &model));
+  else
+    check(glia_hmt_sshmt_train(ctx, n ? rows.data() : nullptr, n, dim, n ? labels.data() : nullptr, blocks.data(), (int)blocks.size(), &so, pmn, pmx,
+                               pinit, &model));
 #else
-  check(glia_hmt_mlp_train(ctx, rows.data(), n, dim, labels.data(), &o, pmn, pmx, pinit, &model));
+  if (batches) check(glia_hmt_mlp_train_batches(ctx, rows.data(), n, dim, labels.data(), &o, &bo, pmn, pmx, pinit, &model));
+  else check(glia_hmt_mlp_train(ctx, rows.data(), n, dim, labels.data(), &o, pmn, pmx, pinit, &model));
 #endif
   int rounds = 0, stopped = 0, nSigma = 0;
   int64_t nTrace = 0, used = 0, nPaths = 0, nUnsRows = 0;

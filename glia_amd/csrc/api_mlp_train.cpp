@@ -6,6 +6,7 @@
 
 #include "api_types.hpp"
 #include "mlp_backward.hpp"
+#include "mlp_batch.hpp"
 #include "sshmt_paths.hpp"
 
 struct glia_hmt_mlp_model {
@@ -52,10 +53,11 @@ int prepare_blocks(const glia_hmt_sshmt_block* blocks, int n_blocks, int dim, co
 
 // One training call, whichever entry point it came through.  c == NULL: the definition on one host thread.  with_u: the caller has the
 // merge-path term (glia_hmt_sshmt_train): wu, update_sigma_u, so's own fields and the blocks count, and labelled rows may be absent
-// while ws is off.
+// while ws is off.  bo != NULL: the caller is a *_train_batches entry point: the batch fields of the options are
+// honoured, and with a sampler on the mini-batch step takes the update's place.
 int train(glia_hmt_ctx* c, bool with_u, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels, const glia_hmt_sshmt_block* blocks,
           int n_blocks, const glia_hmt_sshmt_train_opts& so, const double* h_min, const double* h_max, const double* h_init,
-          glia_hmt_mlp_model** out) {
+          glia_hmt_mlp_model** out, const glia_hmt_batch_opts* bo = nullptr) {
   const auto t0 = std::chrono::steady_clock::now();
   const std::string me = std::string(with_u ? "sshmt_train" : "mlp_train") + (c ? ": " : "_host: ");
   if (!out || n_rows < 0 || dim < 1 || (n_rows > 0 && (!h_rows || !h_labels))) { set_error(me + "invalid argument"); return GLIA_HMT_ERR_ARG; }
@@ -64,7 +66,7 @@ int train(glia_hmt_ctx* c, bool with_u, const double* h_rows, int64_t n_rows, in
   const glia_hmt_mlp_train_opts& o = so.base;
   std::string bad = with_u ? sshmt_train_bad_opts(so) : mlp_train_bad_opts(o);
   if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_ARG; }
-  bad = mlp_train_unsupported(o, with_u);
+  bad = mlp_train_unsupported(o, with_u, bo != nullptr);
   if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_UNSUPPORTED; }
   if (dim > kMlpTrainMaxDim) { set_error("mlp_train: rows of more than " + std::to_string(kMlpTrainMaxDim) + " columns are not supported"); return GLIA_HMT_ERR_UNSUPPORTED; }
   for (int64_t i = 0; i < n_rows * dim; ++i)
@@ -98,7 +100,32 @@ int train(glia_hmt_ctx* c, bool with_u, const double* h_rows, int64_t n_rows, in
   auto zero_timing = [&]() {
     if (c && with_u) c->sst = glia_hmt_sshmt_train_timing();
     if (c && !with_u) c->mlt = glia_hmt_mlp_train_timing();
+    if (c && bo) c->bat = glia_hmt_batch_timing();
   };
+  // the samplers (sshmt_util.hxx:69-107), before any kernel
+  std::unique_ptr<MlpBatchHostStep> step;
+  if (bo) {
+    MlpBatchSamplers S;
+    std::vector<int32_t> lab;
+    for (int64_t r = 0; r < n_rows; ++r) if (h_labels[r] == 1 || h_labels[r] == -1) lab.push_back(h_labels[r]);
+    bad = mlp_batch_make_uns(in.n_paths(), o.uns_batch_size, bo->seed, &S.U, &S.on_u);
+    if (bad.empty()) bad = mlp_batch_make_sup(lab.data(), (int64_t)lab.size(), o.sup_batch_size, o.balance_sup_batch, o.pos_target, o.neg_target, bo->seed, &S.S, &S.on_s);
+    if (bad.empty() && ((S.on_u && !on_u) || (S.on_s && (!on_s || mlp_isfeq(o.ws, 0.0))))) bad = "train_batches: a batch sampler for a term that is off";
+    if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_ARG; }
+    if (S.on_u || S.on_s) {
+      int route = GLIA_HMT_BATCH_STREAM;
+      std::string v;
+      if (option("GLIA_HMT_BATCH", &v) && v != "stream") {
+        if (v != "step") { set_error("train_batches: GLIA_HMT_BATCH must be stream or step, not '" + v + "'"); return GLIA_HMT_ERR_ARG; }
+        route = GLIA_HMT_BATCH_STEP;
+      }
+      if (c) {
+        GLIA_HIP_TRY(hipSetDevice(c->device));
+        if (int rc = mlp_batch_device_create(c->stream, route, d, &step)) return rc;
+      } else step.reset(new MlpBatchHostStep);
+      step->bo = *bo; step->samplers = S; step->in = &in;
+    }
+  }
   if (c) {
     GLIA_HIP_TRY(hipSetDevice(c->device));
     zero_timing();
@@ -126,7 +153,9 @@ int train(glia_hmt_ctx* c, bool with_u, const double* h_rows, int64_t n_rows, in
   MlpTrainUns U;
   U.ev = eu.get(); U.n_paths = R.n_paths; U.n_rows = R.n_uns_rows; U.wu = o.wu; U.sigma_u = so.sigma_u; U.min_sigma2 = o.min_sigma2;
   U.update_sigma_u = o.update_sigma_u;
-  if (int rc = mlp_train_run(o, R.n_used, w, ev.get(), &R, with_u ? &U : nullptr)) { zero_timing(); return rc; }
+  if (step) { step->ev = ev.get(); step->eu = eu.get(); }
+  if (int rc = mlp_train_run(o, R.n_used, w, ev.get(), &R, with_u ? &U : nullptr, step.get())) { zero_timing(); return rc; }
+  if (c && step) c->bat = step->tm;
   if (R.round_w.empty()) R.round_w.push_back(w);
   if (c) {
     for (const glia_hmt_mlp_train_record& r : R.trace) tm->iterations += r.kind == 0;
@@ -183,6 +212,73 @@ int glia_hmt_sshmt_train_host(const double* h_rows, int64_t n_rows, int dim, con
                               int n_blocks, const glia_hmt_sshmt_train_opts* opts, const double* h_min, const double* h_max,
                               const double* h_init, glia_hmt_mlp_model** out) {
   return glia_hmt_sshmt_train(nullptr, h_rows, n_rows, dim, h_labels, blocks, n_blocks, opts, h_min, h_max, h_init, out);
+}
+
+void glia_hmt_batch_opts_default(glia_hmt_batch_opts* opts) {
+  if (opts) { opts->seed = 0; opts->epochs_per_iteration = 1; opts->batches_per_iteration = 1; }
+}
+
+int glia_hmt_mlp_train_batches(glia_hmt_ctx* c, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels,
+                               const glia_hmt_mlp_train_opts* opts, const glia_hmt_batch_opts* batch, const double* h_min, const double* h_max,
+                               const double* h_init, glia_hmt_mlp_model** out) {
+  glia_hmt_sshmt_train_opts so;
+  glia_hmt_batch_opts bo;
+  sshmt_train_opts_default(&so);
+  glia_hmt_batch_opts_default(&bo);
+  if (opts) so.base = *opts;
+  if (batch) bo = *batch;
+  return train(c, false, h_rows, n_rows, dim, h_labels, nullptr, 0, so, h_min, h_max, h_init, out, &bo);
+}
+
+int glia_hmt_sshmt_train_batches(glia_hmt_ctx* c, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels,
+                                 const glia_hmt_sshmt_block* blocks, int n_blocks, const glia_hmt_sshmt_train_opts* opts,
+                                 const glia_hmt_batch_opts* batch, const double* h_min, const double* h_max, const double* h_init,
+                                 glia_hmt_mlp_model** out) {
+  glia_hmt_sshmt_train_opts so;
+  glia_hmt_batch_opts bo;
+  sshmt_train_opts_default(&so);
+  glia_hmt_batch_opts_default(&bo);
+  if (opts) so = *opts;
+  if (batch) bo = *batch;
+  return train(c, true, h_rows, n_rows, dim, h_labels, blocks, n_blocks, so, h_min, h_max, h_init, out, &bo);
+}
+
+int glia_hmt_batch_plan(const int32_t* h_labels, int64_t n_rows, int64_t n_paths, int sup_batch_size, int uns_batch_size,
+                        int balance_sup_batch, double pos_target, double neg_target, uint64_t seed, int k, int64_t* n_sup, int64_t* n_uns,
+                        int64_t* sup_offsets, int32_t* sup_rows, int64_t* uns_offsets, int32_t* uns_paths, int32_t* end_of_epoch) {
+  const bool fill = sup_offsets != nullptr;
+  if (n_rows < 0 || n_paths < 0 || k < 0 || (n_rows > 0 && !h_labels) || !n_sup || !n_uns || fill != (sup_rows != nullptr) ||
+      fill != (uns_offsets != nullptr) || fill != (uns_paths != nullptr)) {
+    set_error("batch_plan: invalid argument");
+    return GLIA_HMT_ERR_ARG;
+  }
+  for (int64_t r = 0; r < n_rows; ++r)
+    if (h_labels[r] != 1 && h_labels[r] != -1) { set_error("batch_plan: label " + std::to_string(r) + " is neither +1 nor -1"); return GLIA_HMT_ERR_ARG; }
+  MlpBatchSamplers S;
+  std::string bad = mlp_batch_make_uns(n_paths, uns_batch_size, seed, &S.U, &S.on_u);
+  if (bad.empty()) bad = mlp_batch_make_sup(h_labels, n_rows, sup_batch_size, balance_sup_batch, pos_target, neg_target, seed, &S.S, &S.on_s);
+  if (!bad.empty()) { set_error(bad); return GLIA_HMT_ERR_ARG; }
+  const int64_t ns = S.on_s ? (int64_t)k * S.S.batch_size() : 0, nu = S.on_u ? (int64_t)k * S.U.batch_size() : 0;
+  if (fill && (*n_sup != ns || *n_uns != nu)) { set_error("batch_plan: the sizes are not those of the first call"); return GLIA_HMT_ERR_ARG; }
+  *n_sup = ns; *n_uns = nu;
+  if (!fill) return GLIA_HMT_OK;
+  std::vector<int32_t> paths, rows;
+  sup_offsets[0] = uns_offsets[0] = 0;
+  for (int i = 0; i < k; ++i) {
+    const bool end = S.draw(&paths, &rows);
+    std::copy(rows.begin(), rows.end(), sup_rows + sup_offsets[i]);
+    std::copy(paths.begin(), paths.end(), uns_paths + uns_offsets[i]);
+    sup_offsets[i + 1] = sup_offsets[i] + (int64_t)rows.size();
+    uns_offsets[i + 1] = uns_offsets[i] + (int64_t)paths.size();
+    if (end_of_epoch) end_of_epoch[i] = end ? 1 : 0;
+  }
+  return GLIA_HMT_OK;
+}
+
+int glia_hmt_last_batch_timing(const glia_hmt_ctx* c, glia_hmt_batch_timing* out) {
+  if (!c || !out) { set_error("last_batch_timing: invalid argument"); return GLIA_HMT_ERR_ARG; }
+  *out = c->bat;
+  return GLIA_HMT_OK;
 }
 
 int glia_hmt_merge_paths(const uint32_t* h_order, int64_t n_merges, int max_len, int min_len, int64_t* n_paths, int64_t* n_members,

@@ -36,5 +36,9 @@ int mlp_train_device_create(const double* h_X, const double* h_t, long long n, i
                             glia_hmt_mlp_train_timing* tm, std::unique_ptr<MlpTrainEval>* out);
 int sshmt_train_device_create(const SshmtInput& in, int n1, int n2, int exp_variant, hipStream_t stream, glia_hmt_sshmt_train_timing* tm,
                               std::unique_ptr<MlpTrainEval>* out);
+// The mini-batch step over device evaluators (mlp_batch.hip): route GLIA_HMT_BATCH_STREAM | GLIA_HMT_BATCH_STEP, d weights.
+// The caller fills the step's options, samplers, input and evaluators (mlp_batch.hpp).
+struct MlpBatchHostStep;
+int mlp_batch_device_create(hipStream_t stream, int route, long long d, std::unique_ptr<MlpBatchHostStep>* out);
 
 }  // namespace glia

@@ -94,6 +94,48 @@ GLIA_MLP_HD double mlp_init_weight(uint64_t seed, uint64_t p) {
   return mlp_mul(mlp_sub(s, 6.0), 0.01);
 }
 
+// The correctly rounded quotient and square root (the host's / and std::sqrt).
+GLIA_MLP_HD double mlp_div(double a, double b) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return __ddiv_rn(a, b);
+#else
+  return a / b;
+#endif
+}
+GLIA_MLP_HD double mlp_sqrt(double a) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return __dsqrt_rn(a);
+#else
+  return __builtin_sqrt(a);
+#endif
+}
+// How the terms' gradients become g and how g moves a weight, per weight: stated once for the trainer's full-data iteration and for the
+// batch steps of DESIGN 3.17, on the host and in k_batch_step (mlp_batch.hip).  *_one: isfeq(weight, 1.0), the reference's shortcut.
+struct MlpStepRule {
+  int optimizer, use_r, use_u, use_s, r_one, u_one, s_one;
+  double wr, wu, ws, sigma_u2, sigma2;
+};
+constexpr double kMlpMomentum = 0.5, kMlpAdamBeta1 = 0.5, kMlpAdamBeta2 = 0.9, kMlpAdamEps = 1e-8;      // alg/gd.hxx:289,347-349
+// type/energy_function.hxx:164-230: from +0.0 the regulariser, the unsupervised term, the supervised term
+GLIA_MLP_HD double mlp_energy_grad_elem(const MlpStepRule& k, double w, double gu, double gs) {
+  double g = 0.0;
+  if (k.use_r) g = mlp_add(g, k.r_one ? w : mlp_mul(k.wr, w));
+  if (k.use_u) { const double t = mlp_div(gu, k.sigma_u2); g = mlp_add(g, k.u_one ? t : mlp_mul(k.wu, t)); }
+  if (k.use_s) { const double t = mlp_div(gs, k.sigma2); g = mlp_add(g, k.s_one ? t : mlp_mul(k.ws, t)); }
+  return g;
+}
+// alg/gd.hxx:73-79 (1: vanilla), 367-384 (2: Adam), 307-315 (3: momentum)
+GLIA_MLP_HD void mlp_update_elem(int optimizer, double step, double g, double* w, double* om, double* ov) {
+  if (optimizer == 1) *w = mlp_sub(*w, mlp_mul(g, step));
+  else if (optimizer == 3) { const double u = mlp_add(g, mlp_mul(kMlpMomentum, *ov)); *w = mlp_sub(*w, mlp_mul(step, u)); *ov = u; }
+  else {
+    const double b1c = mlp_sub(1.0, kMlpAdamBeta1), b2c = mlp_sub(1.0, kMlpAdamBeta2);
+    *om = mlp_add(mlp_mul(kMlpAdamBeta1, *om), mlp_mul(b1c, g));
+    *ov = mlp_add(mlp_mul(kMlpAdamBeta2, *ov), mlp_mul(mlp_mul(b2c, g), g));
+    *w = mlp_sub(*w, mlp_div(mlp_mul(step, *om), mlp_sqrt(mlp_add(*ov, kMlpAdamEps))));
+  }
+}
+
 }  // namespace glia
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -176,16 +218,48 @@ inline void mlp_loss_grad_host(const double* w, int D, int n1, int n2, const dou
   *L = mlp_chunk_sqsum_host(e.data(), n, kMlpTrainChunk);
 }
 
+// One term's share of a batch, in the memory its evaluator works in.  rows == NULL: the term has no sampler and takes
+// all its rows.  Supervised term: rows [n] = the batch, in batch order.  Path term: rows [n] = the rows the batch's paths name, ascending;
+// the batch's P paths in batch order as a CSR over positions in rows; the rows' incidence lists restricted to the batch (sshmt_incidence
+// over that CSR: entries position-in-batch * kSshmtMaxPath + slot, ascending).
+struct MlpBatchView {
+  const int32_t* rows = nullptr;
+  long long n = 0, P = 0;
+  const long long *offsets = nullptr, *members = nullptr, *inc_off = nullptr;
+  const uint32_t* inc = nullptr;
+};
 // Whoever computes L and grad for the trainer; grad == NULL: L alone.  Returns a GLIA_HMT_* code.
 struct MlpTrainEval {
   virtual ~MlpTrainEval() {}
   virtual int eval(const double* w, double* L, double* grad) = 0;
+  // The term's gradient over a batch: the full-data definition applied to the batch's rows in batch order; no energy value.
+  virtual int batch_grad(const double* w, const MlpBatchView& b, double* grad) = 0;
+  // Device evaluators: the kernels of batch_grad up to the chunk partials, enqueued without a wait, the weights read from device memory;
+  // *part_S [*n_chunks][d] is where the partials will lie.
+  virtual int enqueue_batch(const double* d_w, const MlpBatchView& b, const double** part_S, long long* n_chunks) { return GLIA_HMT_ERR_INTERNAL; }
 };
 struct MlpTrainHostEval : MlpTrainEval {
   int D, n1, n2;
   const double *X, *t;
   int64_t n;
   int eval(const double* w, double* L, double* grad) override { mlp_loss_grad_host(w, D, n1, n2, X, t, n, L, grad); return 0; }
+  int batch_grad(const double* w, const MlpBatchView& b, double* grad) override {
+    double L;
+    if (!b.rows) return eval(w, &L, grad);
+    std::vector<double> Xb((size_t)b.n * D), tb((size_t)b.n);
+    for (long long i = 0; i < b.n; ++i) {
+      std::copy(X + (size_t)b.rows[i] * D, X + (size_t)(b.rows[i] + 1) * D, Xb.begin() + (size_t)i * D);
+      tb[(size_t)i] = t[b.rows[i]];
+    }
+    mlp_loss_grad_host(w, D, n1, n2, Xb.data(), tb.data(), b.n, &L, grad);
+    return 0;
+  }
+};
+// The mini-batch step that takes the place of one update when a sampler is on (alg/gd.hxx:86-157; mlp_batch.hpp): every
+// draw, gradient and update of the step, from w, om, ov to those after its last batch.
+struct MlpBatchStep {
+  virtual ~MlpBatchStep() {}
+  virtual int run(const MlpStepRule& k, double step, std::vector<double>& w, std::vector<double>& om, std::vector<double>& ov) = 0;
 };
 
 struct MlpTrainResult {
@@ -224,12 +298,13 @@ inline void mlp_train_opts_default(glia_hmt_mlp_train_opts* o) {
 }
 // What this library does not train (message, or empty), then what no trainer can run (message, or empty).
 // with_u: the caller is the trainer that has the unsupervised term (sshmt_paths.hpp)
-inline std::string mlp_train_unsupported(const glia_hmt_mlp_train_opts& o, bool with_u = false) {
+// batches: the caller is one of the *_train_batches entry points, which honour the three batch fields (mlp_batch.hpp)
+inline std::string mlp_train_unsupported(const glia_hmt_mlp_train_opts& o, bool with_u = false, bool batches = false) {
   if (!with_u && !mlp_isfeq(o.wu, 0.0)) return "mlp_train: the unsupervised term (wu != 0; --uo, --uf, --wu) is not supported";
   if (!with_u && o.update_sigma_u) return "mlp_train: update_sigma_u (--usu) belongs to the unsupervised term, which is not supported";
-  if (o.sup_batch_size > 0) return "mlp_train: sup_batch_size (--bss): batch samplers are not supported";
-  if (o.uns_batch_size > 0) return "mlp_train: uns_batch_size (--bsu): batch samplers are not supported";
-  if (o.balance_sup_batch) return "mlp_train: balance_sup_batch (--bb): batch samplers are not supported";
+  if (!batches && o.sup_batch_size > 0) return "mlp_train: sup_batch_size (--bss): batch samplers are not supported";
+  if (!batches && o.uns_batch_size > 0) return "mlp_train: uns_batch_size (--bsu): batch samplers are not supported";
+  if (!batches && o.balance_sup_batch) return "mlp_train: balance_sup_batch (--bb): batch samplers are not supported";
   if (o.alt_su) return "mlp_train: alt_su is not supported";
   if (o.n1 > kMlpTrainMaxHidden || o.n2 > kMlpTrainMaxHidden)
     return "mlp_train: more than " + std::to_string(kMlpTrainMaxHidden) + " units in a hidden layer are not supported";
@@ -252,17 +327,25 @@ inline std::string mlp_train_bad_opts(const glia_hmt_mlp_train_opts& o, bool wit
 // needed, only while ws is on).  Returns the evaluator's code if it fails.
 // U (optional): the unsupervised term; it is off without a path (sshmt/input.hxx:120-121).  The terms enter fx and g in the order
 // regulariser, unsupervised, supervised (type/energy_function.hxx:164-230); without U not one operation differs from the supervised trainer.
+// B (optional): the mini-batch step; without it not one operation differs from the full-batch trainer.
 inline int mlp_train_run(const glia_hmt_mlp_train_opts& o, int64_t n, std::vector<double>& w, MlpTrainEval* ev, MlpTrainResult* R,
-                         const MlpTrainUns* U = nullptr) {
+                         const MlpTrainUns* U = nullptr, MlpBatchStep* B = nullptr) {
   const long long d = (long long)w.size();
   const bool use_r = !mlp_isfeq(o.wr, 0.0), use_s = !mlp_isfeq(o.ws, 0.0);
   const bool use_u = U && U->ev && U->n_paths > 0 && !mlp_isfeq(U->wu, 0.0);
   double sigma_u2 = U ? U->sigma_u * U->sigma_u : 0.0;
   std::vector<double> gu(use_u ? (size_t)w.size() : 0);
-  const double min_step = 1e-10, grad_tol = 1e-16, fixed_decay = 0.5, mu = 0.5, beta1 = 0.5, beta2 = 0.9, adam_eps = 1e-8;   // alg/gd.hxx:19-28,289,347-349
+  const double min_step = 1e-10, grad_tol = 1e-16, fixed_decay = 0.5;   // alg/gd.hxx:19-28
   double sigma2 = o.sigma_s * o.sigma_s;
   std::vector<double> g((size_t)d), gs((size_t)d), backup, om((size_t)d), ov((size_t)d);
   int rc = 0;
+  auto rule = [&]() {
+    MlpStepRule k;
+    k.optimizer = o.optimizer; k.use_r = use_r; k.use_u = use_u; k.use_s = use_s;
+    k.r_one = mlp_isfeq(o.wr, 1.0); k.u_one = use_u && mlp_isfeq(U->wu, 1.0); k.s_one = mlp_isfeq(o.ws, 1.0);
+    k.wr = o.wr; k.wu = use_u ? U->wu : 0.0; k.ws = o.ws; k.sigma_u2 = sigma_u2; k.sigma2 = sigma2;
+    return k;
+  };
 
   // type/energy_function.hxx:164-230 with alg/function.hxx:72-77,257-267
   auto energy = [&](bool want_grad, double* fx) -> int {
@@ -270,34 +353,21 @@ inline int mlp_train_run(const glia_hmt_mlp_train_opts& o, int64_t n, std::vecto
     if (use_u && (rc = U->ev->eval(w.data(), &Lu, want_grad ? gu.data() : nullptr))) return rc;
     if (use_s && (rc = ev->eval(w.data(), &L, want_grad ? gs.data() : nullptr))) return rc;
     double ret = 0.0;
-    if (want_grad) for (long long p = 0; p < d; ++p) g[p] = 0.0;
-    if (use_r) {
-      ret = ret + o.wr * (mlp_sqnorm(w.data(), d) / 2.0);
-      if (want_grad) for (long long p = 0; p < d; ++p) g[p] = g[p] + (mlp_isfeq(o.wr, 1.0) ? w[p] : o.wr * w[p]);
-    }
-    if (use_u) {
-      ret = ret + U->wu * ((0.5 * Lu) / sigma_u2 + ((double)U->n_paths * std::log(sigma_u2)) / 2.0);
-      if (want_grad) for (long long p = 0; p < d; ++p) { const double t = gu[p] / sigma_u2; g[p] = g[p] + (mlp_isfeq(U->wu, 1.0) ? t : U->wu * t); }
-    }
-    if (use_s) {
-      ret = ret + o.ws * ((0.5 * L) / sigma2 + ((double)n * std::log(sigma2)) / 2.0);
-      if (want_grad) for (long long p = 0; p < d; ++p) { const double t = gs[p] / sigma2; g[p] = g[p] + (mlp_isfeq(o.ws, 1.0) ? t : o.ws * t); }
+    if (use_r) ret = ret + o.wr * (mlp_sqnorm(w.data(), d) / 2.0);
+    if (use_u) ret = ret + U->wu * ((0.5 * Lu) / sigma_u2 + ((double)U->n_paths * std::log(sigma_u2)) / 2.0);
+    if (use_s) ret = ret + o.ws * ((0.5 * L) / sigma2 + ((double)n * std::log(sigma2)) / 2.0);
+    if (want_grad) {
+      const MlpStepRule k = rule();
+      for (long long p = 0; p < d; ++p) g[p] = mlp_energy_grad_elem(k, w[p], use_u ? gu[p] : 0.0, use_s ? gs[p] : 0.0);
     }
     *fx = ret;
     return 0;
   };
   // alg/gd.hxx:73-79 (1), 367-384 (2), 307-315 (3)
-  auto update = [&](double step) {
-    if (o.optimizer == 1) for (long long p = 0; p < d; ++p) w[p] = w[p] - g[p] * step;
-    else if (o.optimizer == 3) for (long long p = 0; p < d; ++p) { const double u = g[p] + mu * ov[p]; w[p] = w[p] - step * u; ov[p] = u; }
-    else {
-      const double b1c = 1.0 - beta1, b2c = 1.0 - beta2;
-      for (long long p = 0; p < d; ++p) {
-        om[p] = beta1 * om[p] + b1c * g[p];
-        ov[p] = beta2 * ov[p] + (b2c * g[p]) * g[p];
-        w[p] = w[p] - (step * om[p]) / std::sqrt(ov[p] + adam_eps);
-      }
-    }
+  auto update = [&](double step) -> int {
+    if (B) return B->run(rule(), step, w, om, ov);      // alg/gd.hxx:191,238,249: helperMiniBatchGD in the update's place
+    for (long long p = 0; p < d; ++p) mlp_update_elem(o.optimizer, step, g[p], &w[p], &om[p], &ov[p]);
+    return 0;
   };
   // sshmt_util.hxx:140-145,188-207: sigma^2 = max(floor, L / n) when it is updated; the evaluated value is recorded either way
   // updateSigmaU (sshmt_util.hxx:148-185), after updateSigmaS (:210-222): sigma_u^2 = max(floor, L_U / P) when it is updated, and
@@ -358,7 +428,7 @@ inline int mlp_train_run(const glia_hmt_mlp_train_opts& o, int64_t n, std::vecto
           record(round, t, last ? 1 : 0, fx, xx, gg, step, 0);
           if (last) break;
           if (std::sqrt(gg) < grad_tol) t = o.max_iterations - 1;      // stop: only the final statistics are left
-          else { backup = w; have_backup = true; update(step); }
+          else { backup = w; have_backup = true; if ((rc = update(step))) return rc; }
         }
       } else {                                            // adaptiveStepGD (alg/gd.hxx:210-272)
         int t = 0;
@@ -369,7 +439,7 @@ inline int mlp_train_run(const glia_hmt_mlp_train_opts& o, int64_t n, std::vecto
           if (!std::isfinite(fx) || !std::isfinite(gg)) { stop_nonfinite(t, xx, 0); break; }
           if (std::sqrt(gg) < grad_tol) break;
           backup = w; have_backup = true;
-          update(step);
+          if ((rc = update(step))) return rc;
           const double fx_prev = fx;
           int rollbacks = 0;
           if ((rc = energy(false, &fx))) return rc;
@@ -377,7 +447,7 @@ inline int mlp_train_run(const glia_hmt_mlp_train_opts& o, int64_t n, std::vecto
             step = mlp_max(min_step, step * o.step_decay);
             if (step == min_step) break;
             w = backup;
-            update(step);
+            if ((rc = update(step))) return rc;
             if ((rc = energy(false, &fx))) return rc;
             ++rollbacks;
           }

@@ -24,6 +24,17 @@ __global__ __launch_bounds__(kTrainThreads) void k_train_fold(const double* __re
   }
 }
 
+int train_memory_fits(uint64_t bytes, const std::string& who, const std::string& detail) {
+  size_t free_b = 0, total_b = 0;
+  GLIA_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (bytes > (uint64_t)(0.85 * (double)free_b)) {
+    set_error(who + " needs " + std::to_string(bytes >> 20) + " MiB of device memory" + detail + ", more than 85 % of the " + std::to_string(free_b >> 20) +
+              " MiB free");
+    return GLIA_HMT_ERR_UNSUPPORTED;
+  }
+  return GLIA_HMT_OK;
+}
+
 TrainCall::~TrainCall() {
   for (const Array& a : arrays) if (*a.p) (void)hipFree(*a.p);      // (the pointers start out NULL: a call that failed half-way frees what it got)
   for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
@@ -41,14 +52,9 @@ int TrainCall::open(const std::string& term, const std::string& what, const std:
   want(&out, (uint64_t)d + 1);
   uint64_t bytes = 0;
   for (const Array& a : arrays) bytes += a.bytes;
-  size_t free_b = 0, total_b = 0;
-  GLIA_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-  if (bytes > (uint64_t)(0.85 * (double)free_b)) {
-    set_error(term + ": " + what + " needs " + std::to_string(bytes >> 20) + " MiB of device memory (rows " + std::to_string(rows >> 20) +
-              " MiB, chunk partials " + std::to_string(partials >> 20) + " MiB" + more + "), more than 85 % of the " + std::to_string(free_b >> 20) +
-              " MiB free");
-    return GLIA_HMT_ERR_UNSUPPORTED;
-  }
+  if (int rc = train_memory_fits(bytes, term + ": " + what, " (rows " + std::to_string(rows >> 20) + " MiB, chunk partials " + std::to_string(partials >> 20) +
+                                                             " MiB" + more + ")"))
+    return rc;
   *plan_bytes = bytes;
   for (const Array& a : arrays) GLIA_HIP_TRY(hipMalloc(a.p, a.bytes));
   for (hipEvent_t& e : ev) GLIA_HIP_TRY(hipEventCreate(&e));
@@ -69,10 +75,10 @@ int TrainCall::begin_eval(const double* h_w) {
   return GLIA_HMT_OK;
 }
 
-int TrainCall::finish_eval(int marks, double* L, double* h_grad, float* ms) {
+int TrainCall::finish_eval(int marks, double* L, double* h_grad, float* ms, long long chunks) {
   const size_t nd = (size_t)d;
   hipLaunchKernelGGL(k_train_fold, dim3((unsigned)((nd + 1 + kTrainThreads - 1) / kTrainThreads)), dim3(kTrainThreads), 0, stream, part_S, part_L,
-                     n_chunks, d, h_grad ? 1 : 0, out, out + nd, n_L);
+                     chunks < 0 ? n_chunks : chunks, d, h_grad ? 1 : 0, out, out + nd, chunks < 0 ? n_L : 0);
   GLIA_HIP_TRY(hipGetLastError());
   GLIA_HIP_TRY(mark(marks));
   if (h_grad) GLIA_HIP_TRY(hipMemcpyAsync(h_out.data(), out, 8 * (nd + 1), hipMemcpyDeviceToHost, stream));
@@ -100,6 +106,24 @@ struct MlpTrainDevice : MlpTrainEval {
     tm->ms_weights += ms[0]; tm->ms_chunk += ms[1]; tm->ms_fold += ms[2]; tm->ms_readback += ms[3];
     tm->evals += 1; tm->grad_evals += h_grad ? 1 : 0;
     return GLIA_HMT_OK;
+  }
+  // the gathered instance over the batch's rows (all rows without a sampler); the times of batches are the batch timing's
+  int enqueue_batch(const double* d_w, const MlpBatchView& b, const double** part_S, long long* n_chunks) override {
+    const long long rows = b.rows ? b.n : call.n;
+    if (int rc = b.rows ? call.chunk(TermSupervisedBatch{b.rows, t}, 1, rows, d_w) : call.chunk(TermSupervised{t, call.part_L}, 1, rows, d_w)) return rc;
+    *part_S = call.part_S;
+    *n_chunks = (rows + kMlpTrainChunk - 1) / kMlpTrainChunk;
+    return GLIA_HMT_OK;
+  }
+  int batch_grad(const double* h_w, const MlpBatchView& b, double* h_grad) override {
+    float ms[4] = {0, 0, 0, 0};
+    const double* part = nullptr;
+    long long chunks = 0;
+    double L;
+    if (int rc = call.begin_eval(h_w)) return rc;
+    if (int rc = enqueue_batch(call.w, b, &part, &chunks)) return rc;
+    GLIA_HIP_TRY(call.mark(2));
+    return call.finish_eval(3, &L, h_grad, ms, chunks);
   }
 };
 

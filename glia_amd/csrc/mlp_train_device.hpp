@@ -25,6 +25,7 @@ constexpr int kTrainThreads = 256;
 // without the gradient.
 struct TermSupervised {
   static constexpr bool kLossByChunk = true;
+  static constexpr bool kGather = false;
   const double* tgt;
   double* part_L;
   __device__ void row(long long r, double f, int want_grad, double* c, uint32_t* named) const { *c = mlp_sub(tgt[r], f); }
@@ -34,6 +35,7 @@ struct TermSupervised {
 // pass alone, f to f_out.
 struct TermPaths {
   static constexpr bool kLossByChunk = false;
+  static constexpr bool kGather = false;
   const double* coef;
   const uint32_t* named;
   double* f_out;
@@ -43,6 +45,26 @@ struct TermPaths {
     *is_named = named[r];
   }
   static __device__ bool skipped(double c, const uint32_t* is_named) { return !*is_named; }
+};
+
+// The terms over a batch: row r of the kernel is X[rows[r]] -- the row-indirected instances of the chunk kernel.  A batch
+// has no energy value.  Supervised: rows = the batch in batch order, the targets by row.  Paths: rows = the rows the batch's paths
+// name, ascending; c, named and f by position in rows.
+struct TermSupervisedBatch {
+  static constexpr bool kLossByChunk = false;
+  static constexpr bool kGather = true;
+  const int32_t* rows;
+  const double* tgt;
+  __device__ void row(long long r, double f, int want_grad, double* c, uint32_t* named) const { *c = mlp_sub(tgt[rows[r]], f); }
+  static __device__ bool skipped(double c, const uint32_t* named) { return mlp_feq0(c); }
+};
+struct TermPathsBatch {
+  static constexpr bool kLossByChunk = false;
+  static constexpr bool kGather = true;
+  const int32_t* rows;
+  TermPaths local;
+  __device__ void row(long long r, double f, int want_grad, double* c, uint32_t* is_named) const { local.row(r, f, want_grad, c, is_named); }
+  static __device__ bool skipped(double c, const uint32_t* is_named) { return TermPaths::skipped(c, is_named); }
 };
 
 template <int NMAX, class Term>
@@ -57,12 +79,21 @@ __global__ __launch_bounds__(kTrainThreads) void k_train_chunk(const double* __r
   const int tid = threadIdx.x;
   const MlpWeights m = mlp_train_weights(w, D, n1, n2);
   const double* Xc = X + (size_t)r0 * (size_t)D;
+  __shared__ int32_t s_row[Term::kGather ? C : 1];      // (the batch terms alone)
+  if constexpr (Term::kGather) {
+    if (tid < nr) s_row[tid] = term.rows[r0 + tid];
+    __syncthreads();
+  }
+  auto xrow = [&](int r) -> const double* {
+    if constexpr (Term::kGather) return X + (size_t)s_row[r] * (size_t)D;
+    else return Xc + (size_t)r * (size_t)D;
+  };
 
   // ---- phase A: forward ----
   if (n1 > 0) {
     for (int q = tid; q < C * n1; q += kTrainThreads) {
       const int r = q & (C - 1), k = q >> 6;
-      if (r < nr) s_h1[k * C + r] = mlp_unit(m.w0, D, 1, k, MlpRow{Xc + (size_t)r * (size_t)D});
+      if (r < nr) s_h1[k * C + r] = mlp_unit(m.w0, D, 1, k, MlpRow{xrow(r)});
     }
     __syncthreads();
     for (int q = tid; q < C * n2; q += kTrainThreads) {
@@ -73,7 +104,7 @@ __global__ __launch_bounds__(kTrainThreads) void k_train_chunk(const double* __r
   }
   if (tid < nr) {
     const int r = tid;
-    const double h3 = n1 > 0 ? mlp_unit(m.w2, n2 + 1, 1, 0, MlpActs{s_h2 + r, n2, C}) : mlp_unit(m.w2, D, 1, 0, MlpRow{Xc + (size_t)r * (size_t)D});
+    const double h3 = n1 > 0 ? mlp_unit(m.w2, n2 + 1, 1, 0, MlpActs{s_h2 + r, n2, C}) : mlp_unit(m.w2, D, 1, 0, MlpRow{xrow(r)});
     const double f = glibc::sigmoid(h3, exp_variant);
     term.row(r0 + r, f, want_grad, &s_c[r], &s_named[r]);
     if (want_grad) {
@@ -107,12 +138,16 @@ __global__ __launch_bounds__(kTrainThreads) void k_train_chunk(const double* __r
     for (int r = 0; r < nr; ++r) {
       const double c = s_c[r];
       if (Term::skipped(c, s_named + r)) continue;
-      const double g = mlp_grad_elem(m, p, MlpRow{Xc + (size_t)r * (size_t)D}, s_h1 + r, s_h2 + r, s_dh1 + r, s_dh2 + r, s_dh3[r], C);
+      const double g = mlp_grad_elem(m, p, MlpRow{xrow(r)}, s_h1 + r, s_h2 + r, s_dh1 + r, s_dh2 + r, s_dh3[r], C);
       S = mlp_sub(S, mlp_mul(g, c));
     }
     out[p] = S;
   }
 }
+
+// The trainers' memory rule, in one place (mlp_train.hip): device memory of `bytes` beyond 85 % of what is free is
+// GLIA_HMT_ERR_UNSUPPORTED with "<who> needs .. MiB of device memory<detail>, more than 85 % of the .. MiB free".
+int train_memory_fits(uint64_t bytes, const std::string& who, const std::string& detail);
 
 // The device state of one evaluator for the lifetime of a training call: the prepared rows X [n][D], the weights, the chunk partials
 // part_S [n_chunks][d] and part_L [n_L], out = the gradient [d] then L, every further array its term wants, and the events around
@@ -144,17 +179,23 @@ struct TrainCall {
   // An evaluation: begin_eval (mark 0, the weights up, mark 1), the term's kernels and marks 2 .. marks - 1, finish_eval (the fold,
   // mark `marks`, L and -- h_grad != NULL -- the gradient down, mark marks + 1, wait: ms [marks + 1]).
   int begin_eval(const double* h_w);
-  template <class Term> int chunk(const Term& term, int want_grad) {
-    const dim3 grid((unsigned)n_chunks), block(kTrainThreads);
+  // rows, wp (batches): the kernel's row count when it is not n, the weights when they are not this call's copy
+  template <class Term> int chunk(const Term& term, int want_grad, long long rows = -1, const double* wp = nullptr) {
+    if (rows < 0) rows = n;
+    if (!wp) wp = w;
+    if (rows < 1 || rows > n) { set_error("mlp_train: a batch outside its term's rows"); return GLIA_HMT_ERR_INTERNAL; }
+    const dim3 grid((unsigned)((rows + kMlpTrainChunk - 1) / kMlpTrainChunk)), block(kTrainThreads);
     if (n1 <= 16 && n2 <= 16)
-      hipLaunchKernelGGL((k_train_chunk<16, Term>), grid, block, 0, stream, X, n, D, n1, n2, w, d, exp_variant, want_grad, term, part_S);
+      hipLaunchKernelGGL((k_train_chunk<16, Term>), grid, block, 0, stream, X, rows, D, n1, n2, wp, d, exp_variant, want_grad, term, part_S);
     else
-      hipLaunchKernelGGL((k_train_chunk<kMlpTrainMaxHidden, Term>), grid, block, 0, stream, X, n, D, n1, n2, w, d, exp_variant, want_grad, term,
+      hipLaunchKernelGGL((k_train_chunk<kMlpTrainMaxHidden, Term>), grid, block, 0, stream, X, rows, D, n1, n2, wp, d, exp_variant, want_grad, term,
                          part_S);
     GLIA_HIP_TRY(hipGetLastError());
     return GLIA_HMT_OK;
   }
-  int finish_eval(int marks, double* L, double* h_grad, float* ms);
+  // chunks (batches): the chunk partials to fold when they are not all n_chunks; a batch has no energy value, so none of part_L is
+  // folded and *L is +0.0
+  int finish_eval(int marks, double* L, double* h_grad, float* ms, long long chunks = -1);
 };
 
 }  // namespace glia

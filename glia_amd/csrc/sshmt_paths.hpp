@@ -176,6 +176,22 @@ struct SshmtHostEval : MlpTrainEval {
   int n1 = 0, n2 = 0;
   const SshmtInput* in = nullptr;
   int eval(const double* w, double* L, double* grad) override { sshmt_loss_grad_host(w, n1, n2, *in, L, grad); return 0; }
+  // the batch's named rows in ascending order and its paths in batch order are an input of their own
+  int batch_grad(const double* w, const MlpBatchView& b, double* grad) override {
+    double L;
+    if (!b.rows) return eval(w, &L, grad);
+    SshmtInput sub;
+    sub.D = in->D; sub.n_rows = b.n; sub.tb = in->tb;
+    sub.X.resize((size_t)b.n * in->D);
+    for (long long i = 0; i < b.n; ++i)
+      std::copy(in->X.begin() + (size_t)b.rows[i] * in->D, in->X.begin() + (size_t)(b.rows[i] + 1) * in->D, sub.X.begin() + (size_t)i * in->D);
+    sub.offsets.assign(b.offsets, b.offsets + b.P + 1);
+    sub.members.assign(b.members, b.members + b.offsets[b.P]);
+    sub.inc_off.assign(b.inc_off, b.inc_off + b.n + 1);
+    sub.inc.assign(b.inc, b.inc + b.offsets[b.P]);
+    sshmt_loss_grad_host(w, n1, n2, sub, &L, grad);
+    return 0;
+  }
 };
 
 // glia_hmt_sshmt_train_opts_default: main_train_sshmt_mlp.cxx:20-53

@@ -97,6 +97,35 @@ struct SshmtTrainDevice : MlpTrainEval {
     tm->u_evals += 1; tm->u_grad_evals += want_grad;
     return GLIA_HMT_OK;
   }
+  // stages 1 to 4 over the batch's lists -- the gathered chunk kernel over the named rows, k_sshmt_paths and
+  // k_sshmt_gather over the batch's own CSRs (positions in the named rows, positions in the batch); f, e, q, c and named by position
+  int enqueue_batch(const double* d_w, const MlpBatchView& b, const double** part_S, long long* n_chunks) override {
+    const long long rows = b.rows ? b.n : call.n, paths = b.rows ? b.P : P;
+    if (paths < 1 || paths > P) { set_error("sshmt_train: a batch outside the paths"); return GLIA_HMT_ERR_INTERNAL; }
+    const TermPaths term{c, named, f};
+    const TermPathsBatch bterm{b.rows, term};
+    if (int rc = b.rows ? call.chunk(bterm, 0, rows, d_w) : call.chunk(term, 0, rows, d_w)) return rc;
+    hipLaunchKernelGGL(k_sshmt_paths, dim3((unsigned)((paths + kSshmtPathChunk - 1) / kSshmtPathChunk)), dim3(kSshmtPathChunk), 0, call.stream, f,
+                       b.rows ? b.offsets : offsets, b.rows ? b.members : members, paths, tb, e, q, call.part_L);
+    GLIA_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sshmt_gather, dim3((unsigned)((rows + kSshmtThreads - 1) / kSshmtThreads)), dim3(kSshmtThreads), 0, call.stream,
+                       b.rows ? b.inc_off : inc_off, b.rows ? b.inc : inc, e, q, rows, c, named);
+    GLIA_HIP_TRY(hipGetLastError());
+    if (int rc = b.rows ? call.chunk(bterm, 1, rows, d_w) : call.chunk(term, 1, rows, d_w)) return rc;
+    *part_S = call.part_S;
+    *n_chunks = (rows + kMlpTrainChunk - 1) / kMlpTrainChunk;
+    return GLIA_HMT_OK;
+  }
+  int batch_grad(const double* h_w, const MlpBatchView& b, double* h_grad) override {
+    float ms[4] = {0, 0, 0, 0};
+    const double* part = nullptr;
+    long long chunks = 0;
+    double L;
+    if (int rc = call.begin_eval(h_w)) return rc;
+    if (int rc = enqueue_batch(call.w, b, &part, &chunks)) return rc;
+    GLIA_HIP_TRY(call.mark(2));
+    return call.finish_eval(3, &L, h_grad, ms, chunks);
+  }
 };
 
 }  // namespace

@@ -903,11 +903,9 @@ def merge_paths(order, max_len=3, min_len=2):
     return [mem[off[i]:off[i + 1]].copy() for i in range(n_paths.value)]
 
 
-def train_sshmt(ctx, rows, labels, unlabelled=(), n1=10, n2=10, minmax=None, init=None, **opts):
-    """train_sshmt_mlp / train_sshmt_logsig with the merge-path term (DESIGN 3.15).  rows / labels as train_mlp takes them; both may be
-    None when ws is off.  unlabelled: [(rows_u [n_i, dim], order_u [n_i, 3]), ...], row k of a block = merge k of its order.  Options:
-    the fields of MLPTrainOpts (wu and update_sigma_u included) and sigma_u, merge_target, path_target, max_path_length,
-    min_path_length.  ctx = None runs the definition on one host thread (train_sshmt_host)."""
+def _sshmt_inputs(who, rows, labels, unlabelled):
+    """What train_sshmt and train_sshmt_batches marshal alike: the labelled rows and labels (empty when None), the unlabelled blocks as
+    contiguous arrays, the number of columns and the glia_hmt_sshmt_block array whose pointers look into the blocks."""
     blocks = [(np.ascontiguousarray(r, dtype=np.float64), np.ascontiguousarray(o, dtype=np.uint32).reshape(-1, 3)) for r, o in unlabelled]
     dim = blocks[0][0].shape[1] if rows is None else np.asarray(rows).shape[1]
     rows = np.zeros((0, dim)) if rows is None else np.ascontiguousarray(rows, dtype=np.float64)
@@ -915,13 +913,22 @@ def train_sshmt(ctx, rows, labels, unlabelled=(), n1=10, n2=10, minmax=None, ini
     assert rows.ndim == 2 and labels.shape[0] == rows.shape[0]
     for r, o in blocks:
         if r.ndim != 2 or r.shape[1] != dim or r.shape[0] != o.shape[0]:
-            raise HmtError(ERR_ARG, "train_sshmt: a block needs one row of %d columns per merge" % dim)
-    o = SSHMTTrainOpts()
-    lib().glia_hmt_sshmt_train_opts_default(C.byref(o))
-    args, h, keep = _train_args("train_sshmt", o, n1, n2, dim, minmax, init, opts)
+            raise HmtError(ERR_ARG, who + ": a block needs one row of %d columns per merge" % dim)
     arr = (SSHMTBlock * max(len(blocks), 1))()
     for i, (r, od) in enumerate(blocks):
         arr[i] = SSHMTBlock(r.ctypes.data if len(r) else None, od.ctypes.data if len(od) else None, len(od))
+    return rows, labels, blocks, dim, arr
+
+
+def train_sshmt(ctx, rows, labels, unlabelled=(), n1=10, n2=10, minmax=None, init=None, **opts):
+    """train_sshmt_mlp / train_sshmt_logsig with the merge-path term (DESIGN 3.15).  rows / labels as train_mlp takes them; both may be
+    None when ws is off.  unlabelled: [(rows_u [n_i, dim], order_u [n_i, 3]), ...], row k of a block = merge k of its order.  Options:
+    the fields of MLPTrainOpts (wu and update_sigma_u included) and sigma_u, merge_target, path_target, max_path_length,
+    min_path_length.  ctx = None runs the definition on one host thread (train_sshmt_host)."""
+    rows, labels, blocks, dim, arr = _sshmt_inputs("train_sshmt", rows, labels, unlabelled)
+    o = SSHMTTrainOpts()
+    lib().glia_hmt_sshmt_train_opts_default(C.byref(o))
+    args, h, keep = _train_args("train_sshmt", o, n1, n2, dim, minmax, init, opts)
     _check(lib().glia_hmt_sshmt_train(ctx.h if ctx is not None else None, _np(rows) if len(rows) else None, C.c_int64(rows.shape[0]), C.c_int(dim),
                                       _np(labels) if len(labels) else None, arr, C.c_int(len(blocks)), *args))
     return MLPModel(h, n1, n2)
@@ -939,6 +946,83 @@ def last_sshmt_train_timing(ctx):
     out = {k: getattr(t, k) for k, _ in SSHMTTrainTiming._fields_ if k != "sup"}
     out["sup"] = {k: getattr(t.sup, k) for k, _ in MLPTrainTiming._fields_}
     return out
+
+
+class BatchOpts(C.Structure):
+    """glia_hmt_batch_opts: the sampler's seed (--bseed), epochs per iteration (--te 1), batches per iteration when that is <= 0 (--tb 1)"""
+    _fields_ = [("seed", C.c_uint64), ("epochs_per_iteration", C.c_int), ("batches_per_iteration", C.c_int)]
+
+
+class BatchTiming(C.Structure):
+    _fields_ = [("steps", C.c_int64), ("batches", C.c_int64), ("ms_plan", C.c_double), ("ms_upload", C.c_double), ("ms_steps", C.c_double),
+                ("ms_wall", C.c_double), ("syncs", C.c_int64), ("route", C.c_int32), ("plan_bytes", C.c_uint64)]      # glia_hmt_batch_timing
+
+
+def _batch_opts(batch):
+    """BatchOpts from None (the defaults), a BatchOpts or a dict of its fields"""
+    bo = BatchOpts()
+    lib().glia_hmt_batch_opts_default(C.byref(bo))
+    if isinstance(batch, BatchOpts):
+        return batch
+    for k, v in (batch or {}).items():
+        if k not in dict(BatchOpts._fields_):
+            raise TypeError("BatchOpts: unknown field " + k)
+        setattr(bo, k, v)
+    return bo
+
+
+def train_mlp_batches(ctx, rows, labels, n1=10, n2=10, minmax=None, init=None, batch=None, **opts):
+    """glia_hmt_mlp_train_batches: train_mlp with mini-batches.  Options as train_mlp's, with sup_batch_size (--bss) and
+    balance_sup_batch (--bb) honoured; batch: a BatchOpts or a dict of its fields (seed, epochs_per_iteration, batches_per_iteration).
+    The batches are this library's sampler's, a function of the seed -- not the reference's.  With no sampler asked for the result is
+    train_mlp's.  ctx = None: the definition on one host thread."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+    assert rows.ndim == 2 and labels.shape[0] == rows.shape[0]
+    o = MLPTrainOpts()
+    lib().glia_hmt_mlp_train_opts_default(C.byref(o))
+    bo = _batch_opts(batch)
+    args, h, keep = _train_args("train_mlp_batches", o, n1, n2, rows.shape[1], minmax, init, opts)
+    _check(lib().glia_hmt_mlp_train_batches(ctx.h if ctx is not None else None, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]),
+                                            _np(labels), args[0], C.byref(bo), *args[1:]))
+    return MLPModel(h, n1, n2)
+
+
+def train_sshmt_batches(ctx, rows, labels, unlabelled=(), n1=10, n2=10, minmax=None, init=None, batch=None, **opts):
+    """glia_hmt_sshmt_train_batches: train_sshmt with mini-batches: sup_batch_size, balance_sup_batch and uns_batch_size
+    (--bsu: batches of merge PATHS) honoured; batch as train_mlp_batches takes it.  ctx = None: the definition on one host thread."""
+    rows, labels, blocks, dim, arr = _sshmt_inputs("train_sshmt_batches", rows, labels, unlabelled)
+    o = SSHMTTrainOpts()
+    lib().glia_hmt_sshmt_train_opts_default(C.byref(o))
+    bo = _batch_opts(batch)
+    args, h, keep = _train_args("train_sshmt_batches", o, n1, n2, dim, minmax, init, opts)
+    _check(lib().glia_hmt_sshmt_train_batches(ctx.h if ctx is not None else None, _np(rows) if len(rows) else None, C.c_int64(rows.shape[0]),
+                                              C.c_int(dim), _np(labels) if len(labels) else None, arr, C.c_int(len(blocks)), args[0], C.byref(bo),
+                                              *args[1:]))
+    return MLPModel(h, n1, n2)
+
+
+def batch_plan(labels, n_paths, k, sup_batch_size=-1, uns_batch_size=-1, balance_sup_batch=0, pos_target=0.05, neg_target=0.95, seed=0):
+    """glia_hmt_batch_plan: the next k draws of the samplers of DESIGN 3.17 for labelled rows with these labels (+1 / -1, every row
+    counts) and n_paths merge paths -> (sup, uns, end): per draw the int32 array of rows, the int32 array of paths (empty without that
+    sampler) and whether the draw ended the epoch.  Host-only."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+    n_sup, n_uns = C.c_int64(0), C.c_int64(0)
+    head = (_np(labels) if len(labels) else None, C.c_int64(len(labels)), C.c_int64(n_paths), C.c_int(sup_batch_size), C.c_int(uns_batch_size),
+            C.c_int(balance_sup_batch), C.c_double(pos_target), C.c_double(neg_target), C.c_uint64(seed), C.c_int(k), C.byref(n_sup), C.byref(n_uns))
+    _check(lib().glia_hmt_batch_plan(*head, None, None, None, None, None))
+    so = np.zeros(k + 1, np.int64); uo = np.zeros(k + 1, np.int64)
+    sr = np.zeros(max(n_sup.value, 1), np.int32); up = np.zeros(max(n_uns.value, 1), np.int32)
+    end = np.zeros(max(k, 1), np.int32)
+    _check(lib().glia_hmt_batch_plan(*head, _np(so), _np(sr), _np(uo), _np(up), _np(end)))
+    return ([sr[so[i]:so[i + 1]].copy() for i in range(k)], [up[uo[i]:uo[i + 1]].copy() for i in range(k)], [bool(e) for e in end[:k]])
+
+
+def last_batch_timing(ctx):
+    """the last train_*_batches call of the context: mini-batch steps, batches, plan build and upload, the steps' device time, waits"""
+    t = BatchTiming()
+    _check(lib().glia_hmt_last_batch_timing(ctx.h, C.byref(t)))
+    return {k: getattr(t, k) for k, _ in BatchTiming._fields_}
 
 
 class TrainOpts(C.Structure):

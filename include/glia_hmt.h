@@ -440,8 +440,8 @@ int glia_hmt_last_forest_oob_timing(const glia_hmt_ctx* ctx, glia_hmt_forest_oob
  * (type/energy_function.hxx:164-230, alg/function.hxx:171-267), the vanilla / Adam / momentum updates with a fixed or an adaptive step
  * (alg/gd.hxx) and the sigma rule and outer loop of sshmt_util.hxx:140-207.  The arithmetic is this library's own definition
  * (glia_amd/csrc/mlp_backward.hpp): no parity with Eigen's sums, Boost's Gaussian or the OpenMP partial sums is
- * possible or claimed.  The unsupervised term is glia_hmt_sshmt_train's, below; batch samplers and altSU are not built: an opts struct
- * that asks for any of them here is GLIA_HMT_ERR_UNSUPPORTED with a message naming the field.  sigma^2 is updated only when update_sigma_s is set (the reference's tool
+ * possible or claimed.  The unsupervised term is glia_hmt_sshmt_train's, below; batch samplers are glia_hmt_mlp_train_batches', further
+ * below, and altSU is not built: an opts struct that asks for any of them here is GLIA_HMT_ERR_UNSUPPORTED with a message naming the field.  sigma^2 is updated only when update_sigma_s is set (the reference's tool
  * also updates it whenever it runs with --v 0).
  * glia_hmt_mlp_train_opts: the tool's options and defaults; min_sigma2 is the floor the tool passes (0.0); seed keys the initial
  * weights of an MLP (a logsig model starts at zeros; h_init, when given, takes precedence over both). */
@@ -522,7 +522,8 @@ int glia_hmt_last_mlp_train_timing(const glia_hmt_ctx* ctx, glia_hmt_mlp_train_t
  * prod_{i>=j} (1 - f_i)) (alg/dnf.hxx:126-326), the residual e = path_target^n - D (sshmt/input.hxx:36-39) and L_U = sum e^2
  * (alg/function.hxx:171-267).  sigma_u^2 = max(min_sigma2, L_U / P) under update_sigma_u, updated after sigma_s^2
  * (sshmt_util.hxx:148-222).  Without a single path the term is off (input.hxx:120-121).  The arithmetic is this library's own
- * definition (glia_amd/csrc/sshmt_paths.hpp).  Batch samplers and alt_su stay refused by name. */
+ * definition (glia_amd/csrc/sshmt_paths.hpp).  Batch samplers (glia_hmt_sshmt_train_batches, below) and alt_su stay refused
+ * by name. */
 typedef struct { const double* rows; const uint32_t* order; int64_t n_merges; } glia_hmt_sshmt_block;  /* rows [n_merges][dim], order [n_merges][3] */
 typedef struct {
   glia_hmt_mlp_train_opts base;          /* wu and update_sigma_u are honoured HERE; the batch fields and alt_su stay refused */
@@ -559,6 +560,61 @@ typedef struct {
   uint64_t u_device_bytes;
 } glia_hmt_sshmt_train_timing;
 int glia_hmt_last_sshmt_train_timing(const glia_hmt_ctx* ctx, glia_hmt_sshmt_train_timing* out);
+
+/* ---- mini-batch training: --bss, --bsu, --bb, --te, --tb of the four trainers -------------------------------
+ * An explicit opt-in: the entry points above keep refusing the batch fields by name, because a caller of these accepts THIS library's
+ * sampler.  The reference shuffles with std::random_shuffle (type/sampler.hxx:53,120,213), whose rand() state also depends on every
+ * shuffled parfor before it (sshmt/sshmt_util.hxx:18,37, sshmt/input.hxx:43): its batch sequence is not a function of its inputs, so
+ * no parity is possible or claimed.  Here permutation number s of a stream is a pure function of (seed, stream, s, n) (DESIGN.md
+ * 3.17; glia_amd/csrc/mlp_batch.hpp); streams: 0 = merge paths, 1 = labelled rows, 2 + c = class c of a balanced batch.
+ * Samplers (sshmt/sshmt_util.hxx:69-107): sup_batch_size B > 0: UniformBatchSampler over the labelled rows (type/sampler.hxx:45-102: a
+ * batch that reaches the end of the permutation goes on from its START, then the permutation is reshuffled and the batch ends the
+ * epoch); with balance_sup_batch: ClassBatchSampler (type/sampler.hxx:105-233), B / 2 rows of the positive target then B - B / 2 of the
+ * negative; balance_sup_batch alone: the smaller class's size from BOTH classes, classes in ascending target; uns_batch_size B > 0:
+ * uniform over the merge PATHS.  A step of the optimiser (alg/gd.hxx:86-157) is then epochs_per_iteration epochs of { draw, gradient
+ * over the batch, update } -- a draw asks the path sampler, then the row sampler, and ends the epoch when EITHER does
+ * (type/energy_function.hxx:42-49) -- or, with epochs_per_iteration <= 0, batches_per_iteration batches.  A term without a sampler takes
+ * all its rows in every batch (type/function_input.hxx:119-134).  An iteration still begins with the evaluation over all rows
+ * (alg/gd.hxx:59-71,176,226); the adaptive rule's roll-back runs the step again on NEW batches (alg/gd.hxx:242-252). */
+typedef struct {
+  uint64_t seed;                     /* --bseed */
+  int epochs_per_iteration;          /* --te 1 */
+  int batches_per_iteration;         /* --tb 1 */
+} glia_hmt_batch_opts;
+void glia_hmt_batch_opts_default(glia_hmt_batch_opts* opts);
+/* glia_hmt_mlp_train / glia_hmt_sshmt_train with opts' sup_batch_size, uns_batch_size and balance_sup_batch honoured (ctx NULL: on one
+ * host thread, the definition).  With no sampler asked for they return what those return, byte for byte.  GLIA_HMT_ERR_ARG: fewer
+ * labelled rows or paths than the batch size ("Error: totalSize must be greater than batchSize"), a class without a row or with fewer
+ * rows than its share (the reference reads out of range there), equal targets under balance_sup_batch, a sampler for a term that is
+ * off.  alt_su stays GLIA_HMT_ERR_UNSUPPORTED.  On the device the batches of a step run back to back on the stream, weights and
+ * optimiser state in device memory, one wait per step; option GLIA_HMT_BATCH = step runs one batch per evaluation with the update on
+ * the host instead and gives the same bytes. */
+int glia_hmt_mlp_train_batches(glia_hmt_ctx* ctx, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels,
+                               const glia_hmt_mlp_train_opts* opts, const glia_hmt_batch_opts* batch, const double* h_min, const double* h_max,
+                               const double* h_init, glia_hmt_mlp_model** out);
+int glia_hmt_sshmt_train_batches(glia_hmt_ctx* ctx, const double* h_rows, int64_t n_rows, int dim, const int32_t* h_labels,
+                                 const glia_hmt_sshmt_block* blocks, int n_blocks, const glia_hmt_sshmt_train_opts* opts,
+                                 const glia_hmt_batch_opts* batch, const double* h_min, const double* h_max, const double* h_init,
+                                 glia_hmt_mlp_model** out);
+/* Host-only: the next k draws of the samplers.  h_labels [n_rows]: +1 / -1 of the labelled rows in the trainer's order (every row
+ * counts); n_paths merge paths.  Call with the four arrays NULL for *n_sup and *n_uns (entries over all k draws), then with
+ * sup_offsets [k + 1], sup_rows [*n_sup], uns_offsets [k + 1], uns_paths [*n_uns]; end_of_epoch [k] (or NULL): whether draw i ended the
+ * epoch.  A sampler that was not asked for leaves its lists empty. */
+int glia_hmt_batch_plan(const int32_t* h_labels, int64_t n_rows, int64_t n_paths, int sup_batch_size, int uns_batch_size,
+                        int balance_sup_batch, double pos_target, double neg_target, uint64_t seed, int k, int64_t* n_sup, int64_t* n_uns,
+                        int64_t* sup_offsets, int32_t* sup_rows, int64_t* uns_offsets, int32_t* uns_paths, int32_t* end_of_epoch);
+/* the last *_train_batches call of this context; option GLIA_HMT_BATCH = stream (default) | step, read per call */
+enum { GLIA_HMT_BATCH_STREAM = 0, GLIA_HMT_BATCH_STEP = 1 };
+typedef struct {
+  int64_t steps, batches;            /* mini-batch steps (each in the place of one update); batches over all of them */
+  double ms_plan, ms_upload;         /* the host builds the plans of the steps; their copies to the device (one per step) */
+  double ms_steps;                   /* device time of the steps, from events (route step: wall clock of its evaluations and updates) */
+  double ms_wall;                    /* wall clock of the steps, all of the above and the waits included */
+  int64_t syncs;                     /* waits for the stream inside the steps: one per step on the stream route */
+  int32_t route;                     /* GLIA_HMT_BATCH_STREAM | GLIA_HMT_BATCH_STEP */
+  uint64_t plan_bytes;               /* the largest plan */
+} glia_hmt_batch_timing;
+int glia_hmt_last_batch_timing(const glia_hmt_ctx* ctx, glia_hmt_batch_timing* out);
 
 /* Length of one feature vector for the configuration the rag was built with (BoundaryClassificationFeats::dim,
  * hmt/bc_feat.hxx:225-230; or selectFeatures' length with --simpf). */
