@@ -87,7 +87,6 @@ HistSpec make_hist_spec(int bins, double lo, double hi) {
 // Which restatement of glibc's log2 / log reproduces THIS host's libm bit for bit (the reference calls std::log2 in
 // stats::entropy, util/stats.hxx:150, and std::log in slog, glia_base.hxx:80-81; the device must return the same bits).
 // Probe vector: histogram fractions c/n, values around 1 (the near-one branch), and a sweep over exponents.
-// GLIA_HMT_LIBM = device | sse2 | fma overrides the choice (tests).
 static LibmSel probe_host_libm() {
   std::vector<double> xs;
   uint64_t s = 0x9E3779B97F4A7C15ull;
@@ -132,6 +131,14 @@ static LibmSel probe_host_libm() {
   if (l2) sel.log2_variant = kLibmSse2;
   if (lf) sel.log_variant = kLibmFma; else if (ls) sel.log_variant = kLibmSse2;
   if (pf) sel.pow_variant = kLibmFma; else if (ps) sel.pow_variant = kLibmSse2;
+  return sel;
+}
+// What a context uses: the probe's answer (taken once per process), unless GLIA_HMT_LIBM = device | sse2 | fma overrides the choice
+// (tests).  The override is read at EVERY context creation and probe call, not only at the process's first: a test makes a context
+// for each family in one process.
+static LibmSel host_libm() {
+  static const LibmSel probed = probe_host_libm();
+  LibmSel sel = probed;
   std::string ov;
   if (option("GLIA_HMT_LIBM", &ov)) {
     const char* e = ov.c_str();
@@ -169,7 +176,7 @@ int glia_hmt_ctx_create(int device, void* hip_stream, glia_hmt_ctx** out) {
     return GLIA_HMT_OK;
   }();
   if (rc) { glia_hmt_ctx_destroy(c); return rc; }      // (destroys what exists: every member starts out null)
-  static const LibmSel sel = probe_host_libm();
+  const LibmSel sel = host_libm();
   c->libm = sel;
   *out = c;
   // The call succeeds either way; a host libm none of the restatements reproduces is reported through glia_hmt_last_error()
@@ -207,13 +214,13 @@ int glia_hmt_ctx_libm_exp(const glia_hmt_ctx* c, int* exp_variant) {
 
 int glia_hmt_host_libm_probe_exp(int* exp_variant) {
   if (!exp_variant) return GLIA_HMT_ERR_ARG;
-  *exp_variant = probe_host_libm().exp_variant;
+  *exp_variant = host_libm().exp_variant;
   return GLIA_HMT_OK;
 }
 
 int glia_hmt_host_libm_probe_pow(int* pow_variant) {
   if (!pow_variant) return GLIA_HMT_ERR_ARG;
-  *pow_variant = probe_host_libm().pow_variant;
+  *pow_variant = host_libm().pow_variant;
   return GLIA_HMT_OK;
 }
 
@@ -228,7 +235,7 @@ int glia_hmt_host_rmap_ranks(const uint32_t* labels, const int64_t* first_voxel,
 }
 
 int glia_hmt_host_libm_probe(int* log2_variant, int* log_variant) {
-  const LibmSel sel = probe_host_libm();
+  const LibmSel sel = host_libm();
   if (log2_variant) *log2_variant = sel.log2_variant;
   if (log_variant) *log_variant = sel.log_variant;
   return GLIA_HMT_OK;

@@ -13,7 +13,7 @@
 #include "median_layout.hpp"
 
 namespace glia {
-GLIA_DECLARE_GREEDY_BC(greedy_bc) {
+int greedy_bc(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier& clf, hipStream_t stream, const BcRequest& req, MergeResult* out) {
   auto* fn = &greedy_bc_generic;
   const bool common = cfg.K == 1 && cfg.n_region == 1 && cfg.n_rlabel == 0 && cfg.n_boundary == 1 && !cfg.use_hist && !cfg.use_log &&
                       !cfg.use_simple && !option("GLIA_HMT_BC_NOCOMMON");
@@ -21,7 +21,7 @@ GLIA_DECLARE_GREEDY_BC(greedy_bc) {
   else if (cfg.libm_log2 == kLibmSse2 && cfg.libm_log == kLibmSse2 && cfg.libm_pow == kLibmSse2) fn = common ? &greedy_bc_sse2_common : &greedy_bc_sse2;
   if (option("GLIA_HMT_BC_GENERIC")) fn = &greedy_bc_generic;       // tests: the run-time-dispatch instance
   if (clf.kind == 2) fn = &greedy_bc_mlp;                           // the one instance that holds the MLP scorer
-  const int rc = fn(rag, cfg, clf, stream, req, out);
+  const int rc = greedy_bc_run(fn(), rag, cfg, clf, stream, req, out);
   return req.init_only ? rc : finish_merge_order(rc, out->order.data(), out->n, (uint32_t)rag.R, stream);
 }
 }  // namespace glia

@@ -137,7 +137,7 @@ struct MedianFeatIn {
 int median_feature_stats(const MedianFeatIn& in, hipStream_t stream, std::vector<double>* reg, std::vector<double>* bnd, std::vector<unsigned long long>* area);
 // GLIA_USE_MEDIAN_AS_FEATS for the INITIAL edges (median_init.hip): every leaf's values and every directed pair's boundary values are
 // sorted once per listed image, and the sets of a record (u, v) -- both leaves -- are selections over those runs.  The records are the
-// ones of the classifier loop's state (greedy_bc.hip); records [e0, e1) that are table edges of the shard get, at slot e - e0,
+// ones of the classifier loop's state (greedy_bc_state.hpp); records [e0, e1) that are table edges of the shard get, at slot e - e0,
 //   reg[((slot * 3 + k) * n_r + c) * 3 + q]   k = P(u) | P(v) | P(u + v),               q = median | mean | stddev
 //   bnd[((slot * 4 + k) * n_b + c) * 3 + q]   k = B(u) | B(v) | B(u + v) | shared boundary
 // (device arrays; u < v are the record's dense leaf ids, NOT the x1 / x2 of the row).  forced / n_merges of `in` are not read.
@@ -194,21 +194,28 @@ struct BcRequest {
   const DeviceMlp* mlp = nullptr;               // DeviceClassifier::kind == 2: the model (its weights on the device) ...
   int exp_variant = 0;                          // ... and the restatement of the host's exp its sigmoid uses (glibc_math.hpp; 0 = the device's exp)
 };
-// greedy_bc.hip is compiled five times: with the libm restatements of the feature code (glibc_math.hpp) selected at run time
-// (any combination, incl. "unpinned"), and with the two combinations real hosts have -- glibc's FMA build and its non-FMA
-// build -- fixed at compile time (a run-time choice between three logarithms at every call site costs the classifier loop
-// 5 %).  greedy_bc() picks the instance from cfg.libm_* (api_loops.cpp).  A sixth instance, greedy_bc_mlp (GLIA_BC_MLP, libm at run
-// time), is the only one that holds the MLP scorer (DeviceClassifier::kind == 2): compiled into the other five it cost the forest's
-// loop a third of its rate (more spilled registers, a larger kernel argument), so they are built without it and refuse kind 2.
-#define GLIA_DECLARE_GREEDY_BC(name) \
-  int name(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier& clf, hipStream_t stream, const BcRequest& req, MergeResult* out)
-GLIA_DECLARE_GREEDY_BC(greedy_bc_generic);
-GLIA_DECLARE_GREEDY_BC(greedy_bc_fma);
-GLIA_DECLARE_GREEDY_BC(greedy_bc_sse2);
-GLIA_DECLARE_GREEDY_BC(greedy_bc_fma_common);      // + GLIA_BC_COMMON (bc_features.hpp): one image on the region and boundary lists, no --logs / --simpf / histogram columns
-GLIA_DECLARE_GREEDY_BC(greedy_bc_sse2_common);
-GLIA_DECLARE_GREEDY_BC(greedy_bc_mlp);
-GLIA_DECLARE_GREEDY_BC(greedy_bc);
+// The loop's set-up kernels and its host driver, greedy_bc_run, are compiled once (greedy_bc_setup.hip).  The three kernels whose
+// feature code is specialised -- the initial scores in both layouts and the loop itself (greedy_bc.hip) -- are compiled SIX times,
+// and each instance is what the driver is given to launch them (BcInstance, greedy_bc_state.hpp):
+//   1      generic: the libm restatements of the feature code (glibc_math.hpp) selected at run time (any combination, incl. "unpinned");
+//   2, 3   fma, sse2: the two combinations real hosts have -- glibc's FMA build and its non-FMA build -- fixed at compile time
+//          (GLIA_LIBM_FIXED; a run-time choice between three logarithms at every call site costs the loop 5 %);
+//   4, 5   fma_common, sse2_common: the same with GLIA_BC_COMMON (bc_features.hpp): one image on the region and boundary lists, no
+//          --logs / --simpf / histogram columns;
+//   6      mlp (GLIA_BC_MLP, libm at run time): the only one that holds the MLP scorer (DeviceClassifier::kind == 2) -- compiled into
+//          the other five it cost the forest's loop a third of its rate (more spilled registers, a larger kernel argument), so they
+//          are built without it and the driver refuses kind 2 for them.
+// greedy_bc() picks the instance from cfg.libm_*, the feature lists and clf.kind (api_loops.cpp).
+struct BcInstance;
+const BcInstance& greedy_bc_generic();
+const BcInstance& greedy_bc_fma();
+const BcInstance& greedy_bc_sse2();
+const BcInstance& greedy_bc_fma_common();
+const BcInstance& greedy_bc_sse2_common();
+const BcInstance& greedy_bc_mlp();
+int greedy_bc_run(const BcInstance& inst, const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier& clf, hipStream_t stream,
+                  const BcRequest& req, MergeResult* out);
+int greedy_bc(const RagArrays& rag, const BcCfg& cfg, const DeviceClassifier& clf, hipStream_t stream, const BcRequest& req, MergeResult* out);
 // bc_feat for a given order as a batch computation over the known merge tree (bc_feat_batch.hip): rows [M][cfg.fdim] in the layout
 // greedy_bc writes them.  forced: dense region pairs of the merges, validated by the caller.
 struct BcFeatBatchInfo {

@@ -487,9 +487,11 @@ def test_sharded_initial_edge_scoring(ctx):
 
 @pytest.mark.parametrize("shape,S,G", [((40, 36, 28), 6, 12), ((72, 72), 4, 16)])
 def test_loop_instances_agree(ctx, shape, S, G):
-    """greedy_bc.hip is compiled five times (hmt_internal.hpp): everything chosen at run time, the libm variants fixed, and
-    libm + the common configuration (one image, full vector) fixed.  The dispatcher's two overrides force the less specialised
-    instances; all three tiers must return the oracle's merge order and saliencies and bit-identical feature rows."""
+    """The loop's three specialised kernels (greedy_bc.hip) are compiled six times (hmt_internal.hpp); a forest or the stub runs one
+    of three tiers: everything chosen at run time, the libm variants fixed, and libm + the common configuration (one image, full
+    vector) fixed.  The dispatcher's two overrides force the less specialised tiers; all three must return the oracle's merge order
+    and saliencies and bit-identical feature rows.  (This host's libm family only: both families are
+    test_both_libm_families_and_all_tiers_agree's; the sixth instance, the MLP's, is test_gpu_bc_mlp.py's.)"""
     from glia_amd import hmt
     from oracle import pyoracle as O
     labels, pb = O.synth(shape, S, G)
@@ -506,6 +508,63 @@ def test_loop_instances_agree(ctx, shape, S, G):
         assert o.shape == o_ref.shape and (o == o_ref).all() and (s == s_ref).all()
         assert (f.view(np.uint64) == results[0][2].view(np.uint64)).all()
     assert (results[0][2].view(np.uint64) == f_ref.view(np.uint64)).all(), "feature rows are bit-identical to the oracle on Q8 inputs"
+
+
+def test_both_libm_families_and_all_tiers_agree(ctx):
+    """A host has one libm family, so a context of its own choosing runs only the instances of that family (and the run-time one).
+    Here a context is created for each family (GLIA_HMT_LIBM is read at every context creation), and under each of the three tiers
+    -- and the run-time tier once more at minimal capacities, so that the driver grows the edge and the entry arrays -- the stub's
+    loop, a 31-tree forest's loop (helper workgroups), the initial scores and bc_feat of the returned orders run: five of the six
+    instances, with the set-up and the driver they share.  Inside a family every result is the same byte for byte across the tiers;
+    the family this host's libm belongs to (ctx.libm()) also equals the oracle: order, saliencies and rows of the stub's and of the
+    forest's run, and bc_feat's rows of both orders (bc_feat of a loop's own order gives that loop's rows).  The oracle has no call
+    for the initial scores alone: those are held to each other across the tiers, and their maximum to the forest run's first
+    saliency, which the oracle's run confirms."""
+    from glia_amd import hmt
+    from oracle import pyoracle as O
+    import _rf
+    labels, pb = O.synth((40, 36, 28), 6, 12)
+    stub = 11 + 4 * 3 + 7 + 1
+    ocfg = O.make_cfg(pb, rb=[(pb, 8, 0.0, 1.0)])
+    ref_stub = O.Rag(labels).merge_order_bc(ocfg, None, stub_index=stub, want_feats=True)      # (a Rag per run: a run merges its regions)
+    forest = _rf.random_forest(np.random.default_rng(7), 31, 6, ref_stub[2])
+    ref_forest = O.Rag(labels).merge_order_bc(ocfg, O.make_forest(forest, -1), want_feats=True)
+    tiers = ({}, {"GLIA_HMT_BC_NOCOMMON": "1"}, {"GLIA_HMT_BC_GENERIC": "1"}, {"GLIA_HMT_BC_GENERIC": "1", "GLIA_HMT_MINCAP": "1"})
+
+    def same(a, b):            # byte for byte (orders are uint32, everything else float64)
+        return a.shape == b.shape and a.dtype == b.dtype and (a.view(np.uint64 if a.dtype == np.float64 else a.dtype) == b.view(np.uint64 if b.dtype == np.float64 else b.dtype)).all()
+
+    compared = 0
+    for family in ("fma", "sse2"):
+        with hmt.options(GLIA_HMT_LIBM=family):
+            fctx = hmt.Context(0)
+        assert fctx.libm() == ((1, 2) if family == "fma" else (1, 1))
+        with tempfile.TemporaryDirectory() as d:
+            path = os.path.join(d, "model.bin")
+            _rf.write_model(path, forest)
+            rf = hmt.RandomForest(fctx, path, predict_label=-1)
+        results = []
+        for env in tiers:
+            with hmt.options(**env):
+                rm = _gpu_rm(fctx, labels, pb)
+                o1, s1, f1 = rm.merge_order_bc(hmt.FeatureStubClassifier(fctx, stub), want_feats=True)
+                o2, s2, f2 = rm.merge_order_bc(rf, want_feats=True)
+                init = rm.score_initial_edges_shard(rf, 0, 1)
+                results.append([o1, s1, f1, o2, s2, f2, rm.bc_feat(o1), rm.bc_feat(o2), init])
+                rm.close()
+        rf.close()
+        first = results[0]
+        assert len(first[0]) == len(first[3]) == len(ref_stub[0]) and first[4][0] == first[8][np.isfinite(first[8])].max()
+        for r in results[1:]:
+            for got, want in zip(r, first):
+                assert same(got, want)
+        if fctx.libm() == ctx.libm():          # this host's own family: the reference's bits
+            compared += 1
+            for got, want in zip(first[:6], list(ref_stub) + list(ref_forest)):
+                assert same(got, want)
+            assert same(first[6], ref_stub[2]) and same(first[7], ref_forest[2])
+        fctx.close()
+    assert compared == (1 if ctx.libm_pinned() else 0)
 
 
 def _median_loose_mask(dim, n_thr, n_r, n_rl, n_b, hist_cols=(0, 0, 0)):

@@ -47,7 +47,7 @@ from _hub_cases import CLASSES, fragile_comb_image, fragile_comb_image_f32, hub_
 
 STUB = 11 + 4 * 3 + 7 + 1          # x0.b0.mean
 kCap, kLdsCap4 = 96, 2252          # W.cap's limit; kWsBytes / (8 + 8 K) at K = 4
-kFragCap, kHelpChunk, kJobMax = 4096, 8, 16384      # greedy_bc.hip: work-list entries per batch; records per helper round; records per job
+kFragCap, kHelpChunk, kJobMax = 4096, 8, 16384      # greedy_bc.hip, greedy_bc_state.hpp: work-list entries per batch; records per helper round; records per job
 kCombN, kCombY = 1100, 2           # fragile comb: cells (chain entries of hub-Y), Y's label
 
 
