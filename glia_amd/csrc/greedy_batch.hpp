@@ -6,6 +6,8 @@
 //   * A member that fails validation has only READ global memory; the commit's stores are waited for at the END of the next scan.
 //   * b.kill[] / b.nkill are filled by committing waves in front of the commit barrier and consumed (then cleared by thread 0)
 //     behind the scan's closing barrier; a kill that matches no window item is harmless.
+//   * b.truehit is written (atomic OR, lane 0 of the earlier member's wave) between [B:compute] and [B:exact], read behind [B:exact]
+//     and in front of [B:commit], and cleared by thread 0 where b.nkill is; [B:exact] sits in a branch every wave takes or none does.
 //   * Below the horizon (WinState::wch) an edge is neither queued nor counted nor marked dead: WinState::rdead speaks for it.
 //     It has no record either (store_new_edge<true>): a record exists iff the edge was created at or above the horizon, or has
 //     been through a baseline.  Both callers of store_new_edge here go through BATCH = true: the commit and batch_contract_wide.
@@ -32,7 +34,12 @@ namespace {
 // neighbour matching in a private LDS table, new means), publishes what it creates (count, largest new saliency, a
 // bitmap of the regions it touches); every wave then evaluates (a) and (b) for the whole batch and the valid prefix
 // COMMITS (stores, queue inserts, deaths) in parallel.  Nothing is speculated on memory: a member that fails the check
-// has only read.  Contractions with more than 64 list entries take the whole workgroup, one at a time.
+// has only read.  Contractions with more than kMemMax list entries take the whole workgroup, one at a time.
+// (b) is tested as stated.  The bitmap (ids mod 2048) is a filter: it holds c0's regions and live neighbours, so a pair it does
+// not flag is independent, but two ids of one residue flag a pair that shares nothing -- at 1024^3 nearly every flag is of that kind.
+// A flagged pair is therefore decided by c0's wave, which compares c1's two ids with the ids it entered into its bitmap (they are in
+// its registers) and reports a real conflict in BatchShared::truehit.  The set so decided is a subset of what the bitmap flags and
+// is exactly (b), so the induction above is untouched; rounds without a flagged pair run as they did.
 // The result is bit-identical to the sequential kernels (same gate: SHA-1 of the whole 1024^3 order).
 // =====================================================================================================================
 constexpr uint32_t kBatchKill = 32;
@@ -47,6 +54,7 @@ struct BatchShared {
   uint32_t m_newcount[kNW], m_total[kNW], m_ok[kNW];
   double m_maxsal[kNW];
   uint32_t bad;
+  uint32_t truehit;                         // bit j: member j of this round shares a region or a neighbour with an earlier member (exact)
 };
 
 // The largest and the second-largest of the 64 lanes' (a1, a2) pairs of unsigned keys -- saliency images or seqs -- (a1 >= a2
@@ -73,6 +81,7 @@ __device__ __forceinline__ void wave_top2_ord(unsigned long long& a1, unsigned l
 #ifdef GLIA_HMT_PROFILE
 __device__ unsigned long long g_scanprof[8];
 __device__ unsigned long long g_scanfill[3][3];           // scans by what came before (reload or eviction / narrow round / wide contraction) x fill n (<= 512, <= 1024, more)
+__device__ unsigned long long g_kovf;                     // scans that found the kill list overflowed (cumulative)
 #define SCAN_T(i) do { if (tid == 0) { const unsigned long long tn_ = __builtin_readcyclecounter(); g_scanprof[i] += tn_ - st_; st_ = tn_; } } while (0)
 #else
 #define SCAN_T(i) do {} while (0)
@@ -86,6 +95,7 @@ __device__ __forceinline__ void batch_scan(const WinState& st, WinShared& w, Bat
   const uint32_t n = w.n < st.wcap ? w.n : st.wcap, nk = b.nkill < kBatchKill ? b.nkill : kBatchKill, kovf = b.kovf;   // [R:scan-head]
 #ifdef GLIA_HMT_PROFILE
   if (tid == 0) g_scanfill[from][n <= 512u ? 0 : n <= 1024u ? 1 : 2] += 1;
+  if (tid == 0 && kovf) g_kovf += 1;
 #endif
   // Slot ownership is STRIPED over the waves (lane l of wave v scans the l-th slot of chunk (v + l) mod 8 in every block
   // of 512): a reload fills consecutive slots with consecutive keys, and the exact top of the queue is only as long as
@@ -197,7 +207,7 @@ __device__ __forceinline__ void batch_scan(const WinState& st, WinShared& w, Bat
   if ((tid & 63) == 0) { b.part1[tid >> 6] = m1; b.part2[tid >> 6] = m2; }   // [W:part12]
   full_barrier();                  // ... and are performed here, before the next round loads the lists they rewrote   // [B:scan-end]
   SCAN_T(4);
-  if (tid == 0) { b.nkill = 0; b.kovf = 0; }   // [W:kill-clear]
+  if (tid == 0) { b.nkill = 0; b.kovf = 0; b.truehit = 0; }   // [W:kill-clear]   // [W:truehit-clear]
 }
 
 #ifdef GLIA_HMT_PROFILE
@@ -304,7 +314,7 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_batch_kernel(WinState s
   unsigned long long k = st.ctrl[CTRL_MERGES], ne = st.ctrl[CTRL_EDGES], pool_used = st.ctrl[CTRL_ENTRIES];
   uint32_t status = ST_RUN;
   win_enter(st, w, s, tid);
-  if (tid == 0) { b.nkill = 0; b.kovf = 0; b.bad = 0; }
+  if (tid == 0) { b.nkill = 0; b.kovf = 0; b.bad = 0; b.truehit = 0; }
   b.bitmap[wave][lane] = 0;
   if (tid < kNW) { Key z; z.sal = -__builtin_inf(); z.seq = 0; z.arg = 0; b.part1[tid] = z; b.part2[tid] = z; }
   full_barrier();   // [B:enter]
@@ -320,7 +330,10 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_batch_kernel(WinState s
   uint32_t* const sg_pos = reinterpret_cast<uint32_t*>(&s.stage[0]) + (2 * kNW + wave) * kTab;
   double* const sg_mean = reinterpret_cast<double*>(reinterpret_cast<uint32_t*>(&s.stage[0]) + 3 * kNW * kTab) + wave * kTab;
 #ifdef GLIA_HMT_PROFILE
-  unsigned long long bph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, blast = __builtin_readcyclecounter(), brounds = 0, bmembers = 0, bvalid = 0, bwide = 0, bcut_sal = 0, bcut_dep = 0;
+  unsigned long long bph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, blast = __builtin_readcyclecounter(), brounds = 0, bmembers = 0, bvalid = 0, bwide = 0, bcut_sal = 0;
+  // rounds whose committed prefix ends at a wide member / at a true conflict / at a bitmap hit that is none; rounds with a flagged pair;
+  // rounds in which the bitmap alone ends the prefix early; members the committed prefix is shorter by than the exact one
+  unsigned long long bcut_wide = 0, bcut_true = 0, bcut_false = 0, bflag = 0, bcut_falsebm = 0, blost = 0;
   unsigned long long bw_n[4] = {0, 0, 0, 0}, bw_cyc[4] = {0, 0, 0, 0}, bw_ent[4] = {0, 0, 0, 0}, bw_new[4] = {0, 0, 0, 0};
   uint32_t bep_above = 0, bep_below = 0;                        // (per thread) edges this thread's commits created at or above / below the horizon
   unsigned long long bsel[2] = {0, 0}, bsel_n[2] = {0, 0};      // loop-top cycles (the select bucket, BPH(0)) of narrow rounds / wide pops, and their number
@@ -485,19 +498,60 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_batch_kernel(WinState s
       const uint32_t u = w.u[kj.arg], v = w.v[kj.arg];
       const uint32_t tj = b.m_total[j], nj = b.m_newcount[j];   // [R:members]
       double pm = -__builtin_inf();
-      uint32_t hit = 0, pre_n = 0, pre_t = 0;
+      uint32_t hitm = 0, pre_n = 0, pre_t = 0;                             // hitm, bit i: u or v is in the bitmap of member i (< j)
 #pragma unroll
       for (uint32_t i = 0; i < (uint32_t)kNW; ++i) {
         const double ms = b.m_maxsal[i];
-        const uint32_t bu = b.bitmap[i][(u >> 5) & 63u], bv = b.bitmap[i][(v >> 5) & 63u];
+        const uint32_t bu = b.bitmap[i][(u >> 5) & 63u], bv = b.bitmap[i][(v >> 5) & 63u];   // [R:bitmap]
         const uint32_t ti = b.m_total[i], ni = b.m_newcount[i];
-        if (i < j) { pm = ms > pm ? ms : pm; hit |= ((bu >> (u & 31u)) | (bv >> (v & 31u))) & 1u; pre_n += ni; pre_t += ti; }
+        if (i < j) { pm = ms > pm ? ms : pm; hitm |= (((bu >> (u & 31u)) | (bv >> (v & 31u))) & 1u) << i; pre_n += ni; pre_t += ti; }
       }
-      const bool okj = j < M && tj != 0xFFFFFFFFu && (j == 0u || (kj.sal > pm && hit == 0u));
-      const uint32_t okbits = (uint32_t)(__ballot(lane < kNW && okj) & 0xFFull);
-      V = (uint32_t)__builtin_ctz(~okbits);                               // members 0 .. V-1 are certain
+      // rule (a) and the wide-member cut alone bound the prefix: only pairs (i, j) below that bound can matter
+      const bool oka = j < M && tj != 0xFFFFFFFFu && (j == 0u || kj.sal > pm);
+      const uint32_t Va = (uint32_t)__builtin_ctz(~(uint32_t)(__ballot(lane < kNW && oka) & 0xFFull));
+      // Rule (b): the bitmap is the cheap filter (ids mod 2048: a hit may come from another id of the same residue), the wave of the
+      // earlier member decides a flagged pair exactly.  Every wave has computed the same hitm from the same LDS words -- all of them
+      // written in front of [B:compute] and none rewritten before [B:commit] -- so `flagged` is the same in every wave of the
+      // workgroup, and the branch below, which holds a barrier, is uniform (as the "compact first?" test is by [R:wn-round]).
+      const uint32_t flagged = (uint32_t)__ballot(lane < (int)Va && hitm != 0u);      // (Va <= 8: lane = j there)
+      uint32_t th = 0;
+      if (flagged) {
+        // Wave i holds member i (narrow: i < Va) and answers for every flagged j > i from its registers: fe[p].rs under act[p] is exactly
+        // what it entered into its bitmap (live entries: not the contracted edge, no tombstones), besides its own r0 and r1.
+        const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+        uint32_t mine = 0;
+        for (uint32_t jj = wv + 1u; jj < Va; ++jj) {
+          if (((uint32_t)__builtin_amdgcn_readlane((int)hitm, (int)jj) >> wv & 1u) == 0u) continue;
+          const uint32_t uj = (uint32_t)__builtin_amdgcn_readlane((int)u, (int)jj), vj = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)jj);
+          bool c = (uj == r0) | (uj == r1) | (vj == r0) | (vj == r1);
+#pragma unroll
+          for (int p = 0; p < kMemP; ++p) c |= act[p] & ((fe[p].rs == uj) | (fe[p].rs == vj));
+          if (__ballot(c) != 0ull) mine |= 1u << jj;
+        }
+        if (mine != 0u && lane == 0) atomicOr(&b.truehit, mine);   // [W:truehit]
+        lds_barrier();   // [B:exact]
+        th = b.truehit;   // [R:truehit]
+      }
+      const bool okj = oka && ((th >> j) & 1u) == 0u;
+      V = (uint32_t)__builtin_ctz(~(uint32_t)(__ballot(lane < kNW && okj) & 0xFFull));      // members 0 .. V-1 are certain (no pair flagged: V = Va)
 #ifdef GLIA_HMT_PROFILE
-      if (V < M) { const uint32_t cutsal = (uint32_t)(__ballot(lane < kNW && j == V && !(kj.sal > pm)) & 0xFFull); if (cutsal) bcut_sal += 1; else bcut_dep += 1; }
+      {
+        // what the bitmap alone would have committed (GLIA_HMT_BITMAP_PREFIX: it still does, the exact test only counts), and why the
+        // committed prefix ends where it does
+        const uint32_t Vb = (uint32_t)__builtin_ctz(~(uint32_t)(__ballot(lane < kNW && oka && hitm == 0u) & 0xFFull));
+        const uint32_t Vx = V;
+#ifdef GLIA_HMT_BITMAP_PREFIX
+        V = Vb;
+#endif
+        if (flagged) bflag += 1;
+        if (Vb < Vx) bcut_falsebm += 1;
+        blost += Vx - V;
+        if (V < M) {
+          const uint32_t cutsal = (uint32_t)(__ballot(lane < kNW && j == V && !(kj.sal > pm)) & 0xFFull);
+          const uint32_t cutwide = (uint32_t)(__ballot(lane < kNW && j == V && tj == 0xFFFFFFFFu) & 0xFFull);
+          if (cutsal) bcut_sal += 1; else if (cutwide) bcut_wide += 1; else if ((th >> V) & 1u) bcut_true += 1; else bcut_false += 1;
+        }
+      }
 #endif
       // offsets of this wave's member, totals of the valid prefix
       my_ne = (uint32_t)__builtin_amdgcn_readlane((int)pre_n, wave); my_pool = (uint32_t)__builtin_amdgcn_readlane((int)pre_t, wave);
@@ -568,8 +622,10 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_batch_kernel(WinState s
   if (tid == 0) printf("[batch profile] created edges at or above / below the horizon (cumulative): narrow commit %llu / %llu  wide on the LDS table %llu / %llu  wide on the global marks %llu / %llu\n",
                        atomicAdd(&g_edgeprof[0][0], 0ull), atomicAdd(&g_edgeprof[0][1], 0ull), atomicAdd(&g_edgeprof[1][0], 0ull), atomicAdd(&g_edgeprof[1][1], 0ull),
                        atomicAdd(&g_edgeprof[2][0], 0ull), atomicAdd(&g_edgeprof[2][1], 0ull));
-  if (tid == 0) printf("[batch profile] merges %llu: select %llu  compute %llu  validate %llu  commit %llu  scan %llu  loop-top %llu  reload %llu (cycles); rounds %llu candidates %llu committed %llu (cut by saliency %llu, by adjacency %llu) wide %llu\n",
-                       k, bph[0], bph[1], bph[2], bph[3], bph[4], bph[5], bph[6], brounds, bmembers, bvalid, bcut_sal, bcut_dep, bwide);
+  if (tid == 0) printf("[batch profile] merges %llu: select %llu  compute %llu  validate %llu  commit %llu  scan %llu  loop-top %llu  reload %llu (cycles); rounds %llu candidates %llu committed %llu (cut by saliency %llu, by a wide member %llu, by a true conflict %llu, by a false bitmap hit %llu) wide %llu\n",
+                       k, bph[0], bph[1], bph[2], bph[3], bph[4], bph[5], bph[6], brounds, bmembers, bvalid, bcut_sal, bcut_wide, bcut_true, bcut_false, bwide);
+  if (tid == 0) printf("[batch profile] conflicts (this launch): rounds with a flagged pair %llu  rounds the bitmap alone would cut short %llu  members lost to false cuts %llu;  scans with an overflowed kill list (cumulative) %llu\n",
+                       bflag, bcut_falsebm, blost, g_kovf);
   if (tid == 0) printf("[batch profile] reload parts (cumulative cycles, thread 0): descent over blocks that load nothing %llu  whole-cell loads %llu  cell split %llu;  empty blocks %llu  reloads %llu\n",
                        g_reloadprof[0], g_reloadprof[1], g_reloadprof[2], g_reloadprof[3], g_reloadprof[4]);
   if (tid == 0) printf("[batch profile] scan phases (cumulative cycles, wave 0): loads %llu  compare %llu  top2 %llu  top2 with a tied best %llu  barrier %llu  calls %llu  tied second %llu  tied best %llu\n",
