@@ -25,7 +25,7 @@ void set_error(const std::string& msg) { g_err = msg; }
 static const char* const kOptionKeys[] = {"GLIA_HMT_PB_WINDOW", "GLIA_HMT_PB_BATCH", "GLIA_HMT_WINCAP", "GLIA_HMT_REBASE", "GLIA_HMT_HORIZON",
                                           "GLIA_HMT_FORCE_TREE", "GLIA_HMT_HELPERS", "GLIA_HMT_TRACE", "GLIA_HMT_LIBM", "GLIA_HMT_BC_NOCOMMON",
                                           "GLIA_HMT_BC_GENERIC", "GLIA_HMT_DEBUG", "GLIA_HMT_MAXITERS", "GLIA_HMT_MINCAP", "GLIA_HMT_MEDIAN_BATCH", "GLIA_HMT_BCFEAT", "GLIA_HMT_CC",
-                                          "GLIA_HMT_TRAIN_TREES", "GLIA_HMT_BASELINE_AUDIT", "GLIA_HMT_COLLECT_LANES", "GLIA_HMT_REBASE_END", "GLIA_HMT_BATCH"};
+                                          "GLIA_HMT_TRAIN_TREES", "GLIA_HMT_BASELINE_AUDIT", "GLIA_HMT_COLLECT_LANES", "GLIA_HMT_REBASE_END", "GLIA_HMT_BATCH", "GLIA_HMT_BLUR"};
 static std::mutex g_opt_mu;
 static std::unordered_map<std::string, std::string> g_opt;
 static bool g_opt_init = false;

@@ -28,6 +28,7 @@ struct glia_hmt_ctx {
   glia_hmt_mlp_train_timing mlt = {};     // the last glia_hmt_mlp_train call
   glia_hmt_sshmt_train_timing sst = {};   // the last glia_hmt_sshmt_train call
   glia_hmt_batch_timing bat = {};         // the last glia_hmt_*_train_batches call
+  double blur_ms = 0; int blur_route = 0; // the last glia_hmt_blur_image call: device time, GLIA_HMT_BLUR_ROUTE_* that ran
   int tz = kTZ;                  // tile depth of the accumulation pass; halved when the LDS tables of a pass overflowed a lot
   LibmSel libm = {kLibmDevice, kLibmDevice, kLibmDevice, kLibmDevice};   // restatement of the host's log2 / log / pow / exp the kernels use (glibc_math.hpp)
 };

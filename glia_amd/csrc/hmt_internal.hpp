@@ -241,6 +241,13 @@ int watershed_labels(int dim, const int64_t dims[3], const float* d_img, double 
 enum { GLIA_HMT_CC_ROUTE_TILED = 0, GLIA_HMT_CC_ROUTE_GLOBAL = 1 };
 int label_components(int dim, const int64_t dims[3], const uint32_t* d_in, const uint32_t* d_mask, int mode, int route, uint32_t* d_out,
                      uint32_t* n_components, hipStream_t stream);
+// blur_image on the device (blur.hip); arguments validated by the caller (api_blur.cpp).  taps[a] = NULL: axis a is left alone;
+// route = GLIA_HMT_BLUR; *route_used: the route that ran (march falls back to passes above kBlurMarchRadius), *ms: its device time
+constexpr int kBlurTileX = 64, kBlurTileY = 16;   // the x-y tile of a marching workgroup
+constexpr int kBlurMarchRadius = 5;               // largest radius of the march route: tile + halo, the x pass and a ring of 2 r + 1 planes in 64 KiB of static LDS
+struct GaussianKernel;
+int blur_image_device(int dim, const int64_t dims[3], int pixel_type, const void* d_in, const GaussianKernel* const taps[3], int route, void* d_out,
+                      hipStream_t stream, double* ms, int* route_used);
 // the contingency table of two label streams under a mask (label_overlap.hip): entries with count > 0 ascending by (a, b); arguments
 // validated by the caller (api.cpp).  info: device time of the counting passes (all of them, a repeated pass included) and how many were repeated
 struct OverlapPass { double ms = 0; int repeats = 0; };

@@ -116,6 +116,47 @@ def overlap_scores(tables, vi_mode="reference"):
     return out.as_dict()
 
 
+PIXEL_TYPES = {"float32": 0, "uint8": 1, "uint16": 2}     # GLIA_HMT_PIXEL_*
+BLUR_ROUTES = {0: "passes", 1: "march"}                   # GLIA_HMT_BLUR_ROUTE_*
+BLUR_MAX_ERROR = 0.01                                     # GLIA_HMT_BLUR_MAX_ERROR
+
+
+def gaussian_kernel(variance, max_width, max_error=BLUR_MAX_ERROR):
+    """glia_hmt_gaussian_kernel (host-only, needs no GPU): the discrete Gaussian of one axis as blur_image truncates it ->
+    (one-sided coefficients c[0..radius] as float64, radius, covered mass before the division)."""
+    c = np.empty(129, np.float64)
+    r, cov = C.c_int(0), C.c_double(0)
+    _check(lib().glia_hmt_gaussian_kernel(C.c_double(variance), C.c_int(max_width), C.c_double(max_error), _np(c), C.c_int(len(c)),
+                                          C.byref(r), C.byref(cov)))
+    return c[:r.value + 1].copy(), r.value, cov.value
+
+
+def blur_limits():
+    """glia_hmt_blur_limits -> dict: tile_x, tile_y (the march route's tile), max_march_radius, max_radius"""
+    v = [C.c_int(0) for _ in range(4)]
+    _check(lib().glia_hmt_blur_limits(*[C.byref(x) for x in v]))
+    return dict(zip(("tile_x", "tile_y", "max_march_radius", "max_radius"), (x.value for x in v)))
+
+
+def _blur_variances(sigma, dim):
+    """sigma: a scalar, or one value per axis in the reference's order (x, y[, z]) -- the reverse of the array's shape"""
+    s = [float(sigma)] * dim if np.isscalar(sigma) else [float(v) for v in sigma]
+    if len(s) != dim:
+        raise ValueError("sigma: a scalar or one value per axis")
+    return (C.c_double * 3)(*([v * v for v in s] + [1.0] * (3 - dim)))
+
+
+def blur_image_host(image, sigma, kernel_width, dim=-1):
+    """glia_hmt_blur_image_host (needs no GPU): the definition of blur_image on a float32 / uint8 / uint16 ndarray in numpy axis
+    order (z, y, x) -> ndarray of the same type.  sigma and dim as Context.blur_image."""
+    a = np.ascontiguousarray(image)
+    ndim, d = _dims(a.shape)
+    out = np.empty_like(a)
+    _check(lib().glia_hmt_blur_image_host(C.c_int(ndim), d, C.c_int(PIXEL_TYPES[a.dtype.name]), _np(a), _blur_variances(sigma, ndim),
+                                          C.c_int(kernel_width), C.c_int(dim if dim >= 0 else -1), _np(out)))
+    return out
+
+
 def set_option(key, value):
     """glia_hmt_set_option: a process-wide tuning / test switch of the loops (value None unsets it)."""
     _check(lib().glia_hmt_set_option(key.encode(), None if value is None else str(value).encode()))
@@ -270,6 +311,29 @@ class Context:
                                                C.c_void_p(mask.data_ptr()) if mask is not None else None, C.c_int(self.CC_MODES[mode]),
                                                C.c_void_p(out.data_ptr()), C.byref(n)))
         return out, n.value
+
+    def blur_image(self, image, sigma, kernel_width, dim=-1):
+        """blurImage (util/image.hxx:376-407, gadget/main_blur_image.cxx) of a CUDA tensor of float32, uint8 or uint16 (an int16
+        tensor is taken as uint16 payload) in numpy axis order (z, y, x) -> a new tensor of the same type; the input is left
+        unchanged.  sigma: a scalar, or one value per axis in the reference's order (x, y[, z]) -- the reverse of the tensor's
+        shape --, in voxels; kernel_width: MaximumKernelWidth.  dim >= 0: the slice-wise mode, axis `dim` (reference order, 0 = x =
+        the last tensor axis) is left alone.  The result equals blur_image_host bit for bit on either route (GLIA_HMT_BLUR)."""
+        import torch
+        names = {torch.float32: "float32", torch.uint8: "uint8", torch.uint16: "uint16", torch.int16: "uint16"}
+        assert image.is_cuda and image.is_contiguous() and image.dtype in names and image.dim() in (2, 3)
+        ndim, d = _dims(tuple(image.shape))
+        out = torch.empty_like(image)
+        _fence(image)
+        _check(lib().glia_hmt_blur_image(self.h, C.c_int(ndim), d, C.c_int(PIXEL_TYPES[names[image.dtype]]), C.c_void_p(image.data_ptr()),
+                                         _blur_variances(sigma, ndim), C.c_int(kernel_width), C.c_int(dim if dim >= 0 else -1),
+                                         C.c_void_p(out.data_ptr())))
+        return out
+
+    def last_blur_timing(self):
+        """glia_hmt_last_blur_timing -> (device ms of the last blur_image call's kernels, the route that ran: "passes" | "march")"""
+        ms, route = C.c_double(0), C.c_int(0)
+        _check(lib().glia_hmt_last_blur_timing(self.h, C.byref(ms), C.byref(route)))
+        return ms.value, BLUR_ROUTES[route.value]
 
     def label_overlap(self, a, b, mask=None, drop_zero_a=False, drop_zero_b=False):
         """glia_hmt_label_overlap: the contingency table of two CUDA label tensors (uint32 payload, same number of voxels, any

@@ -910,6 +910,59 @@ typedef struct {
 } glia_hmt_eval_timing;
 int glia_hmt_last_eval_timing(const glia_hmt_ctx* ctx, glia_hmt_eval_timing* out);
 
+/* ---- smoothing the probability map before the watershed (gadget/main_blur_image.cxx, blurImage util/image.hxx:376-407) ----------
+ * blurImage is itk::DiscreteGaussianImageFilter(variance = sigma^2, MaximumKernelWidth = w); with a dimension argument
+ * (util/image.hxx:389-407) the filter of one dimension less runs slice by slice.  ITK is absent from this image, so -- as for the
+ * watershed -- the operator is defined here and every route reproduces that definition bit for bit; parity with
+ * ITK's last digits is NOT claimed (its Bessel values are polynomial fits good to about 1e-7, the ones here are exact to rounding;
+ * the cut-off rule is itk::GaussianOperator's as understood, unpinned).
+ *
+ * glia_hmt_gaussian_kernel (host-only, no ctx, no HIP call) replaces itk::GaussianOperator::GenerateCoefficients for one axis:
+ * T(n) = exp(-variance) I_n(variance) by the power series of I_n in double; c = [T(0), T(1)], then T(i) is appended while the covered
+ * mass c0 + 2 (c1 + ...) stays below 1 - max_error, stopping after an append that is <= 0 or that makes the one-sided length exceed
+ * max_width; every entry is divided by the covered mass.  coeffs[0..*radius] (one-sided; 1 <= *radius <= max_width), *covered = the
+ * mass before the division (optional).  A kernel cut by max_width is not an error.  GLIA_HMT_ERR_ARG, message "gaussian_kernel: ...":
+ * NULL coeffs or radius, variance not in (0, GLIA_HMT_BLUR_MAX_VARIANCE], max_width not in 1..GLIA_HMT_BLUR_MAX_WIDTH, max_error not in
+ * (0, 1); GLIA_HMT_ERR_CAPACITY (with *radius set): capacity < *radius + 1. */
+#define GLIA_HMT_BLUR_MAX_VARIANCE 256.0
+#define GLIA_HMT_BLUR_MAX_WIDTH 128
+#define GLIA_HMT_BLUR_MAX_ERROR 0.01 /* ITK's default MaximumError: what blur_image and the two calls below use */
+int glia_hmt_gaussian_kernel(double variance, int max_width, double max_error, double* coeffs, int capacity, int* radius, double* covered);
+
+/* The operator.  Axes go x, then y, then z; the axis skip_axis (-1: none) is left alone -- blurImage(image, sigma, kernelWidth, dim),
+ * the slice-wise mode.  One axis pass maps a float32 volume to a float32 volume:
+ *   out[p] = f32( sum_{o = -r..+r} c[|o|] * (double) in[clamp(p + o e_axis)] ),
+ * summed in double with o ascending from an accumulator of +0.0, every product and sum rounded on its own (no fused multiply-add),
+ * coordinates clamped into [0, extent - 1] (ITK's zero-flux Neumann boundary), rounded to float32 once per pass; NaN and infinities
+ * follow IEEE.  variance[a] (voxel units; spacing is the caller's business) is read for the blurred axes only; the kernel of an axis
+ * is glia_hmt_gaussian_kernel(variance[a], max_width, GLIA_HMT_BLUR_MAX_ERROR).  Pixel types: GLIA_HMT_PIXEL_UINT8 / _UINT16 are converted to
+ * float32 (exact), go through the same passes, and after the last one are clamped to the type's range and truncated toward zero
+ * (ITK casts).  With no axis blurred the output equals the input.  dims as for glia_hmt_watershed; 1 to 2^32 - 2 voxels.
+ *
+ * glia_hmt_blur_image_host is the definition as plain C++ on host memory: no ctx, no GPU.  glia_hmt_blur_image works on device memory;
+ * d_out must not be d_in.  Option GLIA_HMT_BLUR = passes | march: two routes to the same bytes --
+ *   passes  one launch per blurred axis through float32 scratch volumes from the context's block cache (one volume per pass but the
+ *           last); any radius;
+ *   march   a workgroup owns a tile of tile_x x tile_y voxels plus its halo and walks along z: per input plane the x pass and the y
+ *           pass run in LDS, the x-y blurred planes are kept in a ring of 2 r + 1 planes in LDS, the z-blurred plane is written; every
+ *           voxel is read once apart from the halo and written once, no scratch.  Radii up to max_march_radius (64 KiB of static LDS);
+ *           a larger radius on any blurred axis takes `passes`, and glia_hmt_last_blur_timing says so.
+ * GLIA_HMT_ERR_ARG, message "blur_image: ...", before any HIP call for: a NULL ctx (device call), dims, variance, input or output; dim
+ * other than 2 or 3; a non-positive extent or a size outside the range; an unknown pixel type; skip_axis outside -1..dim - 1; a
+ * variance of a blurred axis that is not finite, <= 0 or above GLIA_HMT_BLUR_MAX_VARIANCE; max_width outside 1..GLIA_HMT_BLUR_MAX_WIDTH;
+ * d_out == d_in; an unknown value of GLIA_HMT_BLUR (device call). */
+enum { GLIA_HMT_PIXEL_FLOAT32 = 0, GLIA_HMT_PIXEL_UINT8 = 1, GLIA_HMT_PIXEL_UINT16 = 2 };
+enum { GLIA_HMT_BLUR_ROUTE_PASSES = 0, GLIA_HMT_BLUR_ROUTE_MARCH = 1 };
+int glia_hmt_blur_image_host(int dim, const int64_t dims[3], int pixel_type, const void* h_in, const double variance[3], int max_width,
+                             int skip_axis, void* h_out);
+int glia_hmt_blur_image(glia_hmt_ctx* ctx, int dim, const int64_t dims[3], int pixel_type, const void* d_in, const double variance[3],
+                        int max_width, int skip_axis, void* d_out);
+/* what the kernels really use (host-only; any pointer may be NULL): the march tile, the largest radius the march route takes, the
+ * largest radius at all (= GLIA_HMT_BLUR_MAX_WIDTH) */
+int glia_hmt_blur_limits(int* tile_x, int* tile_y, int* max_march_radius, int* max_radius);
+/* the last glia_hmt_blur_image call on this context: device time of its kernels and the route that ran (GLIA_HMT_BLUR_ROUTE_*) */
+int glia_hmt_last_blur_timing(const glia_hmt_ctx* ctx, double* ms, int* route_used);
+
 /* ---- synthetic inputs for tests / bench, generated on the device -------------- */
 int glia_hmt_synth(glia_hmt_ctx* ctx, int dim, const int64_t dims[3], int S, int G, uint64_t seed,
                    int variant, uint32_t* d_labels, float* d_pb);
