@@ -3,11 +3,16 @@
 Names follow the reference: RegionMap ~ TRegionMap(image, mask, onlyContour) (type/region_map.hxx:38-40),
 merge_order_pb ~ hmt/main_merge_order_pb.cxx.  Volumes are torch CUDA tensors (device memory plumbing
 only) in numpy axis order (z, y, x).  No CPU path exists here.
+
+The prototypes live in one table (glia_amd/_abi.py) that lib() installs; the Structure classes and dtypes below re-state structs of
+the header.  tests/test_binding_host.py holds both to the header.
 """
 import ctypes as C
 import os
 
 import numpy as np
+
+from . import _abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("GLIA_HMT_LIB", os.path.join(_HERE, "libglia_hmt.so"))   # override: kernel experiments only
@@ -18,10 +23,7 @@ PREDICT_STAGE_MAX_DIM = 767      # GLIA_HMT_PREDICT_STAGE_MAX_DIM: longer rows a
 
 def predict_tile_rows(n_rows, dim):
     """glia_hmt_forest_predict_tile_rows: rows of the LDS tile RandomForest.predict uses for this input (64, 32, 16, 8), 0 = not staged"""
-    r = lib().glia_hmt_forest_predict_tile_rows(C.c_int64(n_rows), C.c_int(dim))
-    if r < 0:
-        raise HmtError(r, lib().glia_hmt_last_error().decode())
-    return r
+    return _count(lib().glia_hmt_forest_predict_tile_rows(n_rows, dim))
 
 
 class HmtError(RuntimeError):
@@ -63,10 +65,10 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(_SO)
-        L.glia_hmt_last_error.restype = C.c_char_p
-        L.glia_hmt_version.restype = C.c_char_p
-        L.glia_hmt_rag_num_regions.restype = C.c_int64
-        L.glia_hmt_rag_num_pairs.restype = C.c_int64
+        for name, (result, params) in _abi.PROTOTYPES.items():     # the only place that gives a function its prototype
+            f = getattr(L, name)
+            f.restype = result
+            f.argtypes = params
         _lib = L
     return _lib
 
@@ -74,6 +76,60 @@ def lib():
 def _check(rc):
     if rc != 0:
         raise HmtError(rc, lib().glia_hmt_last_error().decode())
+
+
+def _count(n):
+    """the result of a call that returns a count, or a negative status"""
+    if n < 0:
+        raise HmtError(int(n), lib().glia_hmt_last_error().decode())
+    return n
+
+
+def _outs(fn, types, *args):
+    """fn(*args, one out-parameter per type by reference), checked -> the values it wrote"""
+    v = [t() for t in types]
+    _check(fn(*args, *[C.byref(x) for x in v]))
+    return [x.value for x in v]
+
+
+def _struct_out(fn, cls, handle):
+    """fn(handle, &struct), checked -> dict of the struct's fields, a nested struct as a dict: the last_*_timing getters"""
+    def fields(s):
+        return {k: fields(v) if isinstance(v, C.Structure) else v for k, v in ((k, getattr(s, k)) for k, *_ in s._fields_)}
+    s = cls()
+    _check(fn(handle, C.byref(s)))
+    return fields(s)
+
+
+def _new(fn, *args):
+    """the handle that fn(*args, &handle) creates, checked"""
+    h = C.c_void_p()
+    _check(fn(*args, C.byref(h)))
+    return h
+
+
+class _Handle:
+    """Owner of one native handle: h, freed once by the library function the class names; close() may be called again."""
+    _free = None
+
+    @classmethod
+    def _wrap(cls, h, **attrs):
+        """an instance around an existing handle, the constructor not run"""
+        self = cls.__new__(cls)
+        self.h = h
+        vars(self).update(attrs)
+        return self
+
+    def close(self):
+        if self.h:
+            getattr(lib(), self._free)(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 ERR_ARG, ERR_CAPACITY, ERR_INTERNAL = -1, -4, -7
@@ -112,7 +168,7 @@ def overlap_scores(tables, vi_mode="reference"):
     ptrs = (C.c_void_p * max(n, 1))(*[t.ctypes.data if len(t) else None for t in keep])
     lens = (C.c_int64 * max(n, 1))(*[len(t) for t in keep])
     out = EvalResult()
-    _check(lib().glia_hmt_overlap_scores(ptrs, lens, C.c_int(n), C.c_int(VI_MODES[vi_mode]), C.byref(out)))
+    _check(lib().glia_hmt_overlap_scores(ptrs, lens, n, VI_MODES[vi_mode], C.byref(out)))
     return out.as_dict()
 
 
@@ -125,17 +181,13 @@ def gaussian_kernel(variance, max_width, max_error=BLUR_MAX_ERROR):
     """glia_hmt_gaussian_kernel (host-only, needs no GPU): the discrete Gaussian of one axis as blur_image truncates it ->
     (one-sided coefficients c[0..radius] as float64, radius, covered mass before the division)."""
     c = np.empty(129, np.float64)
-    r, cov = C.c_int(0), C.c_double(0)
-    _check(lib().glia_hmt_gaussian_kernel(C.c_double(variance), C.c_int(max_width), C.c_double(max_error), _np(c), C.c_int(len(c)),
-                                          C.byref(r), C.byref(cov)))
-    return c[:r.value + 1].copy(), r.value, cov.value
+    r, cov = _outs(lib().glia_hmt_gaussian_kernel, (C.c_int, C.c_double), variance, max_width, max_error, _np(c), len(c))
+    return c[:r + 1].copy(), r, cov
 
 
 def blur_limits():
     """glia_hmt_blur_limits -> dict: tile_x, tile_y (the march route's tile), max_march_radius, max_radius"""
-    v = [C.c_int(0) for _ in range(4)]
-    _check(lib().glia_hmt_blur_limits(*[C.byref(x) for x in v]))
-    return dict(zip(("tile_x", "tile_y", "max_march_radius", "max_radius"), (x.value for x in v)))
+    return dict(zip(("tile_x", "tile_y", "max_march_radius", "max_radius"), _outs(lib().glia_hmt_blur_limits, (C.c_int,) * 4)))
 
 
 def _blur_variances(sigma, dim):
@@ -152,8 +204,8 @@ def blur_image_host(image, sigma, kernel_width, dim=-1):
     a = np.ascontiguousarray(image)
     ndim, d = _dims(a.shape)
     out = np.empty_like(a)
-    _check(lib().glia_hmt_blur_image_host(C.c_int(ndim), d, C.c_int(PIXEL_TYPES[a.dtype.name]), _np(a), _blur_variances(sigma, ndim),
-                                          C.c_int(kernel_width), C.c_int(dim if dim >= 0 else -1), _np(out)))
+    _check(lib().glia_hmt_blur_image_host(ndim, d, PIXEL_TYPES[a.dtype.name], _np(a), _blur_variances(sigma, ndim), kernel_width,
+                                          dim if dim >= 0 else -1, _np(out)))
     return out
 
 
@@ -185,7 +237,7 @@ def check_merge_order(dense_order, n_regions):
     creates region n_regions + k, else the first merge that does not."""
     o = np.ascontiguousarray(dense_order, dtype=np.uint32).reshape(-1, 3)
     bad = C.c_int64(-1)
-    rc = lib().glia_hmt_check_merge_order(o.ctypes.data_as(C.c_void_p), C.c_int64(len(o)), C.c_int64(int(n_regions)), C.byref(bad))
+    rc = lib().glia_hmt_check_merge_order(_np(o), len(o), int(n_regions), C.byref(bad))
     if rc not in (0, ERR_ARG):
         _check(rc)
     return int(bad.value)
@@ -203,6 +255,11 @@ def _np(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _ptr(t):
+    """device pointer of a tensor that may be absent"""
+    return None if t is None else t.data_ptr()
+
+
 def _fence(t):
     """The library works on its own HIP stream: finish whatever torch has queued on the tensor's device first
     (a clone() or copy_ producing the input), so the kernels below see the data."""
@@ -210,50 +267,34 @@ def _fence(t):
     torch.cuda.current_stream(t.device).synchronize()
 
 
-class Context:
+class Context(_Handle):
+    _free = "glia_hmt_ctx_destroy"
+
     def __init__(self, device=0, stream=None):
-        self.h = C.c_void_p()
-        _check(lib().glia_hmt_ctx_create(C.c_int(device), C.c_void_p(stream) if stream else None, C.byref(self.h)))
+        self.h = _new(lib().glia_hmt_ctx_create, device, stream if stream else None)
         self.device = device
         self._overlap_room = 0           # entries of the last label_overlap table: the size of the next call's host buffer
         if lib().glia_hmt_ctx_libm_status(self.h) == 0:
             import warnings
             warnings.warn(lib().glia_hmt_last_error().decode())
 
-    def close(self):
-        if self.h:
-            lib().glia_hmt_ctx_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def sync(self):
         _check(lib().glia_hmt_ctx_sync(self.h))
 
     def libm(self):
         """(log2 variant, log variant) the kernels use: 1 = glibc non-FMA, 2 = glibc FMA, 0 = device libm (unpinned)."""
-        a, b = C.c_int(0), C.c_int(0)
-        _check(lib().glia_hmt_ctx_libm(self.h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return tuple(_outs(lib().glia_hmt_ctx_libm, (C.c_int, C.c_int), self.h))
 
     @staticmethod
     def release_cached_memory():
         """Scratch blocks the library parks for reuse go back to the driver (glia_hmt_release_cached_memory); returns the bytes released."""
-        f = lib().glia_hmt_release_cached_memory
-        f.restype = C.c_ulonglong
-        return int(f())
+        return int(lib().glia_hmt_release_cached_memory())
 
     @staticmethod
     def internal_errors():
         """Calls of this process that ended with GLIA_HMT_ERR_INTERNAL -- a merge loop's own consistency stop or an order that
         failed the replay of glia_hmt_check_merge_order (glia_hmt_internal_errors).  0 is the only healthy answer."""
-        f = lib().glia_hmt_internal_errors
-        f.restype = C.c_ulonglong
-        return int(f())
+        return int(lib().glia_hmt_internal_errors())
 
     def libm_pinned(self):
         """True when log2, log and pow of the host libm are all reproduced bit for bit (glia_hmt_ctx_libm_status)."""
@@ -261,23 +302,18 @@ class Context:
 
     def libm_pow(self):
         """variant of std::pow(perim, 1.5) the kernels use (same codes as libm())"""
-        a = C.c_int(0)
-        _check(lib().glia_hmt_ctx_libm_pow(self.h, C.byref(a)))
-        return a.value
+        return _outs(lib().glia_hmt_ctx_libm_pow, (C.c_int,), self.h)[0]
 
     def libm_exp(self):
         """variant of std::exp the classifier loop's MLP sigmoid uses (same codes as libm()); not part of libm_pinned()"""
-        a = C.c_int(0)
-        _check(lib().glia_hmt_ctx_libm_exp(self.h, C.byref(a)))
-        return a.value
+        return _outs(lib().glia_hmt_ctx_libm_exp, (C.c_int,), self.h)[0]
 
     def libm_eval(self, function, variant, x):
         """Device restatement of the host libm over a CUDA f64 tensor: function 0 = log2, 1 = log, 2 = pow(x, 1.5), 3 = exp,
         4 = the sigmoid 1 / (1 + exp(-x))."""
         import torch
         out = torch.empty_like(x)
-        _check(lib().glia_hmt_libm_eval(self.h, C.c_int(function), C.c_int(variant), C.c_void_p(x.data_ptr()),
-                                        C.c_void_p(out.data_ptr()), C.c_int64(x.numel())))
+        _check(lib().glia_hmt_libm_eval(self.h, function, variant, x.data_ptr(), out.data_ptr(), x.numel()))
         self.sync()
         return out
 
@@ -287,11 +323,9 @@ class Context:
         assert image.is_cuda and image.dtype == torch.float32 and image.is_contiguous()
         dim, d = _dims(tuple(image.shape))
         out = torch.empty(image.shape, dtype=torch.int32, device=image.device)
-        n, sw = C.c_uint32(0), C.c_int(0)
         _fence(image)
-        _check(lib().glia_hmt_watershed(self.h, C.c_int(dim), d, C.c_void_p(image.data_ptr()), C.c_double(level), C.c_void_p(out.data_ptr()),
-                                        C.byref(n), C.byref(sw)))
-        return out, n.value, sw.value
+        n, sw = _outs(lib().glia_hmt_watershed, (C.c_uint32, C.c_int), self.h, dim, d, image.data_ptr(), level, out.data_ptr())
+        return out, n, sw
 
     CC_MODES = {"identity": 0, "binary": 1, "binary_inverted": 2}
 
@@ -305,12 +339,10 @@ class Context:
         assert mask is None or (mask.is_cuda and mask.is_contiguous() and mask.element_size() == 4 and mask.shape == labels.shape)
         dim, d = _dims(tuple(labels.shape))
         out = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
-        n = C.c_uint32(0)
         _fence(labels)
-        _check(lib().glia_hmt_label_components(self.h, C.c_int(dim), d, C.c_void_p(labels.data_ptr()),
-                                               C.c_void_p(mask.data_ptr()) if mask is not None else None, C.c_int(self.CC_MODES[mode]),
-                                               C.c_void_p(out.data_ptr()), C.byref(n)))
-        return out, n.value
+        n, = _outs(lib().glia_hmt_label_components, (C.c_uint32,), self.h, dim, d, labels.data_ptr(), _ptr(mask), self.CC_MODES[mode],
+                   out.data_ptr())
+        return out, n
 
     def blur_image(self, image, sigma, kernel_width, dim=-1):
         """blurImage (util/image.hxx:376-407, gadget/main_blur_image.cxx) of a CUDA tensor of float32, uint8 or uint16 (an int16
@@ -324,16 +356,14 @@ class Context:
         ndim, d = _dims(tuple(image.shape))
         out = torch.empty_like(image)
         _fence(image)
-        _check(lib().glia_hmt_blur_image(self.h, C.c_int(ndim), d, C.c_int(PIXEL_TYPES[names[image.dtype]]), C.c_void_p(image.data_ptr()),
-                                         _blur_variances(sigma, ndim), C.c_int(kernel_width), C.c_int(dim if dim >= 0 else -1),
-                                         C.c_void_p(out.data_ptr())))
+        _check(lib().glia_hmt_blur_image(self.h, ndim, d, PIXEL_TYPES[names[image.dtype]], image.data_ptr(), _blur_variances(sigma, ndim),
+                                         kernel_width, dim if dim >= 0 else -1, out.data_ptr()))
         return out
 
     def last_blur_timing(self):
         """glia_hmt_last_blur_timing -> (device ms of the last blur_image call's kernels, the route that ran: "passes" | "march")"""
-        ms, route = C.c_double(0), C.c_int(0)
-        _check(lib().glia_hmt_last_blur_timing(self.h, C.byref(ms), C.byref(route)))
-        return ms.value, BLUR_ROUTES[route.value]
+        ms, route = _outs(lib().glia_hmt_last_blur_timing, (C.c_double, C.c_int), self.h)
+        return ms, BLUR_ROUTES[route]
 
     def label_overlap(self, a, b, mask=None, drop_zero_a=False, drop_zero_b=False):
         """glia_hmt_label_overlap: the contingency table of two CUDA label tensors (uint32 payload, same number of voxels, any
@@ -347,9 +377,7 @@ class Context:
         out = np.empty(max(self._overlap_room, 1 << 12), OVERLAP_ENTRY)
         n = C.c_int64(0)
         while True:
-            rc = lib().glia_hmt_label_overlap(self.h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
-                                              C.c_void_p(mask.data_ptr()) if mask is not None else None, C.c_int64(a.numel()), C.c_int(flags),
-                                              _np(out), C.c_int64(len(out)), C.byref(n))
+            rc = lib().glia_hmt_label_overlap(self.h, a.data_ptr(), b.data_ptr(), _ptr(mask), a.numel(), flags, _np(out), len(out), C.byref(n))
             if rc != ERR_CAPACITY or n.value <= len(out):
                 break
             out = np.empty(n.value, OVERLAP_ENTRY)          # the table is larger than the guess: once more with room for it
@@ -372,21 +400,19 @@ class Context:
                 assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == p.numel()
                 _fence(t)
         n = len(res)
-        ptrs = lambda ts: (C.c_void_p * n)(*[None if t is None else t.data_ptr() for t in ts])
+        ptrs = lambda ts: (C.c_void_p * n)(*[_ptr(t) for t in ts])
         nv = (C.c_int64 * n)(*[p.numel() for p in res])
         out = EvalResult()
-        _check(lib().glia_hmt_eval(self.h, C.c_int(n), ptrs(res), ptrs(ref), ptrs(masks) if masks is not None else None, nv,
-                                   C.c_int(VI_MODES[vi_mode]), C.byref(out)))
+        _check(lib().glia_hmt_eval(self.h, n, ptrs(res), ptrs(ref), ptrs(masks) if masks is not None else None, nv, VI_MODES[vi_mode],
+                                   C.byref(out)))
         return out.as_dict()
 
     def last_eval_timing(self):
         """the counting passes of the last label_overlap / evaluate call: ms_count (device), entries, repeats"""
-        t = EvalTiming()
-        _check(lib().glia_hmt_last_eval_timing(self.h, C.byref(t)))
-        return {k: getattr(t, k) for k, _ in EvalTiming._fields_}
+        return _struct_out(lib().glia_hmt_last_eval_timing, EvalTiming, self.h)
 
     def set_table_hint(self, regions, pairs):
-        _check(lib().glia_hmt_ctx_set_table_hint(self.h, C.c_int64(regions), C.c_int64(pairs)))
+        _check(lib().glia_hmt_ctx_set_table_hint(self.h, regions, pairs))
 
     def synth(self, shape, S, G, seed=0x9E3779B97F4A7C15, variant=0):
         """Synthetic supervoxels + pb on the device; returns torch tensors (labels i32 view, pb)."""
@@ -395,8 +421,7 @@ class Context:
         dev = torch.device("cuda", self.device)
         labels = torch.empty(shape, dtype=torch.int32, device=dev)   # uint32 payload
         pb = torch.empty(shape, dtype=torch.float32, device=dev)
-        _check(lib().glia_hmt_synth(self.h, C.c_int(dim), d, C.c_int(S), C.c_int(G), C.c_uint64(seed),
-                                    C.c_int(variant), C.c_void_p(labels.data_ptr()), C.c_void_p(pb.data_ptr())))
+        _check(lib().glia_hmt_synth(self.h, dim, d, S, G, seed, variant, labels.data_ptr(), pb.data_ptr()))
         return labels, pb
 
 
@@ -436,10 +461,7 @@ def gen_tree(order):
     cap = 3 * len(order) + 1      # a forest of several components has more than 2n+1 nodes
     lab = np.empty(cap, np.uint32)
     par = np.empty(cap, np.int32); c0 = np.empty(cap, np.int32); c1 = np.empty(cap, np.int32)
-    lib().glia_hmt_gen_tree.restype = C.c_int64
-    n = lib().glia_hmt_gen_tree(_np(order), C.c_int64(len(order)), _np(lab), _np(par), _np(c0), _np(c1), C.c_int64(cap))
-    if n < 0:
-        raise HmtError(int(n), lib().glia_hmt_last_error().decode())
+    n = _count(lib().glia_hmt_gen_tree(_np(order), len(order), _np(lab), _np(par), _np(c0), _np(c1), cap))
     return lab[:n], par[:n], c0[:n], c1[:n]
 
 
@@ -448,10 +470,7 @@ def transform_keys(order):
     order = np.ascontiguousarray(order, dtype=np.uint32)
     cap = 2 * len(order) + 1
     src = np.empty(cap, np.uint32); dst = np.empty(cap, np.uint32)
-    lib().glia_hmt_transform_keys.restype = C.c_int64
-    n = lib().glia_hmt_transform_keys(_np(order), C.c_int64(len(order)), _np(src), _np(dst), C.c_int64(cap))
-    if n < 0:
-        raise HmtError(int(n), lib().glia_hmt_last_error().decode())
+    n = _count(lib().glia_hmt_transform_keys(_np(order), len(order), _np(src), _np(dst), cap))
     return src[:n].copy(), dst[:n].copy()
 
 
@@ -460,10 +479,8 @@ def transform_image(ctx, labels, src, dst, mask=None, fill_missing=False):
     src = np.ascontiguousarray(src, dtype=np.uint32); dst = np.ascontiguousarray(dst, dtype=np.uint32)
     assert labels.is_cuda and labels.is_contiguous() and labels.element_size() == 4
     _fence(labels)
-    _check(lib().glia_hmt_transform_image(ctx.h, C.c_void_p(labels.data_ptr()), C.c_int64(labels.numel()), _np(src), _np(dst),
-                                          C.c_int64(len(src)), C.c_void_p(mask.data_ptr()) if mask is not None else None,
-                                          C.c_int(1 if fill_missing else 0)))
-    lib().glia_hmt_last_transform_ms.restype = C.c_double
+    _check(lib().glia_hmt_transform_image(ctx.h, labels.data_ptr(), labels.numel(), _np(src), _np(dst), len(src), _ptr(mask),
+                                          1 if fill_missing else 0))
     return lib().glia_hmt_last_transform_ms(ctx.h)
 
 
@@ -471,61 +488,41 @@ def relabel_image(ctx, labels, min_size=0):
     """relabelImage (util/image.hxx:992-1001): consecutive labels by decreasing size, in place; returns #labels."""
     assert labels.is_cuda and labels.is_contiguous() and labels.element_size() == 4
     _fence(labels)
-    n = C.c_uint32(0)
-    _check(lib().glia_hmt_relabel_image(ctx.h, C.c_void_p(labels.data_ptr()), C.c_int64(labels.numel()), C.c_int64(min_size),
-                                        C.byref(n)))
-    return n.value
+    return _outs(lib().glia_hmt_relabel_image, (C.c_uint32,), ctx.h, labels.data_ptr(), labels.numel(), min_size)[0]
 
 
-def _tree_potentials(L, prefix, order, merge_probs, region_probs, ptr):
+def tree_potentials(order, merge_probs=None, region_probs=None):
+    """genTree / genTreeWithNodePotentials (hmt/tree_build.hxx:12-63) -> (label, parent, child0, child1, potential)."""
     order = np.ascontiguousarray(order, dtype=np.uint32)
     cap = 3 * len(order) + 1
     lab = np.empty(cap, np.uint32); par = np.empty(cap, np.int32); c0 = np.empty(cap, np.int32); c1 = np.empty(cap, np.int32)
     pot = np.empty(cap, np.float64)
     mp = None if merge_probs is None else np.ascontiguousarray(merge_probs, dtype=np.float64)
     rp = None if region_probs is None else np.ascontiguousarray(region_probs, dtype=np.float64)
-    f = getattr(L, prefix + "tree_potentials"); f.restype = C.c_int64
-    n = f(ptr(order), C.c_int64(len(order)), ptr(mp) if mp is not None else None, ptr(rp) if rp is not None else None,
-          ptr(lab), ptr(par), ptr(c0), ptr(c1), ptr(pot), C.c_int64(cap))
+    n = lib().glia_hmt_tree_potentials(_np(order), len(order), _np(mp), _np(rp), _np(lab), _np(par), _np(c0), _np(c1), _np(pot), cap)
     assert n >= 0
     return lab[:n].copy(), par[:n].copy(), c0[:n].copy(), c1[:n].copy(), pot[:n].copy()
 
 
-def _resolve(L, prefix, par, c0, c1, pot, ptr):
-    par = np.ascontiguousarray(par, np.int32); c0 = np.ascontiguousarray(c0, np.int32); c1 = np.ascontiguousarray(c1, np.int32)
-    pot = np.ascontiguousarray(pot, np.float64)
+def resolve_tree_greedy(parent, child0, child1, potential):
+    """resolveTreeGreedy (hmt/tree_greedy.hxx:104-152, one tree): node indices in pick order."""
+    par = np.ascontiguousarray(parent, np.int32); c0 = np.ascontiguousarray(child0, np.int32); c1 = np.ascontiguousarray(child1, np.int32)
+    pot = np.ascontiguousarray(potential, np.float64)
     picks = np.empty(max(len(par), 1), np.int32)
-    f = getattr(L, prefix + "resolve_tree_greedy"); f.restype = C.c_int64
-    n = f(ptr(par), ptr(c0), ptr(c1), ptr(pot), C.c_int64(len(par)), ptr(picks), C.c_int64(len(picks)))
+    n = lib().glia_hmt_resolve_tree_greedy(_np(par), _np(c0), _np(c1), _np(pot), len(par), _np(picks), len(picks))
     assert n >= 0
     return picks[:n].copy()
 
 
-def _label_transform(L, prefix, lab, c0, c1, picks, key, ptr):
-    lab = np.ascontiguousarray(lab, np.uint32); c0 = np.ascontiguousarray(c0, np.int32); c1 = np.ascontiguousarray(c1, np.int32)
+def label_transform(node_label, child0, child1, picks, key_to_assign=1):
+    """genLabelTransform (hmt/tree_segment.hxx:10-21) -> (src, dst) sorted by src."""
+    lab = np.ascontiguousarray(node_label, np.uint32); c0 = np.ascontiguousarray(child0, np.int32); c1 = np.ascontiguousarray(child1, np.int32)
     picks = np.ascontiguousarray(picks, np.int32)
     src = np.empty(max(len(lab), 1), np.uint32); dst = np.empty(max(len(lab), 1), np.uint32)
-    f = getattr(L, prefix + "label_transform"); f.restype = C.c_int64
-    n = f(ptr(lab), ptr(c0), ptr(c1), C.c_int64(len(lab)), ptr(picks), C.c_int64(len(picks)), C.c_uint32(key), ptr(src), ptr(dst),
-          C.c_int64(len(src)))
+    n = lib().glia_hmt_label_transform(_np(lab), _np(c0), _np(c1), len(lab), _np(picks), len(picks), key_to_assign, _np(src), _np(dst), len(src))
     assert n >= 0
     o = np.argsort(src[:n], kind="stable")
     return src[:n][o].copy(), dst[:n][o].copy()
-
-
-def tree_potentials(order, merge_probs=None, region_probs=None):
-    """genTree / genTreeWithNodePotentials (hmt/tree_build.hxx:12-63) -> (label, parent, child0, child1, potential)."""
-    return _tree_potentials(lib(), "glia_hmt_", order, merge_probs, region_probs, _np)
-
-
-def resolve_tree_greedy(parent, child0, child1, potential):
-    """resolveTreeGreedy (hmt/tree_greedy.hxx:104-152, one tree): node indices in pick order."""
-    return _resolve(lib(), "glia_hmt_", parent, child0, child1, potential, _np)
-
-
-def label_transform(node_label, child0, child1, picks, key_to_assign=1):
-    """genLabelTransform (hmt/tree_segment.hxx:10-21) -> (src, dst) sorted by src."""
-    return _label_transform(lib(), "glia_hmt_", node_label, child0, child1, picks, key_to_assign, _np)
 
 
 def tree_energies(order, merge_probs):
@@ -537,10 +534,8 @@ def tree_energies(order, merge_probs):
     cap = 3 * len(order) + 1
     lab = np.empty(cap, np.uint32); par = np.empty(cap, np.int32); c0 = np.empty(cap, np.int32); c1 = np.empty(cap, np.int32)
     e = [np.empty(cap, np.float64) for _ in range(4)]
-    f = lib().glia_hmt_tree_energies; f.restype = C.c_int64
-    n = f(_np(order), C.c_int64(len(order)), _np(mp), _np(lab), _np(par), _np(c0), _np(c1), _np(e[0]), _np(e[1]), _np(e[2]), _np(e[3]), C.c_int64(cap))
-    if n < 0:
-        raise HmtError(int(n), lib().glia_hmt_last_error().decode())
+    n = _count(lib().glia_hmt_tree_energies(_np(order), len(order), _np(mp), _np(lab), _np(par), _np(c0), _np(c1), _np(e[0]), _np(e[1]), _np(e[2]),
+                                            _np(e[3]), cap))
     return tuple(a[:n].copy() for a in [lab, par, c0, c1] + e)
 
 
@@ -549,7 +544,7 @@ def tree_energy_tuples(child0, child1, em, es):
     c0 = np.ascontiguousarray(child0, np.int32); c1 = np.ascontiguousarray(child1, np.int32)
     em = np.ascontiguousarray(em, np.float64); es = np.ascontiguousarray(es, np.float64)
     Em = np.empty(max(len(c0), 1), np.float64); Es = np.empty(max(len(c0), 1), np.float64)
-    _check(lib().glia_hmt_tree_energy_tuples(_np(c0), _np(c1), _np(em), _np(es), C.c_int64(len(c0)), _np(Em), _np(Es)))
+    _check(lib().glia_hmt_tree_energy_tuples(_np(c0), _np(c1), _np(em), _np(es), len(c0), _np(Em), _np(Es)))
     return Em[:len(c0)].copy(), Es[:len(c0)].copy()
 
 
@@ -558,10 +553,7 @@ def resolve_tree_ccm(child0, child1, Em, Es):
     c0 = np.ascontiguousarray(child0, np.int32); c1 = np.ascontiguousarray(child1, np.int32)
     Em = np.ascontiguousarray(Em, np.float64); Es = np.ascontiguousarray(Es, np.float64)
     picks = np.empty(max(len(c0), 1), np.int32)
-    f = lib().glia_hmt_resolve_tree_ccm; f.restype = C.c_int64
-    n = f(_np(c0), _np(c1), _np(Em), _np(Es), C.c_int64(len(c0)), _np(picks), C.c_int64(len(picks)))
-    if n < 0:
-        raise HmtError(int(n), lib().glia_hmt_last_error().decode())
+    n = _count(lib().glia_hmt_resolve_tree_ccm(_np(c0), _np(c1), _np(Em), _np(Es), len(c0), _np(picks), len(picks)))
     return picks[:n].copy()
 
 
@@ -570,13 +562,14 @@ def tree_ccm_confidence(parent, child0, child1, es, Em, Es):
     par = np.ascontiguousarray(parent, np.int32); c0 = np.ascontiguousarray(child0, np.int32); c1 = np.ascontiguousarray(child1, np.int32)
     es = np.ascontiguousarray(es, np.float64); Em = np.ascontiguousarray(Em, np.float64); Es = np.ascontiguousarray(Es, np.float64)
     out = [np.empty(max(len(par), 1), np.float64) for _ in range(3)]
-    _check(lib().glia_hmt_tree_ccm_confidence(_np(par), _np(c0), _np(c1), _np(es), _np(Em), _np(Es), C.c_int64(len(par)), _np(out[0]), _np(out[1]),
+    _check(lib().glia_hmt_tree_ccm_confidence(_np(par), _np(c0), _np(c1), _np(es), _np(Em), _np(Es), len(par), _np(out[0]), _np(out[1]),
                                               _np(out[2])))
     return tuple(a[:len(par)].copy() for a in out)
 
 
-def _resolve_trees(L, prefix, trees, ptr):
-    """trees: list of (label, parent, child0, child1, potential)"""
+def resolve_trees_greedy(trees):
+    """resolveTreeGreedy over several trees (hmt/tree_greedy.hxx:104-152) -> (tree index, node index) per pick.
+    trees: list of (label, parent, child0, child1, potential)"""
     nt = len(trees)
     keep = [[np.ascontiguousarray(t[0], np.uint32), np.ascontiguousarray(t[1], np.int32), np.ascontiguousarray(t[2], np.int32),
              np.ascontiguousarray(t[3], np.int32), np.ascontiguousarray(t[4], np.float64)] for t in trees]
@@ -584,29 +577,22 @@ def _resolve_trees(L, prefix, trees, ptr):
     arr = lambda j: (C.c_void_p * nt)(*[k[j].ctypes.data for k in keep])
     tot = sum(len(k[0]) for k in keep)
     pt = np.empty(max(tot, 1), np.int32); pn = np.empty(max(tot, 1), np.int32)
-    f = getattr(L, prefix + "resolve_trees_greedy"); f.restype = C.c_int64
-    n = f(C.c_int(nt), nn, arr(0), arr(1), arr(2), arr(3), arr(4), ptr(pt), ptr(pn), C.c_int64(len(pt)))
+    n = lib().glia_hmt_resolve_trees_greedy(nt, nn, arr(0), arr(1), arr(2), arr(3), arr(4), _np(pt), _np(pn), len(pt))
     assert n >= 0
     return pt[:n].copy(), pn[:n].copy()
 
 
-def resolve_trees_greedy(trees):
-    """resolveTreeGreedy over several trees (hmt/tree_greedy.hxx:104-152) -> (tree index, node index) per pick."""
-    return _resolve_trees(lib(), "glia_hmt_", trees, _np)
-
-
-class RandomForest:
+class RandomForest(_Handle):
     """alg::RandomForest / alg::EnsembleRandomForest (alg/rf.hxx) loaded from GLIA model files onto the device."""
+    _free = "glia_hmt_forest_free"
 
     def __init__(self, ctx, model_files, predict_label=-1, distributor_args=None):
         if isinstance(model_files, str):
             model_files = [model_files]
         arr = (C.c_char_p * len(model_files))(*[m.encode() for m in model_files])
         dist = (C.c_double * 3)(*distributor_args) if distributor_args is not None else None
-        self.h = C.c_void_p()
         self.ctx = ctx
-        _check(lib().glia_hmt_forest_load(ctx.h, C.c_int(len(model_files)), arr, C.c_int(predict_label), dist,
-                                          C.byref(self.h)))
+        self.h = _new(lib().glia_hmt_forest_load, ctx.h, len(model_files), arr, predict_label, dist)
 
     def predict(self, rows):
         """pred_rf (ml/rf/main_pred_rf.cxx:28-38): the classifier's value for every row of an [n, dim] float64 array -- what bc_feat and
@@ -617,87 +603,68 @@ class RandomForest:
             rows = np.ascontiguousarray(rows, dtype=np.float64)
             assert rows.ndim == 2
             out = np.empty(rows.shape[0], np.float64)
-            _check(lib().glia_hmt_forest_predict(self.ctx.h, self.h, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(out)))
+            _check(lib().glia_hmt_forest_predict(self.ctx.h, self.h, _np(rows), rows.shape[0], rows.shape[1], _np(out)))
             return out
         import torch
         assert rows.is_cuda and rows.dtype == torch.float64 and rows.dim() == 2 and (rows.shape[1] == 0 or rows.stride(1) == 1)
         assert rows.shape[0] <= 1 or rows.stride(0) >= rows.shape[1]
         out = torch.empty(rows.shape[0], dtype=torch.float64, device=rows.device)
         _fence(rows)
-        _check(lib().glia_hmt_forest_predict_device(self.ctx.h, self.h, C.c_void_p(rows.data_ptr()), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]),
-                                                    C.c_int64(rows.stride(0) if rows.shape[0] > 1 else rows.shape[1]), C.c_void_p(out.data_ptr())))
+        _check(lib().glia_hmt_forest_predict_device(self.ctx.h, self.h, rows.data_ptr(), rows.shape[0], rows.shape[1],
+                                                    rows.stride(0) if rows.shape[0] > 1 else rows.shape[1], out.data_ptr()))
         self.ctx.sync()
         return out
-
-    def close(self):
-        if self.h:
-            lib().glia_hmt_forest_free(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class FeatureStubClassifier(RandomForest):
     """Diagnostic scorer P(merge) = 1 - x[index] (tests; SURVEY.md Appendix D recipe P4)."""
 
     def __init__(self, ctx, index):
-        self.h = C.c_void_p()
         self.ctx = ctx
-        _check(lib().glia_hmt_forest_stub(ctx.h, C.c_int(index), C.byref(self.h)))
+        self.h = _new(lib().glia_hmt_forest_stub, ctx.h, index)
 
 
 def mlp_limits(n1=10, n2=10):
     """glia_hmt_mlp_limits: the tier boundaries of MLP.predict under hidden layers of n1 and n2 units (0, 0: logsig) -- stage_max_dim (the
     longest row staged in LDS; longer rows are read from global memory; 0: none), unit_block (hidden units a thread accumulates at a
     time), slots (waves that split a layer), max_hidden, max_dim.  Host-only."""
-    v = [C.c_int() for _ in range(5)]
-    _check(lib().glia_hmt_mlp_limits(C.c_int(n1), C.c_int(n2), *[C.byref(x) for x in v]))
-    return dict(zip(("stage_max_dim", "unit_block", "slots", "max_hidden", "max_dim"), (x.value for x in v)))
+    return dict(zip(("stage_max_dim", "unit_block", "slots", "max_hidden", "max_dim"), _outs(lib().glia_hmt_mlp_limits, (C.c_int,) * 5, n1, n2)))
 
 
 def mlp_loop_limits():
     """glia_hmt_mlp_loop_limits: the most units per hidden layer of an MLP that RegionMap.merge_order_bc takes.  Host-only."""
-    v = C.c_int()
-    _check(lib().glia_hmt_mlp_loop_limits(C.byref(v)))
-    return {"max_hidden": v.value}
+    return dict(zip(("max_hidden",), _outs(lib().glia_hmt_mlp_loop_limits, (C.c_int,))))
 
 
 def mlp_tile_rows(dim, n1, n2):
     """glia_hmt_mlp_predict_tile_rows: (rows of a workgroup's tile, whether rows of dim columns are staged in LDS).  Host-only."""
     staged = C.c_int()
-    r = lib().glia_hmt_mlp_predict_tile_rows(C.c_int(dim), C.c_int(n1), C.c_int(n2), C.byref(staged))
-    if r < 0:
-        raise HmtError(r, lib().glia_hmt_last_error().decode())
+    r = _count(lib().glia_hmt_mlp_predict_tile_rows(dim, n1, n2, C.byref(staged)))
     return r, bool(staged.value)
 
 
 def mlp_file_parse(path):
     """glia_hmt_mlp_file_parse: the weights of a model file (readData(w, file, true)).  Host-only."""
-    n = C.c_int64()
-    _check(lib().glia_hmt_mlp_file_parse(str(path).encode(), None, C.c_int64(0), C.byref(n)))
-    w = np.empty(n.value, np.float64)
-    _check(lib().glia_hmt_mlp_file_parse(str(path).encode(), _np(w), C.c_int64(n.value), C.byref(n)))
+    n, = _outs(lib().glia_hmt_mlp_file_parse, (C.c_int64,), str(path).encode(), None, 0)
+    w = np.empty(n, np.float64)
+    _outs(lib().glia_hmt_mlp_file_parse, (C.c_int64,), str(path).encode(), _np(w), n)
     return w
 
 
-class MLP:
+class MLP(_Handle):
     """alg::MLP2v / alg::EnsembleMLP2v (alg/nn.hxx) -- pred_mlp's classifier (sshmt/main_pred_mlp.cxx): one model file or three with
     distributor_args = (dim0, dim1, threshold), hidden layers of n1 and n2 units, an optional min/max file to rescale rows by.
     ctx = None gives a host-only model (predict_host).  The arithmetic: DESIGN 3.13."""
+    _free = "glia_hmt_mlp_free"
 
     def __init__(self, ctx, model_files, n1, n2, minmax=None, distributor_args=None):
         if isinstance(model_files, (str, os.PathLike)):
             model_files = [model_files]
         arr = (C.c_char_p * len(model_files))(*[str(m).encode() for m in model_files])
         dist = (C.c_double * 3)(*distributor_args) if distributor_args is not None else None
-        self.h = C.c_void_p()
         self.ctx = ctx
-        _check(lib().glia_hmt_mlp_load(ctx.h if ctx is not None else None, C.c_int(len(model_files)), arr, C.c_int(n1), C.c_int(n2),
-                                       str(minmax).encode() if minmax is not None else None, dist, C.byref(self.h)))
+        self.h = _new(lib().glia_hmt_mlp_load, ctx.h if ctx is not None else None, len(model_files), arr, n1, n2,
+                      str(minmax).encode() if minmax is not None else None, dist)
 
     @classmethod
     def from_arrays(cls, ctx, weights, n1, n2, mn=None, mx=None, distributor_args=None):
@@ -705,18 +672,14 @@ class MLP:
         if isinstance(weights, np.ndarray):
             weights = [weights]
         ws = [np.ascontiguousarray(w, dtype=np.float64) for w in weights]
-        self = cls.__new__(cls)
-        self.h = C.c_void_p()
-        self.ctx = ctx
         ptrs = (C.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
         lens = (C.c_int64 * len(ws))(*[w.size for w in ws])
         dist = (C.c_double * 3)(*distributor_args) if distributor_args is not None else None
         if mn is not None:
             mn = np.ascontiguousarray(mn, dtype=np.float64); mx = np.ascontiguousarray(mx, dtype=np.float64)
-        _check(lib().glia_hmt_mlp_create(ctx.h if ctx is not None else None, C.c_int(len(ws)), ptrs, lens, C.c_int(n1), C.c_int(n2),
-                                         _np(mn) if mn is not None else None, _np(mx) if mn is not None else None,
-                                         C.c_int64(min(mn.size, mx.size) if mn is not None else 0), dist, C.byref(self.h)))
-        return self
+        h = _new(lib().glia_hmt_mlp_create, ctx.h if ctx is not None else None, len(ws), ptrs, lens, n1, n2, _np(mn),
+                 _np(mx) if mn is not None else None, min(mn.size, mx.size) if mn is not None else 0, dist)
+        return cls._wrap(h, ctx=ctx)
 
     @property
     def dim(self):
@@ -728,7 +691,7 @@ class MLP:
         rows = np.ascontiguousarray(rows, dtype=np.float64)
         assert rows.ndim == 2
         pred = np.empty(rows.shape[0], np.float64); logit = np.empty(rows.shape[0], np.float64)
-        _check(lib().glia_hmt_mlp_predict_host(self.h, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(pred), _np(logit)))
+        _check(lib().glia_hmt_mlp_predict_host(self.h, _np(rows), rows.shape[0], rows.shape[1], _np(pred), _np(logit)))
         return (pred, logit) if want_logits else pred
 
     def predict(self, rows, want_logits=False):
@@ -742,7 +705,7 @@ class MLP:
             rows = np.ascontiguousarray(rows, dtype=np.float64)
             assert rows.ndim == 2
             pred = np.empty(rows.shape[0], np.float64); logit = np.empty(rows.shape[0], np.float64)
-            _check(lib().glia_hmt_mlp_predict(self.ctx.h, self.h, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(pred), _np(logit)))
+            _check(lib().glia_hmt_mlp_predict(self.ctx.h, self.h, _np(rows), rows.shape[0], rows.shape[1], _np(pred), _np(logit)))
             return (pred, logit) if want_logits else pred
         import torch
         assert rows.is_cuda and rows.dtype == torch.float64 and rows.dim() == 2 and (rows.shape[1] == 0 or rows.stride(1) == 1)
@@ -750,22 +713,10 @@ class MLP:
         pred = torch.empty(rows.shape[0], dtype=torch.float64, device=rows.device)
         logit = torch.empty(rows.shape[0], dtype=torch.float64, device=rows.device) if want_logits else None
         _fence(rows)
-        _check(lib().glia_hmt_mlp_predict_device(self.ctx.h, self.h, C.c_void_p(rows.data_ptr()), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]),
-                                                 C.c_int64(rows.stride(0) if rows.shape[0] > 1 else rows.shape[1]), C.c_void_p(pred.data_ptr()),
-                                                 C.c_void_p(logit.data_ptr()) if want_logits else None))
+        _check(lib().glia_hmt_mlp_predict_device(self.ctx.h, self.h, rows.data_ptr(), rows.shape[0], rows.shape[1],
+                                                 rows.stride(0) if rows.shape[0] > 1 else rows.shape[1], pred.data_ptr(), _ptr(logit)))
         self.ctx.sync()
         return (pred, logit) if want_logits else pred
-
-    def close(self):
-        if self.h:
-            lib().glia_hmt_mlp_free(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Logsig(MLP):
@@ -805,16 +756,13 @@ MLP_TRAIN_RECORD = np.dtype([("fx", np.float64), ("xnorm", np.float64), ("gnorm"
 
 def mlp_train_limits():
     """glia_hmt_mlp_train_limits: rows of a chunk of the gradient's reduction, the most hidden units, the most columns"""
-    v = [C.c_int() for _ in range(3)]
-    _check(lib().glia_hmt_mlp_train_limits(*[C.byref(x) for x in v]))
-    return dict(zip(("chunk_rows", "max_hidden", "max_dim"), (x.value for x in v)))
+    return dict(zip(("chunk_rows", "max_hidden", "max_dim"), _outs(lib().glia_hmt_mlp_train_limits, (C.c_int,) * 3)))
 
 
 def mlp_init_weights(seed, n):
     """glia_hmt_mlp_init_weight: the first n initial weights of an MLP under seed.  Host-only."""
     f = lib().glia_hmt_mlp_init_weight
-    f.restype = C.c_double
-    return np.array([f(C.c_uint64(seed), C.c_uint64(p)) for p in range(n)], np.float64)
+    return np.array([f(seed, p) for p in range(n)], np.float64)
 
 
 def rows_minmax(blocks):
@@ -827,20 +775,20 @@ def rows_minmax(blocks):
     ptrs = (C.c_void_p * len(keep))(*[b.ctypes.data for b in keep])
     lens = (C.c_int64 * len(keep))(*[b.shape[0] for b in keep])
     mn = np.empty(dim, np.float64); mx = np.empty(dim, np.float64)
-    _check(lib().glia_hmt_rows_minmax(ptrs, lens, C.c_int(len(keep)), C.c_int(dim), _np(mn), _np(mx)))
+    _check(lib().glia_hmt_rows_minmax(ptrs, lens, len(keep), dim, _np(mn), _np(mx)))
     return mn, mx
 
 
-class MLPModel:
+class MLPModel(_Handle):
     """A trained MLP / logsig model on the host (glia_hmt_mlp_model): the weights after every sigma round, the optimiser's trace, the
     sigmas, whether training stopped on a value that was not finite."""
+    _free = "glia_hmt_mlp_model_free"
 
     def __init__(self, handle, n1, n2):
         self.h = handle
         self.n1, self.n2 = n1, n2
-        v = (C.c_int(), C.c_int64(), C.c_int64(), C.c_int(), C.c_int64(), C.c_int())
-        _check(lib().glia_hmt_mlp_model_info(self.h, *[C.byref(x) for x in v]))
-        self.rounds, self.n_weights, n_trace, stopped, self.n_used_rows, n_sigma = (x.value for x in v)
+        info = _outs(lib().glia_hmt_mlp_model_info, (C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int), self.h)
+        self.rounds, self.n_weights, n_trace, stopped, self.n_used_rows, n_sigma = info
         self.stopped_nonfinite = bool(stopped)
         self.trace = np.zeros(n_trace, MLP_TRAIN_RECORD)
         _check(lib().glia_hmt_mlp_model_trace(self.h, _np(self.trace) if n_trace else None))
@@ -849,37 +797,20 @@ class MLPModel:
         # the merge-path term's (train_sshmt): sigma_u^2 per sigma update (zeros while the term is off), its paths and unlabelled rows
         self.sigma_u2 = np.zeros(n_sigma); self.sigma_u2_eval = np.zeros(n_sigma)
         _check(lib().glia_hmt_mlp_model_sigmas_u(self.h, _np(self.sigma_u2), _np(self.sigma_u2_eval)))
-        v = (C.c_int64(), C.c_int64())
-        _check(lib().glia_hmt_mlp_model_paths(self.h, *[C.byref(x) for x in v]))
-        self.n_paths, self.n_uns_rows = (x.value for x in v)
+        self.n_paths, self.n_uns_rows = _outs(lib().glia_hmt_mlp_model_paths, (C.c_int64, C.c_int64), self.h)
 
     def weights(self, round=-1):
         w = np.empty(self.n_weights, np.float64)
-        _check(lib().glia_hmt_mlp_model_weights(self.h, C.c_int(round), _np(w)))
+        _check(lib().glia_hmt_mlp_model_weights(self.h, round, _np(w)))
         return w
 
     def write(self, path, round=-1):
         """one %.17g double per line: reads back bit for bit (mlp_file_parse, MLP(...))"""
-        _check(lib().glia_hmt_mlp_model_write(self.h, str(path).encode(), C.c_int(round)))
+        _check(lib().glia_hmt_mlp_model_write(self.h, str(path).encode(), round))
 
     def mlp(self, ctx, round=-1):
         """the classifier MLP.predict / RegionMap.merge_order_bc take, with the min/max table the training used; ctx None: host-only"""
-        m = MLP.__new__(MLP)
-        m.h = C.c_void_p()
-        m.ctx = ctx
-        _check(lib().glia_hmt_mlp_model_create_mlp(ctx.h if ctx is not None else None, self.h, C.c_int(round), C.byref(m.h)))
-        return m
-
-    def close(self):
-        if self.h:
-            lib().glia_hmt_mlp_model_free(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return MLP._wrap(_new(lib().glia_hmt_mlp_model_create_mlp, ctx.h if ctx is not None else None, self.h, round), ctx=ctx)
 
 
 def _train_args(who, o, n1, n2, dim, minmax, init, opts):
@@ -921,8 +852,7 @@ def train_mlp(ctx, rows, labels, n1=10, n2=10, minmax=None, init=None, **opts):
     o = MLPTrainOpts()
     lib().glia_hmt_mlp_train_opts_default(C.byref(o))
     args, h, keep = _train_args("train_mlp", o, n1, n2, rows.shape[1], minmax, init, opts)
-    _check(lib().glia_hmt_mlp_train(ctx.h if ctx is not None else None, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(labels),
-                                    *args))
+    _check(lib().glia_hmt_mlp_train(ctx.h if ctx is not None else None, _np(rows), rows.shape[0], rows.shape[1], _np(labels), *args))
     return MLPModel(h, n1, n2)
 
 
@@ -932,9 +862,7 @@ def train_mlp_host(rows, labels, n1=10, n2=10, minmax=None, init=None, **opts):
 
 
 def last_mlp_train_timing(ctx):
-    t = MLPTrainTiming()
-    _check(lib().glia_hmt_last_mlp_train_timing(ctx.h, C.byref(t)))
-    return {k: getattr(t, k) for k, _ in MLPTrainTiming._fields_}
+    return _struct_out(lib().glia_hmt_last_mlp_train_timing, MLPTrainTiming, ctx.h)
 
 
 class SSHMTTrainOpts(C.Structure):
@@ -960,7 +888,7 @@ def merge_paths(order, max_len=3, min_len=2):
     int64 arrays of merge indices, bottom-up, by ascending first member.  Host-only."""
     o = np.ascontiguousarray(order, dtype=np.uint32).reshape(-1, 3)
     n_paths, n_members = C.c_int64(0), C.c_int64(0)
-    args = (_np(o) if len(o) else None, C.c_int64(len(o)), C.c_int(max_len), C.c_int(min_len), C.byref(n_paths), C.byref(n_members))
+    args = (_np(o) if len(o) else None, len(o), max_len, min_len, C.byref(n_paths), C.byref(n_members))
     _check(lib().glia_hmt_merge_paths(*args, None, None))
     off = np.zeros(n_paths.value + 1, np.int64); mem = np.zeros(max(n_members.value, 1), np.int64)
     _check(lib().glia_hmt_merge_paths(*args, _np(off), _np(mem)))
@@ -993,8 +921,8 @@ def train_sshmt(ctx, rows, labels, unlabelled=(), n1=10, n2=10, minmax=None, ini
     o = SSHMTTrainOpts()
     lib().glia_hmt_sshmt_train_opts_default(C.byref(o))
     args, h, keep = _train_args("train_sshmt", o, n1, n2, dim, minmax, init, opts)
-    _check(lib().glia_hmt_sshmt_train(ctx.h if ctx is not None else None, _np(rows) if len(rows) else None, C.c_int64(rows.shape[0]), C.c_int(dim),
-                                      _np(labels) if len(labels) else None, arr, C.c_int(len(blocks)), *args))
+    _check(lib().glia_hmt_sshmt_train(ctx.h if ctx is not None else None, _np(rows) if len(rows) else None, rows.shape[0], dim,
+                                      _np(labels) if len(labels) else None, arr, len(blocks), *args))
     return MLPModel(h, n1, n2)
 
 
@@ -1005,11 +933,7 @@ def train_sshmt_host(rows, labels, unlabelled=(), n1=10, n2=10, minmax=None, ini
 
 def last_sshmt_train_timing(ctx):
     """the last train_sshmt call of the context: the supervised evaluator's fields under "sup", then the merge-path term's stages"""
-    t = SSHMTTrainTiming()
-    _check(lib().glia_hmt_last_sshmt_train_timing(ctx.h, C.byref(t)))
-    out = {k: getattr(t, k) for k, _ in SSHMTTrainTiming._fields_ if k != "sup"}
-    out["sup"] = {k: getattr(t.sup, k) for k, _ in MLPTrainTiming._fields_}
-    return out
+    return _struct_out(lib().glia_hmt_last_sshmt_train_timing, SSHMTTrainTiming, ctx.h)
 
 
 class BatchOpts(C.Structure):
@@ -1047,8 +971,8 @@ def train_mlp_batches(ctx, rows, labels, n1=10, n2=10, minmax=None, init=None, b
     lib().glia_hmt_mlp_train_opts_default(C.byref(o))
     bo = _batch_opts(batch)
     args, h, keep = _train_args("train_mlp_batches", o, n1, n2, rows.shape[1], minmax, init, opts)
-    _check(lib().glia_hmt_mlp_train_batches(ctx.h if ctx is not None else None, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]),
-                                            _np(labels), args[0], C.byref(bo), *args[1:]))
+    _check(lib().glia_hmt_mlp_train_batches(ctx.h if ctx is not None else None, _np(rows), rows.shape[0], rows.shape[1], _np(labels), args[0],
+                                            C.byref(bo), *args[1:]))
     return MLPModel(h, n1, n2)
 
 
@@ -1060,9 +984,8 @@ def train_sshmt_batches(ctx, rows, labels, unlabelled=(), n1=10, n2=10, minmax=N
     lib().glia_hmt_sshmt_train_opts_default(C.byref(o))
     bo = _batch_opts(batch)
     args, h, keep = _train_args("train_sshmt_batches", o, n1, n2, dim, minmax, init, opts)
-    _check(lib().glia_hmt_sshmt_train_batches(ctx.h if ctx is not None else None, _np(rows) if len(rows) else None, C.c_int64(rows.shape[0]),
-                                              C.c_int(dim), _np(labels) if len(labels) else None, arr, C.c_int(len(blocks)), args[0], C.byref(bo),
-                                              *args[1:]))
+    _check(lib().glia_hmt_sshmt_train_batches(ctx.h if ctx is not None else None, _np(rows) if len(rows) else None, rows.shape[0], dim,
+                                              _np(labels) if len(labels) else None, arr, len(blocks), args[0], C.byref(bo), *args[1:]))
     return MLPModel(h, n1, n2)
 
 
@@ -1072,8 +995,8 @@ def batch_plan(labels, n_paths, k, sup_batch_size=-1, uns_batch_size=-1, balance
     sampler) and whether the draw ended the epoch.  Host-only."""
     labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
     n_sup, n_uns = C.c_int64(0), C.c_int64(0)
-    head = (_np(labels) if len(labels) else None, C.c_int64(len(labels)), C.c_int64(n_paths), C.c_int(sup_batch_size), C.c_int(uns_batch_size),
-            C.c_int(balance_sup_batch), C.c_double(pos_target), C.c_double(neg_target), C.c_uint64(seed), C.c_int(k), C.byref(n_sup), C.byref(n_uns))
+    head = (_np(labels) if len(labels) else None, len(labels), n_paths, sup_batch_size, uns_batch_size, balance_sup_batch, pos_target, neg_target,
+            seed, k, C.byref(n_sup), C.byref(n_uns))
     _check(lib().glia_hmt_batch_plan(*head, None, None, None, None, None))
     so = np.zeros(k + 1, np.int64); uo = np.zeros(k + 1, np.int64)
     sr = np.zeros(max(n_sup.value, 1), np.int32); up = np.zeros(max(n_uns.value, 1), np.int32)
@@ -1084,9 +1007,7 @@ def batch_plan(labels, n_paths, k, sup_batch_size=-1, uns_batch_size=-1, balance
 
 def last_batch_timing(ctx):
     """the last train_*_batches call of the context: mini-batch steps, batches, plan build and upload, the steps' device time, waits"""
-    t = BatchTiming()
-    _check(lib().glia_hmt_last_batch_timing(ctx.h, C.byref(t)))
-    return {k: getattr(t, k) for k, _ in BatchTiming._fields_}
+    return _struct_out(lib().glia_hmt_last_batch_timing, BatchTiming, ctx.h)
 
 
 class TrainOpts(C.Structure):
@@ -1111,8 +1032,9 @@ class ForestOobTiming(C.Structure):
                [(k, C.c_int64) for k in ("oob_rows", "walks_nominal", "walks_done")] + [("device_bytes", C.c_uint64)]
 
 
-class ForestModel:
+class ForestModel(_Handle):
     """A trained forest on the host (glia_hmt_forest_model): every array of the GLIA model file."""
+    _free = "glia_hmt_forest_model_free"
     _TREE = (("xbestsplit", np.float64, 1), ("treemap", np.int32, 2), ("nodestatus", np.int32, 1), ("nodeclass", np.int32, 1),
              ("bestvar", np.int32, 1))
     _CLASS = (("classwt", np.float64), ("cutoff", np.float64), ("orig_labels", np.int32), ("new_labels", np.int32))
@@ -1131,15 +1053,10 @@ class ForestModel:
         a.setdefault("new_labels", np.arange(1, nclass + 1))
         keep = [np.ascontiguousarray(a[k], dtype=t) for k, t, _ in cls._TREE] + [np.ascontiguousarray(a["ndbigtree"], dtype=np.int32)] + \
                [np.ascontiguousarray(a[k], dtype=t) for k, t in cls._CLASS]
-        h = C.c_void_p()
-        _check(lib().glia_hmt_forest_model_from_arrays(C.c_int(ntree), C.c_int(nrnodes), C.c_int(nclass), C.c_int(int(a.get("mtry", 3))),
-                                                       *[_np(x) for x in keep], C.byref(h)))
-        return cls(ctx, h)
+        return cls(ctx, _new(lib().glia_hmt_forest_model_from_arrays, ntree, nrnodes, nclass, int(a.get("mtry", 3)), *[_np(x) for x in keep]))
 
     def sizes(self):
-        v = [C.c_int() for _ in range(4)]
-        _check(lib().glia_hmt_forest_model_sizes(self.h, *[C.byref(x) for x in v]))
-        return dict(zip(("ntree", "nrnodes", "nclass", "mtry"), (x.value for x in v)))
+        return dict(zip(("ntree", "nrnodes", "nclass", "mtry"), _outs(lib().glia_hmt_forest_model_sizes, (C.c_int,) * 4, self.h)))
 
     def arrays(self):
         """dict of the model's arrays in synth_forest's layout: tree arrays [ntree, nrnodes], treemap [ntree, nrnodes, 2]"""
@@ -1156,16 +1073,15 @@ class ForestModel:
         """dict of the out-of-bag arrays of a model trained with oob=True and / or importance=True, shaped as the model file
         holds them: outcl [N], counttr [nclass, N], votes [N, nclass], oob_times [N], errtr [ntree, nclass + 1] with the integers it
         divides (err_wrong, err_seen); importance [D, nclass + 2], importanceSD [D, nclass + 1].  HmtError when the model has none."""
-        n, d, has_oob, has_imp = C.c_int64(), C.c_int(), C.c_int(), C.c_int()
-        _check(lib().glia_hmt_forest_model_oob_sizes(self.h, C.byref(n), C.byref(d), C.byref(has_oob), C.byref(has_imp)))
+        N, D, has_oob, has_imp = _outs(lib().glia_hmt_forest_model_oob_sizes, (C.c_int64, C.c_int, C.c_int, C.c_int), self.h)
         s = self.sizes()
-        N, D, nc, nt = n.value, d.value, s["nclass"], s["ntree"]
+        nc, nt = s["nclass"], s["ntree"]
         out = {}
-        if has_oob.value:
+        if has_oob:
             out.update(outcl=np.zeros(N, np.int32), counttr=np.zeros((nc, N), np.int32), votes=np.zeros((N, nc), np.int32),
                        oob_times=np.zeros(N, np.int32), errtr=np.zeros((nt, nc + 1)), err_wrong=np.zeros((nt, nc + 1), np.int64),
                        err_seen=np.zeros((nt, nc + 1), np.int64))
-        if has_imp.value:
+        if has_imp:
             out.update(importance=np.zeros((D, nc + 2)), importanceSD=np.zeros((D, nc + 1)))
         order = ("outcl", "counttr", "votes", "oob_times", "errtr", "err_wrong", "err_seen", "importance", "importanceSD")
         _check(lib().glia_hmt_forest_model_oob_arrays(self.h, *[_np(out[k]) if k in out else None for k in order]))
@@ -1176,29 +1092,15 @@ class ForestModel:
         order = (("outcl", np.int32), ("counttr", np.int32), ("votes", np.int32), ("oob_times", np.int32), ("errtr", np.float64),
                  ("importance", np.float64), ("importanceSD", np.float64))
         keep = [np.ascontiguousarray(arrays[k], dtype=t) if k in arrays else None for k, t in order]
-        _check(lib().glia_hmt_forest_model_set_oob(self.h, C.c_int64(n_rows), C.c_int(dim), *[_np(x) for x in keep]))
+        _check(lib().glia_hmt_forest_model_set_oob(self.h, n_rows, dim, *[_np(x) for x in keep]))
 
     def write(self, path):
         _check(lib().glia_hmt_forest_model_write(self.h, str(path).encode()))
 
     def forest(self, predict_label=-1, ctx=None):
         """the classifier RandomForest.predict / merge_order_bc take, without a trip through a file"""
-        f = RandomForest.__new__(RandomForest)
-        f.h = C.c_void_p()
-        f.ctx = ctx or self.ctx
-        _check(lib().glia_hmt_forest_from_model(f.ctx.h, self.h, C.c_int(predict_label), C.byref(f.h)))
-        return f
-
-    def close(self):
-        if self.h:
-            lib().glia_hmt_forest_model_free(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        ctx = ctx or self.ctx
+        return RandomForest._wrap(_new(lib().glia_hmt_forest_from_model, ctx.h, self.h, predict_label), ctx=ctx)
 
 
 def train_forest(ctx, rows, labels, oob=False, importance=False, **opts):
@@ -1214,27 +1116,21 @@ def train_forest(ctx, rows, labels, oob=False, importance=False, **opts):
         if k not in dict(TrainOpts._fields_):
             raise TypeError("train_forest: unknown option " + k)
         setattr(o, k, v)
-    h = C.c_void_p()
     if oob or importance:
         oo = OobOpts(1 if oob else 0, 1 if importance else 0)
-        _check(lib().glia_hmt_forest_train_oob(ctx.h, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(labels), C.byref(o),
-                                               C.byref(oo), C.byref(h)))
+        h = _new(lib().glia_hmt_forest_train_oob, ctx.h, _np(rows), rows.shape[0], rows.shape[1], _np(labels), C.byref(o), C.byref(oo))
     else:
-        _check(lib().glia_hmt_forest_train(ctx.h, _np(rows), C.c_int64(rows.shape[0]), C.c_int(rows.shape[1]), _np(labels), C.byref(o), C.byref(h)))
+        h = _new(lib().glia_hmt_forest_train, ctx.h, _np(rows), rows.shape[0], rows.shape[1], _np(labels), C.byref(o))
     return ForestModel(ctx, h)
 
 
 def last_forest_train_timing(ctx):
-    t = ForestTrainTiming()
-    _check(lib().glia_hmt_last_forest_train_timing(ctx.h, C.byref(t)))
-    return {k: getattr(t, k) for k, _ in ForestTrainTiming._fields_}
+    return _struct_out(lib().glia_hmt_last_forest_train_timing, ForestTrainTiming, ctx.h)
 
 
 def last_forest_oob_timing(ctx):
     """the out-of-bag passes of the last train_forest call (all zero when it asked for neither)"""
-    t = ForestOobTiming()
-    _check(lib().glia_hmt_last_forest_oob_timing(ctx.h, C.byref(t)))
-    return {k: getattr(t, k) for k, _ in ForestOobTiming._fields_}
+    return _struct_out(lib().glia_hmt_last_forest_oob_timing, ForestOobTiming, ctx.h)
 
 
 class Slab(C.Structure):
@@ -1247,20 +1143,20 @@ class DistStats(C.Structure):
     _fields_ = [("records", C.c_uint64), ("cut_records", C.c_uint64), ("bytes_cut_exchange", C.c_uint64), ("bytes_to_loop_owner", C.c_uint64)]
 
 
-class Comm:
+class Comm(_Handle):
     """glia_hmt_comm: the ranks of this process in the slab route (glia_amd/csrc/slab_dist.cpp)."""
+    _free = "glia_hmt_comm_destroy"
 
     def __init__(self, ctx, world, rank=None, unique_id=None):
         """rank None: all `world` ranks in this process on ctx's GPU (device copies); else one RCCL rank (unique_id: 128 bytes
         from Comm.unique_id() on one rank)."""
         self.ctx, self.world = ctx, world
-        self.h = C.c_void_p()
         if rank is None:
-            _check(lib().glia_hmt_comm_create_local(ctx.h, C.c_int(world), C.byref(self.h)))
+            self.h = _new(lib().glia_hmt_comm_create_local, ctx.h, world)
             self.local = list(range(world))
         else:
             buf = (C.c_char * 128).from_buffer_copy(unique_id)
-            _check(lib().glia_hmt_comm_create_rccl(ctx.h, C.c_int(world), C.c_int(rank), buf, C.byref(self.h)))
+            self.h = _new(lib().glia_hmt_comm_create_rccl, ctx.h, world, rank, buf)
             self.local = [rank]
 
     @staticmethod
@@ -1269,23 +1165,10 @@ class Comm:
         _check(lib().glia_hmt_comm_unique_id(buf))
         return bytes(buf)
 
-    def close(self):
-        if self.h:
-            lib().glia_hmt_comm_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def slab_range(nz, world, rank):
     """glia_hmt_slab_range -> (first plane handed in, planes handed in, z_begin, z_end)"""
-    a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
-    _check(lib().glia_hmt_slab_range(C.c_int64(nz), C.c_int(world), C.c_int(rank), C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
-    return a.value, b.value, c.value, d.value
+    return tuple(_outs(lib().glia_hmt_slab_range, (C.c_int64,) * 4, nz, world, rank))
 
 
 def build_distributed(ctx, comm, slabs, nz_global, only_contour=False, loop_owner=0, with_values=False):
@@ -1299,14 +1182,14 @@ def build_distributed(ctx, comm, slabs, nz_global, only_contour=False, loop_owne
         arr[i].dims_local[0], arr[i].dims_local[1], arr[i].dims_local[2] = lab.shape[2], lab.shape[1], lab.shape[0]
         arr[i].z_global_of_plane0, arr[i].z_begin, arr[i].z_end = first, zb, ze
         arr[i].d_labels = lab.data_ptr()
-        arr[i].d_pb = pb.data_ptr() if pb is not None else None
+        arr[i].d_pb = _ptr(pb)
         arr[i].cfg = C.pointer(cfg) if cfg is not None else None
         keep.append((lab, pb, cfg))
     h = C.c_void_p()
     st = DistStats()
-    _check(lib().glia_hmt_rag_build_distributed(ctx.h, comm.h, arr, C.c_int64(nz_global), C.c_int(int(only_contour)), C.c_int(int(with_values)), C.c_int(loop_owner),
-                                                C.byref(h), C.byref(st)))
-    rm = RegionMap(ctx, None, cfg=slabs[0][5], _handle=h) if h else None
+    _check(lib().glia_hmt_rag_build_distributed(ctx.h, comm.h, arr, nz_global, int(only_contour), int(with_values), loop_owner, C.byref(h),
+                                                C.byref(st)))
+    rm = RegionMap._wrap(h)._configure(ctx, slabs[0][5]) if h else None
     if rm is not None:
         rm._keep = keep
     return rm, st
@@ -1326,50 +1209,33 @@ class BcLabelTiming(C.Structure):
                 ("moves", C.c_int64), ("node_pairs", C.c_int64)]
 
 
-class RegionMap:
+class RegionMap(_Handle):
     """Device-resident region adjacency structure with sufficient statistics.
     Mirrors TRegionMap(image, mask, onlyContour) (type/region_map.hxx:38-40)."""
+    _free = "glia_hmt_rag_free"
 
-    def __init__(self, ctx, labels, pb=None, mask=None, only_contour=False, cfg=None, slab=None, _handle=None):
+    def __init__(self, ctx, labels, pb=None, mask=None, only_contour=False, cfg=None, slab=None):
         """slab = (z_global_of_plane0, nz_global, z_begin, z_end): build the PARTIAL map of a z-slab whose planes
         (plus halo planes) are `labels` / `pb` (see include/glia_hmt.h, glia_hmt_rag_build_slab)."""
-        self.ctx = ctx
-        self.cfg = cfg
-        self._keep = (labels, pb, mask, cfg)
-        self.h = C.c_void_p()
-        if _handle is not None:
-            self.h = _handle
+        self._configure(ctx, cfg, (labels, pb, mask))
+        assert labels.is_cuda and labels.is_contiguous() and labels.element_size() == 4
+        _fence(labels)
+        self.shape = tuple(labels.shape)
+        self.dim, d = _dims(self.shape)
+        cfg_ref = C.byref(cfg) if cfg is not None else None
+        if slab is None:
+            self.h = _new(lib().glia_hmt_rag_build, ctx.h, self.dim, d, labels.data_ptr(), _ptr(mask), int(only_contour), _ptr(pb), cfg_ref)
         else:
-            assert labels.is_cuda and labels.is_contiguous() and labels.element_size() == 4
-            _fence(labels)
-            self.shape = tuple(labels.shape)
-            self.dim, d = _dims(self.shape)
-            if slab is None:
-                _check(lib().glia_hmt_rag_build(
-                    ctx.h, C.c_int(self.dim), d, C.c_void_p(labels.data_ptr()),
-                    C.c_void_p(mask.data_ptr()) if mask is not None else None, C.c_int(int(only_contour)),
-                    C.c_void_p(pb.data_ptr()) if pb is not None else None,
-                    C.byref(cfg) if cfg is not None else None, C.byref(self.h)))
-            else:
-                gz0, gnz, zb, ze = slab
-                _check(lib().glia_hmt_rag_build_slab(
-                    ctx.h, d, C.c_int64(gz0), C.c_int64(gnz), C.c_int64(zb), C.c_int64(ze), C.c_void_p(labels.data_ptr()),
-                    C.c_int(int(only_contour)), C.c_void_p(pb.data_ptr()) if pb is not None else None,
-                    C.byref(cfg) if cfg is not None else None, C.byref(self.h)))
+            gz0, gnz, zb, ze = slab
+            self.h = _new(lib().glia_hmt_rag_build_slab, ctx.h, d, gz0, gnz, zb, ze, labels.data_ptr(), int(only_contour), _ptr(pb), cfg_ref)
+
+    def _configure(self, ctx, cfg, volumes=(None, None, None)):
+        """what a built map and a map around a handle the library returned (_wrap) hold alike"""
+        self.ctx, self.cfg, self._keep = ctx, cfg, volumes + (cfg,)
         self.bins = cfg.region[0].bins if cfg is not None and cfg.n_region else \
             (cfg.boundary[0].bins if cfg is not None and cfg.n_boundary else 8)
         self.nthr = cfg.n_thresholds if cfg is not None else 0
-
-    def close(self):
-        if self.h:
-            lib().glia_hmt_rag_free(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self
 
     @property
     def num_regions(self):
@@ -1386,26 +1252,23 @@ class RegionMap:
     def merge(ctx, parts):
         """glia_hmt_rag_merge: combine the partial maps of several slabs (same configuration)."""
         arr = (C.c_void_p * len(parts))(*[p.h for p in parts])
-        h = C.c_void_p()
-        _check(lib().glia_hmt_rag_merge(ctx.h, arr, C.c_int(len(parts)), C.byref(h)))
-        return RegionMap(ctx, None, cfg=parts[0].cfg, _handle=h)
+        return RegionMap._wrap(_new(lib().glia_hmt_rag_merge, ctx.h, arr, len(parts)))._configure(ctx, parts[0].cfg)
 
     def to_tensors(self):
         """The compact record arrays as torch tensors on the context's device (for torch.distributed)."""
         import torch
         dev = torch.device("cuda", self.ctx.device)
         R, P = self.num_regions, self.num_pairs
-        rw, pw = C.c_int(), C.c_int()
-        _check(lib().glia_hmt_rag_device_arrays(self.h, None, None, None, None, None, C.byref(rw), C.byref(pw)))
-        t = dict(rlabel=torch.empty(R, dtype=torch.int32, device=dev), rrec=torch.empty((R, rw.value), dtype=torch.int32, device=dev),
+        rw, pw = _outs(lib().glia_hmt_rag_device_arrays, (C.c_int, C.c_int), self.h, None, None, None, None, None)
+        t = dict(rlabel=torch.empty(R, dtype=torch.int32, device=dev), rrec=torch.empty((R, rw), dtype=torch.int32, device=dev),
                  pa=torch.empty(P, dtype=torch.int32, device=dev), pb=torch.empty(P, dtype=torch.int32, device=dev),
-                 prec=torch.empty((P, pw.value), dtype=torch.int32, device=dev))
-        _check(lib().glia_hmt_rag_copy_arrays(self.h, *[C.c_void_p(t[k].data_ptr()) for k in ("rlabel", "rrec", "pa", "pb", "prec")]))
+                 prec=torch.empty((P, pw), dtype=torch.int32, device=dev))
+        _check(lib().glia_hmt_rag_copy_arrays(self.h, *[t[k].data_ptr() for k in ("rlabel", "rrec", "pa", "pb", "prec")]))
         # further image channels (feature lists with several volumes): same keys, one more record set each
         for k in range(1, lib().glia_hmt_rag_num_channels(self.h)):
-            t["rrec%d" % k] = torch.empty((R, rw.value), dtype=torch.int32, device=dev)
-            t["prec%d" % k] = torch.empty((P, pw.value), dtype=torch.int32, device=dev)
-            _check(lib().glia_hmt_rag_copy_channel(self.h, C.c_int(k), C.c_void_p(t["rrec%d" % k].data_ptr()), C.c_void_p(t["prec%d" % k].data_ptr())))
+            t["rrec%d" % k] = torch.empty((R, rw), dtype=torch.int32, device=dev)
+            t["prec%d" % k] = torch.empty((P, pw), dtype=torch.int32, device=dev)
+            _check(lib().glia_hmt_rag_copy_channel(self.h, k, t["rrec%d" % k].data_ptr(), t["prec%d" % k].data_ptr()))
         return t
 
     def cut_flags(self, labels_slab, z_begin, z_end):
@@ -1416,30 +1279,24 @@ class RegionMap:
         rcut = torch.zeros(max(self.num_regions, 1), dtype=torch.uint8, device=dev)
         pcut = torch.zeros(max(self.num_pairs, 1), dtype=torch.uint8, device=dev)
         _fence(labels_slab)
-        _check(lib().glia_hmt_rag_cut_flags(self.ctx.h, self.h, d, C.c_int64(z_begin), C.c_int64(z_end), C.c_void_p(labels_slab.data_ptr()),
-                                            C.c_void_p(rcut.data_ptr()), C.c_void_p(pcut.data_ptr())))
+        _check(lib().glia_hmt_rag_cut_flags(self.ctx.h, self.h, d, z_begin, z_end, labels_slab.data_ptr(), rcut.data_ptr(), pcut.data_ptr()))
         return rcut[:self.num_regions].bool(), pcut[:self.num_pairs].bool()
 
     @staticmethod
     def from_tensors(ctx, like, t):
-        h = C.c_void_p()
         for k in t:
             assert t[k].is_cuda and t[k].is_contiguous()
         _fence(t["rlabel"])
-        _check(lib().glia_hmt_rag_from_arrays(ctx.h, like.h, C.c_int64(t["rlabel"].numel()), C.c_void_p(t["rlabel"].data_ptr()),
-                                              C.c_void_p(t["rrec"].data_ptr()), C.c_int64(t["pa"].numel()),
-                                              C.c_void_p(t["pa"].data_ptr()), C.c_void_p(t["pb"].data_ptr()),
-                                              C.c_void_p(t["prec"].data_ptr()), C.byref(h)))
+        h = _new(lib().glia_hmt_rag_from_arrays, ctx.h, like.h, t["rlabel"].numel(), t["rlabel"].data_ptr(), t["rrec"].data_ptr(), t["pa"].numel(),
+                 t["pa"].data_ptr(), t["pb"].data_ptr(), t["prec"].data_ptr())
         k = 1
         while "rrec%d" % k in t:
-            _check(lib().glia_hmt_rag_add_channel(ctx.h, h, C.c_void_p(t["rrec%d" % k].data_ptr()), C.c_void_p(t["prec%d" % k].data_ptr())))
+            _check(lib().glia_hmt_rag_add_channel(ctx.h, h, t["rrec%d" % k].data_ptr(), t["prec%d" % k].data_ptr()))
             k += 1
-        return RegionMap(ctx, None, cfg=like.cfg, _handle=h)
+        return RegionMap._wrap(h)._configure(ctx, like.cfg)
 
     def last_pass(self):
-        ms, by = C.c_double(), C.c_double()
-        _check(lib().glia_hmt_rag_last_pass(self.h, C.byref(ms), C.byref(by)))
-        return ms.value, by.value
+        return tuple(_outs(lib().glia_hmt_rag_last_pass, (C.c_double, C.c_double), self.h))
 
     def regions(self):
         n = self.num_regions
@@ -1465,10 +1322,8 @@ class RegionMap:
         cap = max(self.num_regions, 1)
         order = np.empty((cap, 3), np.uint32)
         sal = np.empty(cap, np.float64)
-        n = C.c_int64(0)
-        _check(lib().glia_hmt_merge_order_pb(self.ctx.h, self.h, C.c_int(type), _np(order), _np(sal), C.c_int64(cap),
-                                             C.byref(n)))
-        return order[:n.value].copy(), sal[:n.value].copy()
+        n, = _outs(lib().glia_hmt_merge_order_pb, (C.c_int64,), self.ctx.h, self.h, type, _np(order), _np(sal), cap)
+        return order[:n].copy(), sal[:n].copy()
 
     def feat_dim(self):
         return lib().glia_hmt_feat_dim(self.h)
@@ -1481,12 +1336,11 @@ class RegionMap:
         sal = np.empty(cap, np.float64)
         d = self.feat_dim()
         feats = np.empty((cap, d), np.float64) if want_feats else None
-        n = C.c_int64(0)
         fn = lib().glia_hmt_merge_order_bc_mlp if isinstance(classifier, MLP) else lib().glia_hmt_merge_order_bc
-        _check(fn(self.ctx.h, self.h, classifier.h, _np(order), _np(sal), _np(feats), C.c_int64(cap), C.byref(n)))
+        n, = _outs(fn, (C.c_int64,), self.ctx.h, self.h, classifier.h, _np(order), _np(sal), _np(feats), cap)
         if want_feats:
-            return order[:n.value].copy(), sal[:n.value].copy(), feats[:n.value].copy()
-        return order[:n.value].copy(), sal[:n.value].copy()
+            return order[:n].copy(), sal[:n].copy(), feats[:n].copy()
+        return order[:n].copy(), sal[:n].copy()
 
     def pre_merge(self, size_thresholds, rpb_threshold):
         """gadget/main_pre_merge.cxx: pb-mean merges restricted by the region-size condition."""
@@ -1494,41 +1348,33 @@ class RegionMap:
         order = np.empty((cap, 3), np.uint32)
         sal = np.empty(cap, np.float64)
         st = (C.c_int * len(size_thresholds))(*size_thresholds)
-        n = C.c_int64(0)
-        _check(lib().glia_hmt_pre_merge(self.ctx.h, self.h, st, C.c_int(len(size_thresholds)), C.c_double(rpb_threshold),
-                                        _np(order), _np(sal), C.c_int64(cap), C.byref(n)))
-        return order[:n.value].copy(), sal[:n.value].copy()
+        n, = _outs(lib().glia_hmt_pre_merge, (C.c_int64,), self.ctx.h, self.h, st, len(size_thresholds), rpb_threshold, _np(order), _np(sal), cap)
+        return order[:n].copy(), sal[:n].copy()
+
+    def _bc_feat(self, fn, order, saliencies, init_sal, sal_bias):
+        order = np.ascontiguousarray(order, dtype=np.uint32)
+        d = lib().glia_hmt_bc_feat_dim(self.h, 1 if saliencies is not None else 0)
+        feats = np.empty((len(order), d), np.float64)
+        sal = None if saliencies is None else np.ascontiguousarray(saliencies, dtype=np.float64)
+        _check(fn(self.ctx.h, self.h, _np(order), len(order), _np(sal), init_sal, sal_bias, _np(feats)))
+        return feats
 
     def bc_feat(self, order, saliencies=None, init_sal=1.0, sal_bias=1.0):
         """hmt/main_bc_feat.cxx: feature rows of a given merge order; with `saliencies` (-y) also the saliency features."""
-        order = np.ascontiguousarray(order, dtype=np.uint32)
-        d = lib().glia_hmt_bc_feat_dim(self.h, C.c_int(1 if saliencies is not None else 0))
-        feats = np.empty((len(order), d), np.float64)
-        sal = None if saliencies is None else np.ascontiguousarray(saliencies, dtype=np.float64)
-        _check(lib().glia_hmt_bc_feat_saliency(self.ctx.h, self.h, _np(order), C.c_int64(len(order)), _np(sal),
-                                               C.c_double(init_sal), C.c_double(sal_bias), _np(feats)))
-        return feats
+        return self._bc_feat(lib().glia_hmt_bc_feat_saliency, order, saliencies, init_sal, sal_bias)
 
     def bc_feat_batch(self, order, saliencies=None, init_sal=1.0, sal_bias=1.0):
         """the rows of bc_feat by the batch route (hmt/main_bc_feat.cxx:59-95 is parallel over merges too): every set of the known
         merge tree at once instead of a replay of the order; same arguments, row width and errors"""
-        order = np.ascontiguousarray(order, dtype=np.uint32)
-        d = lib().glia_hmt_bc_feat_dim(self.h, C.c_int(1 if saliencies is not None else 0))
-        feats = np.empty((len(order), d), np.float64)
-        sal = None if saliencies is None else np.ascontiguousarray(saliencies, dtype=np.float64)
-        _check(lib().glia_hmt_bc_feat_batch(self.ctx.h, self.h, _np(order), C.c_int64(len(order)), _np(sal),
-                                            C.c_double(init_sal), C.c_double(sal_bias), _np(feats)))
-        return feats
+        return self._bc_feat(lib().glia_hmt_bc_feat_batch, order, saliencies, init_sal, sal_bias)
 
     BC_FEAT_ROUTES = ("replay", "batch")
 
     def last_bc_feat_timing(self):
         """stages of the last bc_feat / bc_feat_batch call: ms_plan (host), ms_sets, ms_rows (device), height, launches,
         path_updates, route ("replay" | "batch")"""
-        t = BcFeatTiming()
-        _check(lib().glia_hmt_last_bc_feat_timing(self.h, C.byref(t)))
-        out = {k: getattr(t, k) for k, _ in BcFeatTiming._fields_}
-        out["route"] = self.BC_FEAT_ROUTES[t.route]
+        out = _struct_out(lib().glia_hmt_last_bc_feat_timing, BcFeatTiming, self.h)
+        out["route"] = self.BC_FEAT_ROUTES[out["route"]]
         return out
 
     BC_METRICS = {"f1": 0, "ri": 1, "vi": 2}
@@ -1546,22 +1392,17 @@ class RegionMap:
         ptrs = (C.c_void_p * max(len(truths), 1))(*[t.data_ptr() for t in truths])
         opts = BcLabelOpts(self.BC_METRICS[metric], int(bool(tweak)), float(mpd), int(bool(opt_split)), int(opt))
         out = np.empty(max(len(order), 1), np.int32)
-        _check(lib().glia_hmt_bc_label(self.ctx.h, self.h, ptrs, C.c_int(len(truths)), _np(order), C.c_int64(len(order)),
-                                       C.byref(opts), _np(out)))
+        _check(lib().glia_hmt_bc_label(self.ctx.h, self.h, ptrs, len(truths), _np(order), len(order), C.byref(opts), _np(out)))
         return out[:len(order)].copy()
 
     def last_bc_label_timing(self):
         """stages of the last bc_label call: ms_count (device), ms_nodes, ms_rules (host), entries, moves, node_pairs"""
-        t = BcLabelTiming()
-        _check(lib().glia_hmt_last_bc_label_timing(self.h, C.byref(t)))
-        return {k: getattr(t, k) for k, _ in BcLabelTiming._fields_}
+        return _struct_out(lib().glia_hmt_last_bc_label_timing, BcLabelTiming, self.h)
 
     def score_initial_edges(self, classifier):
         """features + scores of the initial table edges (TBoundaryTable::init) -> (edges scored, device ms).  With
         use_median_features the medians come from sorted value runs of every leaf and directed pair (whole-volume maps only)."""
-        n, ms = C.c_int64(0), C.c_double(0)
-        _check(lib().glia_hmt_score_initial_edges(self.ctx.h, self.h, classifier.h, C.byref(n), C.byref(ms)))
-        return n.value, ms.value
+        return tuple(_outs(lib().glia_hmt_score_initial_edges, (C.c_int64, C.c_double), self.ctx.h, self.h, classifier.h))
 
     def score_initial_edges_shard(self, classifier, shard, n_shards):
         """scores of the initial records e with e % n_shards == shard (-inf elsewhere); max over shards = all scores.  Works with
@@ -1569,10 +1410,9 @@ class RegionMap:
         statistics layout only."""
         cap = max(self.num_pairs, 1)
         out = np.empty(cap, np.float64)
-        n = C.c_int64(0)
         fn = lib().glia_hmt_score_initial_edges_shard_mlp if isinstance(classifier, MLP) else lib().glia_hmt_score_initial_edges_shard
-        _check(fn(self.ctx.h, self.h, classifier.h, C.c_int(shard), C.c_int(n_shards), _np(out), C.c_int64(cap), C.byref(n)))
-        return out[:n.value].copy()
+        n, = _outs(fn, (C.c_int64,), self.ctx.h, self.h, classifier.h, shard, n_shards, _np(out), cap)
+        return out[:n].copy()
 
     def boundary_confidence(self, trees):
         """segment_greedy -b (genBoundaryConfidenceImage, all nodes): float32 CUDA tensor of the volume's shape"""
@@ -1583,10 +1423,9 @@ class RegionMap:
         nn = (C.c_int64 * nt)(*[len(k[0]) for k in keep])
         arr = lambda j: (C.c_void_p * nt)(*[k[j].ctypes.data for k in keep])
         out = torch.empty(self.shape, dtype=torch.float32, device=torch.device("cuda", self.ctx.device))
-        _check(lib().glia_hmt_boundary_confidence(self.ctx.h, self.h, C.c_int(nt), nn, arr(0), arr(1), arr(2), arr(3), C.c_void_p(out.data_ptr())))
+        _check(lib().glia_hmt_boundary_confidence(self.ctx.h, self.h, nt, nn, arr(0), arr(1), arr(2), arr(3), out.data_ptr()))
         return out
 
     def last_merge_timing(self):
-        a, b, c, n = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
-        _check(lib().glia_hmt_last_merge_timing(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
-        return dict(ms_table=a.value, ms_init=b.value, ms_loop=c.value, n_edges_scored=n.value)
+        return dict(zip(("ms_table", "ms_init", "ms_loop", "n_edges_scored"),
+                        _outs(lib().glia_hmt_last_merge_timing, (C.c_double, C.c_double, C.c_double, C.c_int64), self.h)))
